@@ -1,6 +1,6 @@
 """Headline benchmark: score-vector evals/sec (+ SVD wall-clock) of the manifold_dimension path, 32x32x3 NCSN++.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -8,14 +8,18 @@ One step = one data point of BASELINE config 3: 4480 score rows (B=128 -> (1024/
 empty; dim_reduction.py:166-171) of the nf=128 NCSN++ on a synthetic 32x32x3 image, written into the
 device-resident S [4480, 3072], then its centred singular spectrum and the integer ID.  Inputs (image, weights)
 are resident in HBM before the timed region.  With N ranks every rank processes K points of its own (weak
-scaling) and the region ends with the one exchange step the path has (parallel.gather_spectra).
+scaling) and the region ends with the one exchange step the path has (parallel.gather_spectra).  Weights, images
+and noise are seeded: the same arguments give the same inputs in every run.
 
-Passes, in order:
+A plain run does pass 1 only; --full adds passes 2-5 (each still subject to its --no-* switch):
   1. warm-up (W points), then the TIMED region (K points, no instrumentation)            -> value, ms_per_step
   2. the same K points again with HIP events around the instrumented launches (rank 0)   -> roofline, roofline.kernels
   3. the spectrum stages of one point, alone on the device                                -> svd_wall_clock_ms_per_point
   4. extra.cfg2 / extra.cfg5: KSphere + fcn and 64x64 BeatGANs side measurements (rank 0, N = 1, seconds each)
   5. cpu_baseline: the oracle on this box's host cores, bounded sample (rank 0, N = 1)
+Without --full, roofline and svd_wall_clock_ms_per_point are null and extra / cpu_baseline are absent.
+
+--dump-outputs DIR: right after pass 1, rank 0 writes what the last timed step computed (see dump_outputs).
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -658,16 +662,44 @@ def timed_region(work, warmup, steps, dev):
     return elapsed, allsv, alldims
 
 
+DUMP_SCORE_ROWS = 1024          # rows of S in score_rows.npy: 12.6 MB of the 55 MB matrix at config 3
+
+
+def dump_outputs(out_dir, allsv, alldims, world, steps, last_S):
+    """What the caller of the timed path receives for the last timed step, as .npy files in ``out_dir``:
+      singular_values.npy  float64 [world, D]  the centred spectra of the step's points, in rank order
+      id_estimates.npy     float64 [world]     their integer IDs
+      score_rows.npy       float32 [n, D]      rows of rank 0's score matrix S of that step: a fixed sample of
+                                               DUMP_SCORE_ROWS rows (generator seed 0, ascending), all rows if fewer
+    ``allsv`` / ``alldims``: the gathered layout of timed_region (point p = rank p % world, step p // world)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    last = slice((steps - 1) * world, steps * world)
+    np.save(os.path.join(out_dir, "singular_values.npy"), allsv[last].cpu().double().numpy())
+    np.save(os.path.join(out_dir, "id_estimates.npy"), torch.as_tensor(alldims)[last].cpu().double().numpy())
+    if last_S is not None:
+        rows = last_S.shape[0]
+        if rows > DUMP_SCORE_ROWS:
+            pick = torch.randperm(rows, generator=torch.Generator().manual_seed(0))[:DUMP_SCORE_ROWS].sort().values
+            last_S = last_S[pick.to(last_S.device)]
+        np.save(os.path.join(out_dir, "score_rows.npy"), last_S.float().cpu().numpy())
+
+
 def main(argv=None, workload_factory=Workload):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--inflight", type=int, default=2240, help="score rows per launch set (measured best of 512..4480)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the instrumented pass, the spectrum stages, the config-2 / config-5 side "
+                         "measurements and the CPU baseline (a plain run times the headline loop only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/*.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--no-overlap", action="store_true", help="run each point's spectrum on the main stream")
-    ap.add_argument("--no-probe", action="store_true", help="skip the instrumented second pass (roofline = null)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the config-2 / config-5 side measurements (extra = null)")
+    ap.add_argument("--no-probe", action="store_true", help="(--full) skip the instrumented second pass (roofline = null)")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) skip the config-2 / config-5 side measurements (extra = null)")
     ap.add_argument("--concurrent-sets", type=int, default=1,
                     help="launch sets of a point on this many worker streams (2: -1.8 %% per point; per-kernel events then overlap)")
     ap.add_argument("--device", default=None, help="(tests) 'cpu' with a stand-in workload")
@@ -704,10 +736,12 @@ def main(argv=None, workload_factory=Workload):
     work = workload_factory(args, rank, dev)
     with torch.no_grad():
         elapsed, allsv, alldims = timed_region(work, args.warmup, args.steps, dev)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, allsv, alldims, world, args.steps, work.last_S)
     rows, D = work.rows, work.D
     line = None
-    if dev.type == "cuda":
-        roofline, svd_ms, stages = None, None, None
+    roofline, svd_ms = None, None
+    if dev.type == "cuda" and args.full:
         if rank == 0 and not args.no_probe:
             probe = KernelProbe()
             probe.install()
@@ -746,7 +780,7 @@ def main(argv=None, workload_factory=Workload):
             line["model_tflops_per_gpu_direct_conv_equivalent"] = rows * args.steps * 21.79e9 / elapsed / 1e12
             line["svd_wall_clock_ms_per_point"] = svd_ms
             line["roofline"] = roofline
-            if world == 1 and not args.no_extras:
+            if args.full and world == 1 and not args.no_extras:
                 # the other workloads north_star names, each bounded to a few seconds; not part of `value`
                 last_S, work.last_S = work.last_S, None
                 del work.model, work.builder, work.pipe
@@ -754,7 +788,7 @@ def main(argv=None, workload_factory=Workload):
                 with torch.no_grad():
                     line["extra"] = {"cfg2": extra_cfg2(dev), "cfg5": extra_cfg5(dev)}
                 work.last_S = last_S
-            if world == 1 and not args.no_cpu_baseline:
+            if args.full and world == 1 and not args.no_cpu_baseline:
                 line["cpu_baseline"] = cpu_baseline(work.cfg, rows, D, work.last_S)
         print(json.dumps(line))
     if dist.is_available() and dist.is_initialized():

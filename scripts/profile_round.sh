@@ -2,8 +2,8 @@
 # Everything profiles/ holds for one round, in one GPU-box call:  bash scripts/profile_round.sh r01
 #   1. FETCH_SIZE / WRITE_SIZE passes over scripts/wino_shapes.py  -> profiles/<tag>_wino_traffic.json
 #   2. PMC passes over one dominant-kernel shape (MFMA busy, waits, LDS)      -> gpurun_out/<tag>_pmc.log
-#   3. rocprofv3 --kernel-trace --stats of the default bench (no cpu baseline) -> <tag>_kernel_stats.csv, <tag>_bench_under_rocprof.json
-#   4. the plain default bench with cpu_baseline                             -> <tag>_bench.json
+#   3. rocprofv3 --kernel-trace --stats of the --full bench (no cpu baseline)  -> <tag>_kernel_stats.csv, <tag>_bench_under_rocprof.json
+#   4. the --full bench with cpu_baseline                                    -> <tag>_bench.json
 set -uo pipefail
 TAG=${1:-r02}
 R=$GRAFT_REPO_ROOT
@@ -57,12 +57,12 @@ PY
 cat $O/${TAG}_pmc_winograd.txt
 echo "[3] kernel stats of the bench"
 cd $R
-( cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $O/${TAG}_bench_under_rocprof.json 2> $O/bench_under_rocprof.err ) || echo "stats run failed"
+( cd "$TMPDIR" && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-extras > $O/${TAG}_bench_under_rocprof.json 2> $O/bench_under_rocprof.err ) || echo "stats run failed"
 f=$(find $O/stats -name "*kernel_stats.csv" | head -1)
 [ -n "$f" ] && cp $f $O/${TAG}_kernel_stats.csv && python3 scripts/stats_top.py $O/stats 30 > $O/${TAG}_kernel_stats_top.txt
 cat $O/${TAG}_kernel_stats_top.txt | head -12
-echo "[4] plain bench"
-timeout -k 10 600 python3 bench.py --steps 3 --warmup 1 > $O/${TAG}_bench.json 2> $O/bench.err || echo "bench failed"
+echo "[4] full bench"
+timeout -k 10 600 python3 bench.py --steps 3 --warmup 1 --full > $O/${TAG}_bench.json 2> $O/bench.err || echo "bench failed"
 cut -c1-300 $O/${TAG}_bench.json
 echo "[5] eigensolver kernels (two-stage) at D = 3072 and 12288"
 bash $R/scripts/sbr_prof.sh ${TAG}_sbr > $O/${TAG}_eigensolver_kernels.txt 2>&1 || echo "sbr profile failed"

@@ -63,7 +63,7 @@ elif mode == "bench_full":
         report("inside bench.main, right before extra_cfg5")
         return orig(dev_)
     bench.extra_cfg5 = wrapped
-    bench.main(["--steps", "3", "--warmup", "1", "--no-cpu-baseline"] + sys.argv[2:])
+    bench.main(["--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"] + sys.argv[2:])
     report("after bench.main")
 elif mode in ("late_probe", "late_cfg2"):
     import argparse

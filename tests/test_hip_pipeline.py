@@ -463,7 +463,7 @@ def _bench_two_ranks_worker(rank, world, port, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK="0",
                       IDIFF_DIST_BACKEND="gloo")     # two processes on the one card: RCCL wants a GPU per rank
     import bench
-    line = bench.main(["--gpus", str(world), "--steps", "1", "--warmup", "1", "--no-cpu-baseline"])
+    line = bench.main(["--gpus", str(world), "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline"])
     q.put((rank, line))
 
 
@@ -593,6 +593,29 @@ def test_bench_two_ranks_sharing_the_card_rehearsal():
     assert line["config"]["rank_devices"] == ["cuda:0", f"cuda:{1 % n}"]
     assert len(line["id_estimates_all_ranks"]) == 2 and all(3000 < d <= 3072 for d in line["id_estimates_all_ranks"])
     assert line["value"] == pytest.approx(2 * line["config"]["rows_per_point"] / (line["ms_per_step"] * 1e-3), rel=1e-6)
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """A plain `python bench.py --gpus 1` runs the timed region only (the instrumented pass, the spectrum stages, the side
+    measurements and the CPU baseline are --full), and --dump-outputs writes the last timed step: its spectrum, its ID and a
+    fixed sample of its score rows."""
+    import json
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "IDIFF_DIST_BACKEND")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "0",
+                        "--dump-outputs", str(tmp_path)], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    line = lines[0]
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["roofline"] is None and line["svd_wall_clock_ms_per_point"] is None
+    assert "extra" not in line and "cpu_baseline" not in line
+    sv, ids, rows = (np.load(tmp_path / f) for f in ("singular_values.npy", "id_estimates.npy", "score_rows.npy"))
+    assert sv.dtype == np.float64 and sv.shape == (1, 3072) and np.isfinite(sv).all() and (sv >= 0).all()
+    assert ids.dtype == np.float64 and ids.tolist() == [float(line["id_estimates"][-1])]
+    assert plot_utils.estimate_dim(sv[0].tolist()) == line["id_estimates"][-1]
+    assert rows.dtype == np.float32 and rows.shape == (1024, 3072) and np.isfinite(rows).all() and rows.std() > 0
 
 
 @pytest.mark.gpu

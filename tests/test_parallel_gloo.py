@@ -210,6 +210,24 @@ def test_bench_plain_process_starts_its_own_two_ranks():
     assert line["value"] == pytest.approx(2 * 3 * 12 / (line["ms_per_step"] * 3e-3), rel=1e-6)
 
 
+def test_bench_dump_outputs_of_the_last_step(tmp_path):
+    """--dump-outputs DIR: the spectra and IDs of the LAST timed step (one point per rank, in rank order) as float64 .npy
+    files, identical in a second run with the same arguments."""
+    import numpy as np
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        r = _plain(["--gpus", "2", "--device", "cpu", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert len([l for l in r.stdout.splitlines() if l.startswith("{")]) == 1
+    sv, ids = np.load(dirs[0] / "singular_values.npy"), np.load(dirs[0] / "id_estimates.npy")
+    assert sv.dtype == np.float64 and sv.shape == (2, 5) and ids.dtype == np.float64 and ids.tolist() == [2.0, 2.0]
+    # the stand-in's spectrum encodes (rank, point): point 3 = warm-up 1 + the third timed step, ranks 0 and 1
+    np.testing.assert_allclose(sv[:, 0], [50.0 + 0.03, 50.0 + 0.03 + 0.001], rtol=1e-6)
+    assert sorted(p.name for p in dirs[0].iterdir()) == ["id_estimates.npy", "singular_values.npy"]
+    for name in ("singular_values.npy", "id_estimates.npy"):
+        assert np.array_equal(np.load(dirs[0] / name), np.load(dirs[1] / name))
+
+
 def test_bench_world_size_mismatch_is_an_error():
     """A launcher that started another world than --gpus asks for is an error on every rank, not a warning."""
     r = _plain(["--gpus", "2", "--device", "cpu", "--steps", "1", "--warmup", "0"],
