@@ -43,6 +43,7 @@ _SIGNATURES = {
     "idiff_gemm_pairs_2src_f32": (c_i, [c_p, c_p, c_i64, c_i, c_p, c_p, c_i64, c_p, c_p, c_i64, c_i, c_i, c_i, c_p, c_p]),
     "idiff_set_thread_option": (c_i, [ctypes.c_char_p, c_i, c_i]),
     "idiff_upfirdn2d_f32": (c_i, [c_p, c_p, c_p] + [c_i] * 14 + [c_p]),
+    "idiff_upfirdn2d_route": (ctypes.c_char_p, [c_p, c_p] + [c_i] * 14),
     "idiff_fused_bias_act_f32": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_i, c_f, c_f, c_p]),
     "idiff_upfirdn2d_f16": (c_i, [c_p, c_p, c_p] + [c_i] * 14 + [c_p]),
     "idiff_upfirdn2d_f64": (c_i, [c_p, c_p, c_p] + [c_i] * 14 + [c_p]),
@@ -263,6 +264,15 @@ def upfirdn2d_raw(x, k, out, major, in_h, in_w, minor, up_x, up_y, down_x, down_
     fn = getattr(lib(), "idiff_upfirdn2d_" + sfx)
     _check(fn(x.data_ptr(), k.data_ptr(), out.data_ptr(), major, in_h, in_w, minor, kh, kw,
               up_x, up_y, down_x, down_y, px0, px1, py0, py1, _stream()), "idiff_upfirdn2d_" + sfx)
+
+
+def upfirdn2d_route(x, out, major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, px0, px1, py0, py1):
+    """Name of the kernel ``upfirdn2d_raw`` would launch for these arguments (fp32 entry point), None if it refuses them.
+    x / out: tensors or raw addresses (only their 16-byte alignment matters); nothing is launched."""
+    addr = lambda t: t if isinstance(t, int) else t.data_ptr()
+    name = lib().idiff_upfirdn2d_route(addr(x), addr(out), major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y,
+                                       px0, px1, py0, py1)
+    return None if name is None else name.decode()
 
 
 def upfirdn2d_out_size(in_size, up, down, pad0, pad1, k):

@@ -40,9 +40,13 @@ constexpr int kMaxTaps = 64;  // kh*kw kept in LDS for the fast kernels
 // plain FIR 15.4 us at 15 planes per group).  So: among the admissible group sizes pick the one with the least (rounds x planes per
 // group), launch ceil(groups / rounds) workgroups and let each walk its groups (grid-stride), so that every workgroup does the same
 // number of groups +- 1 and all of them are resident from the start.  256 CUs x min(8, LDS) workgroups of 256 threads are resident.
+// A launch is held to 64 KB of dynamic LDS (above that it needs hipFuncSetAttribute, runtime.hip set_dynamic_lds_once): when no
+// group size is admissible one plane per group is taken, and when even one plane does not fit the result is ppb == 0, "none":
+// the caller does not take that kernel.
 struct GroupPlan { int ppb, grid, ngroups; };
 template <typename LdsBytes, typename Admissible>
 GroupPlan plan_plane_groups(int major, int ppb_max, LdsBytes lds_bytes_of, Admissible admissible) {
+  if (lds_bytes_of(1) > 64 * 1024) return {0, 0, 0};
   GroupPlan best = {1, major, major};
   double best_cost = 1e300;
   for (int ppb = 1; ppb <= ppb_max; ++ppb) {
@@ -629,11 +633,11 @@ upfirdn2d_generic_t(const T *__restrict__ x, const T *__restrict__ k, T *__restr
   }
 }
 
-// argument checks and output geometry shared by the three dtypes; returns 0 and fills p, or an error code
-int ufd_geometry(const void *x, const void *k, const void *out, int major, int in_h, int in_w, int minor, int kh, int kw, int up_x,
-                 int up_y, int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1, UfdParams &p) {
+// argument checks and output geometry shared by the three dtypes; returns 0 and fills p, or an error code.  The pointers are
+// checked by the callers (the route query has no FIR kernel to pass).
+int ufd_geometry(int major, int in_h, int in_w, int minor, int kh, int kw, int up_x, int up_y, int down_x, int down_y, int pad_x0,
+                 int pad_x1, int pad_y0, int pad_y1, UfdParams &p) {
   using namespace idiff;
-  if (!x || !k || !out) return fail("upfirdn2d: null pointer");
   if (major < 0 || in_h <= 0 || in_w <= 0 || minor <= 0 || kh <= 0 || kw <= 0)
     return fail("upfirdn2d: bad shape major=%d in=%dx%d minor=%d k=%dx%d", major, in_h, in_w, minor, kh, kw);
   if (up_x < 1 || up_y < 1 || down_x < 1 || down_y < 1) return fail("upfirdn2d: up/down factors must be >= 1");
@@ -650,13 +654,153 @@ template <typename T, typename ACC>
 int ufd_launch_t(const void *x, const void *k, void *out, int major, int in_h, int in_w, int minor, int kh, int kw, int up_x, int up_y,
                  int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1, void *stream, const char *what) {
   UfdParams p;
-  if (int rc = ufd_geometry(x, k, out, major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1, p))
+  if (major != 0 && (!x || !k || !out)) return idiff::fail("upfirdn2d: null pointer");   // an empty batch may have none
+  if (int rc = ufd_geometry(major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1, p))
     return rc;
   if (major == 0) return 0;
   const int64_t total = (int64_t)major * p.out_h * p.out_w * minor;
   hipLaunchKernelGGL((upfirdn2d_generic_t<T, ACC>), dim3(idiff::streaming_grid(total, 256)), dim3(256), 0, (hipStream_t)stream,
                      (const T *)x, (const T *)k, (T *)out, p, total);
   return idiff::launch_status(what);
+}
+
+// ---------------------------------------------------------------- fp32 dispatch
+// The admission chain of idiff_upfirdn2d_f32, kept in one place: the launcher switches on its result and
+// idiff_upfirdn2d_route reports it, so a test can see which kernel serves a geometry.
+enum UfdRoute {
+  UFD_NONE,                  // major == 0: nothing to launch
+  UFD_PLANES_FIR4, UFD_PLANES_ROWSLIDE, UFD_PLANES_DOWN2, UFD_PLANES_WHOLE0, UFD_PLANES_WHOLE1, UFD_PLANES_WHOLE_ANY,
+  UFD_PLANES_LDS, UFD_NHWC_UP2_BLOCK, UFD_NHWC_ROWS0, UFD_NHWC_ROWS1, UFD_NHWC_ROWS_ANY, UFD_NHWC_VEC4, UFD_GENERIC,
+};
+const char *const kUfdRouteNames[] = {"none", "planes_fir4", "planes_rowslide", "planes_down2", "planes_whole<0>", "planes_whole<1>",
+                                      "planes_whole<-1>", "planes_lds", "nhwc_up2_block", "nhwc_rows<0>", "nhwc_rows<1>",
+                                      "nhwc_rows<-1>", "nhwc_vec4", "generic"};
+
+// The chosen kernel and its launch numbers (only the fields of the chosen route are set).
+struct UfdPlan {
+  UfdRoute route;
+  dim3 grid;
+  size_t lds;                                   // dynamic LDS bytes
+  int ppb, ngroups, rows, pitch;                // planes_* (rows / pitch: framed-plane kernels)
+  int tx_log2;                                  // planes_whole
+  int toh, tow, tih, tiw, tiles_x;              // planes_lds
+  int cv, col_step;                             // nhwc_rows / nhwc_up2_block
+  int64_t total;                                // nhwc_vec4 (float4 count) / generic (element count)
+};
+
+// Returns 0 and fills p and c, or the error code of a geometry the launcher refuses.
+int ufd_choose(const void *x, const void *out, int major, int in_h, int in_w, int minor, int kh, int kw, int up_x, int up_y,
+               int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1, UfdParams &p, UfdPlan &c) {
+  using namespace idiff;
+  if (major != 0 && (!x || !out)) return fail("upfirdn2d: null pointer");   // an empty batch (major == 0) may have none
+  if (int rc = ufd_geometry(major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1, p))
+    return rc;
+  c = UfdPlan{};
+  c.route = UFD_NONE;
+  if (major == 0) return 0;
+  const int64_t total = (int64_t)major * p.out_h * p.out_w * minor;
+
+  if (minor == 1 && up_x == 1 && up_y == 1 && down_x == 1 && down_y == 1 && kh <= 4 && kw <= 4 && pad_x0 >= 0 && pad_y0 >= 0 &&
+      pad_x0 <= 4 && pad_y0 <= 4 && in_w % 4 == 0 && (int64_t)in_h * in_w <= 4096 && ((uintptr_t)x & 15) == 0 && !option(OPT_UFD_ROWS)) {
+    // plain FIR, strip form: frame rows -pad_y0 .. out_h + 2 - pad_y0, columns -pad_x0 .. 4 ceil(out_w / 4) + 3 - pad_x0
+    const int rows = max(in_h + pad_y0, p.out_h + 3), pitch = (max(in_w + pad_x0, 4 * ((p.out_w + 3) / 4) + 4) + 3) & ~3;
+    const int fsz = rows * pitch;
+    auto lds_of = [&](int ppb) { return (size_t)ppb * fsz * sizeof(float); };
+    const GroupPlan g = plan_plane_groups(major, std::min(major, 64), lds_of, [](int) { return true; });
+    if (g.ppb > 0) {
+      c.route = UFD_PLANES_FIR4; c.grid = dim3(g.grid); c.lds = lds_of(g.ppb); c.ppb = g.ppb; c.ngroups = g.ngroups;
+      c.rows = rows; c.pitch = pitch;
+      return 0;
+    }
+  }
+  if (minor == 1 && up_x == 1 && up_y == 1 && down_x == 1 && down_y == 1 && kh <= 4 && kw <= 4 && p.out_h <= 128 &&
+      (int64_t)in_h * in_w <= 4096) {
+    // plain FIR on small planes: one thread per (plane, output row)
+    const int lpsz = in_h * (in_w + 1), osz = p.out_h * p.out_w;
+    auto lds_of = [&](int ppb) { return (16 + (size_t)ppb * (lpsz + osz)) * sizeof(float); };
+    const GroupPlan g = plan_plane_groups(major, max(1, 256 / p.out_h), lds_of, [](int) { return true; });
+    if (g.ppb > 0) {
+      c.route = UFD_PLANES_ROWSLIDE; c.grid = dim3(g.grid); c.lds = lds_of(g.ppb); c.ppb = g.ppb; c.ngroups = g.ngroups;
+      return 0;
+    }
+  }
+  if (minor == 1 && up_x == 1 && up_y == 1 && down_x == 2 && down_y == 2 && kh <= 4 && kw <= 4 && pad_x0 >= 0 && pad_y0 >= 0 &&
+      pad_x0 <= 4 && pad_y0 <= 4 && p.out_h % 2 == 0 && p.out_w % 2 == 0 && in_w % 4 == 0 && (int64_t)in_h * in_w <= 4096 &&
+      (((uintptr_t)x | (uintptr_t)out) & 15) == 0 && !option(OPT_UFD_ROWS)) {
+    // FIR + decimation by 2: 2 x 2 output blocks from framed planes in LDS.  Frame: rows -pad_y0 .. 2 out_h + 1 - pad_y0, columns
+    // -pad_x0 .. 2 out_w + 1 - pad_x0 (the last block's window), pitch a multiple of 4 floats
+    const int rows = max(in_h + pad_y0, 2 * p.out_h + 2), pitch = (max(in_w + pad_x0, 2 * p.out_w + 2) + 3) & ~3;
+    const int fsz = rows * pitch, nb = (p.out_h / 2) * (p.out_w / 2);
+    auto lds_of = [&](int ppb) { return (size_t)ppb * fsz * sizeof(float); };
+    // whole rounds of 256 output blocks per group where the shape allows it (no idle lanes in the last round of a group)
+    auto full_rounds = [&](int ppb) {
+      if (nb >= 256 || 256 % nb != 0) return true;
+      const int unit = 256 / nb;                                     // planes per round of 256 blocks
+      return ppb % unit == 0 || (major < unit && ppb == major);
+    };
+    const GroupPlan g = plan_plane_groups(major, std::min(major, 64), lds_of, full_rounds);
+    if (g.ppb > 0) {
+      c.route = UFD_PLANES_DOWN2; c.grid = dim3(g.grid); c.lds = lds_of(g.ppb); c.ppb = g.ppb; c.ngroups = g.ngroups;
+      c.rows = rows; c.pitch = pitch;
+      return 0;
+    }
+  }
+  if (minor == 1 && kh * kw <= kMaxTaps && (int64_t)in_h * in_w <= 8192 && (int64_t)p.out_h * p.out_w <= 16384) {
+    // whole planes in LDS: <= 32 KB per plane; as many planes per workgroup as fit 32 KB / ~16 outputs per thread
+    const int psz = in_h * in_w, osz = p.out_h * p.out_w;
+    int ppb = max(1, min((32 * 1024 / 4) / psz, 4096 / max(osz, 1)));
+    ppb = max(1, min(ppb, max(1, major / 1024)));  // keep >= ~4 workgroups per CU when there are few planes
+    int tx_log2 = 0;
+    while ((1 << tx_log2) < min(p.out_w, 64)) ++tx_log2;
+    const int uplog = (up_x == up_y && kh <= 4 && kw <= 4) ? (up_x == 1 ? 0 : up_x == 2 ? 1 : -1) : -1;
+    c.route = uplog == 0 ? UFD_PLANES_WHOLE0 : uplog == 1 ? UFD_PLANES_WHOLE1 : UFD_PLANES_WHOLE_ANY;
+    c.grid = dim3(ceil_div(major, ppb)); c.lds = (kMaxTaps + (size_t)ppb * psz) * sizeof(float); c.ppb = ppb; c.tx_log2 = tx_log2;
+    return 0;
+  }
+  if (minor == 1 && kh * kw <= kMaxTaps) {
+    // output tile: up to 32 x 64 pixels, several planes per workgroup when planes are small
+    const int tow = min(p.out_w, 64), toh = min(p.out_h, 32);
+    const int tih = ((toh - 1) * down_y + kh - 1) / up_y + 2;
+    const int tiw = ((tow - 1) * down_x + kw - 1) / up_x + 2;
+    const int tile_elems = toh * tow;
+    int ppb = max(1, 2048 / tile_elems);                      // ~8 outputs per thread
+    const int max_ppb_lds = max(1, (int)((48 * 1024 / sizeof(float) - kMaxTaps) / (tih * (tiw + 1))));
+    ppb = min(min(ppb, max_ppb_lds), major);
+    const size_t lds_bytes = (kMaxTaps + (size_t)ppb * tih * (tiw + 1)) * sizeof(float);
+    if (lds_bytes <= 64 * 1024) {
+      const int tiles_x = ceil_div(p.out_w, tow), tiles_y = ceil_div(p.out_h, toh);
+      const dim3 grid(ceil_div(major, ppb), tiles_x * tiles_y);
+      if (grid.y <= 65535) {
+        c.route = UFD_PLANES_LDS; c.grid = grid; c.lds = lds_bytes; c.ppb = ppb;
+        c.toh = toh; c.tow = tow; c.tih = tih; c.tiw = tiw; c.tiles_x = tiles_x;
+        return 0;
+      }
+    }
+  }
+  // one grid dimension holds at most 2^32 - 1 work-items: 2^24 - 1 workgroups of 256 (beyond: nhwc_vec4's capped grid-stride launch)
+  constexpr int64_t kMaxRowGroups = 0xffffffffll / 256;
+  if (minor % 4 == 0 && minor <= 1024 && kh * kw <= kMaxTaps && ((uintptr_t)x % 16 == 0) && ((uintptr_t)out % 16 == 0) &&
+      (int64_t)major * p.out_h <= kMaxRowGroups) {
+    c.cv = minor / 4; c.col_step = 256 / c.cv;
+    // enough rows to fill the chip: one workgroup per output row (each thread walks out_w / col_step pixels);
+    // otherwise split rows over up to 8 workgroups
+    const int gx = (int64_t)major * p.out_h >= 2048 ? 1 : max(1, min(ceil_div(p.out_w, c.col_step), 8));
+    if (up_x == 2 && up_y == 2 && down_x == 1 && down_y == 1 && kh == 4 && kw == 4 && pad_x0 == 2 && pad_y0 == 2 &&
+        p.out_h == 2 * in_h && p.out_w == 2 * in_w && (int64_t)major * in_h <= kMaxRowGroups && !option(OPT_UFD_ROWS)) {
+      c.route = UFD_NHWC_UP2_BLOCK; c.grid = dim3(major * in_h);
+      return 0;
+    }
+    const int uplog = (up_x == up_y && kh <= 4 && kw <= 4) ? (up_x == 1 ? 0 : up_x == 2 ? 1 : -1) : -1;
+    c.route = uplog == 0 ? UFD_NHWC_ROWS0 : uplog == 1 ? UFD_NHWC_ROWS1 : UFD_NHWC_ROWS_ANY;
+    c.grid = dim3(major * p.out_h, gx);
+    return 0;
+  }
+  if (minor % 4 == 0 && kh * kw <= kMaxTaps && ((uintptr_t)x % 16 == 0) && ((uintptr_t)out % 16 == 0)) {
+    c.route = UFD_NHWC_VEC4; c.total = total / 4; c.grid = dim3(streaming_grid(c.total, 256));
+    return 0;
+  }
+  c.route = UFD_GENERIC; c.total = total; c.grid = dim3(streaming_grid(total, 256));
+  return 0;
 }
 
 }  // namespace
@@ -679,123 +823,63 @@ IDIFF_API int idiff_upfirdn2d_f32(const float *x, const float *k, float *out, in
                                   int minor, int kh, int kw, int up_x, int up_y, int down_x, int down_y,
                                   int pad_x0, int pad_x1, int pad_y0, int pad_y1, void *stream) {
   using namespace idiff;
-  if (!x || !k || !out) return fail("upfirdn2d: null pointer");
-  if (major < 0 || in_h <= 0 || in_w <= 0 || minor <= 0 || kh <= 0 || kw <= 0)
-    return fail("upfirdn2d: bad shape major=%d in=%dx%d minor=%d k=%dx%d", major, in_h, in_w, minor, kh, kw);
-  if (up_x < 1 || up_y < 1 || down_x < 1 || down_y < 1) return fail("upfirdn2d: up/down factors must be >= 1");
+  if (major != 0 && !k) return fail("upfirdn2d: null pointer");
   UfdParams p;
-  p.major = major; p.in_h = in_h; p.in_w = in_w; p.minor = minor; p.kh = kh; p.kw = kw;
-  p.up_x = up_x; p.up_y = up_y; p.down_x = down_x; p.down_y = down_y; p.pad_x0 = pad_x0; p.pad_y0 = pad_y0;
-  const int span_h = in_h * up_y + pad_y0 + pad_y1 - kh, span_w = in_w * up_x + pad_x0 + pad_x1 - kw;
-  if (span_h < 0 || span_w < 0) return fail("upfirdn2d: kernel larger than padded input");
-  p.out_h = span_h / down_y + 1;
-  p.out_w = span_w / down_x + 1;
-  if (major == 0) return 0;
+  UfdPlan c;
+  if (int rc = ufd_choose(x, out, major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1, p, c))
+    return rc;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t total = (int64_t)major * p.out_h * p.out_w * minor;
-
-  if (minor == 1 && up_x == 1 && up_y == 1 && down_x == 1 && down_y == 1 && kh <= 4 && kw <= 4 && pad_x0 >= 0 && pad_y0 >= 0 &&
-      pad_x0 <= 4 && pad_y0 <= 4 && in_w % 4 == 0 && (int64_t)in_h * in_w <= 4096 && ((uintptr_t)x & 15) == 0 && !option(OPT_UFD_ROWS)) {
-    // plain FIR, strip form: frame rows -pad_y0 .. out_h + 2 - pad_y0, columns -pad_x0 .. 4 ceil(out_w / 4) + 3 - pad_x0
-    const int rows = max(in_h + pad_y0, p.out_h + 3), pitch = (max(in_w + pad_x0, 4 * ((p.out_w + 3) / 4) + 4) + 3) & ~3;
-    const int fsz = rows * pitch;
-    auto lds_of = [&](int ppb) { return (size_t)ppb * fsz * sizeof(float); };
-    const GroupPlan g = plan_plane_groups(major, std::min(major, 64), lds_of, [](int) { return true; });
-    hipLaunchKernelGGL(upfirdn2d_planes_fir4, dim3(g.grid), dim3(256), lds_of(g.ppb), st, x, k, out, p, g.ppb, rows, pitch, g.ngroups);
-    return launch_status("upfirdn2d_planes_fir4");
-  }
-  if (minor == 1 && up_x == 1 && up_y == 1 && down_x == 1 && down_y == 1 && kh <= 4 && kw <= 4 && p.out_h <= 128 &&
-      (int64_t)in_h * in_w <= 4096) {
-    // plain FIR on small planes: one thread per (plane, output row)
-    const int lpsz = in_h * (in_w + 1), osz = p.out_h * p.out_w;
-    auto lds_of = [&](int ppb) { return (16 + (size_t)ppb * (lpsz + osz)) * sizeof(float); };
-    const GroupPlan g = plan_plane_groups(major, max(1, 256 / p.out_h), lds_of, [](int) { return true; });
-    hipLaunchKernelGGL(upfirdn2d_planes_rowslide, dim3(g.grid), dim3(256), lds_of(g.ppb), st, x, k, out, p, g.ppb, g.ngroups);
-    return launch_status("upfirdn2d_planes_rowslide");
-  }
-  if (minor == 1 && up_x == 1 && up_y == 1 && down_x == 2 && down_y == 2 && kh <= 4 && kw <= 4 && pad_x0 >= 0 && pad_y0 >= 0 &&
-      pad_x0 <= 4 && pad_y0 <= 4 && p.out_h % 2 == 0 && p.out_w % 2 == 0 && in_w % 4 == 0 && (int64_t)in_h * in_w <= 4096 &&
-      (((uintptr_t)x | (uintptr_t)out) & 15) == 0 && !option(OPT_UFD_ROWS)) {
-    // FIR + decimation by 2: 2 x 2 output blocks from framed planes in LDS.  Frame: rows -pad_y0 .. 2 out_h + 1 - pad_y0, columns
-    // -pad_x0 .. 2 out_w + 1 - pad_x0 (the last block's window), pitch a multiple of 4 floats
-    const int rows = max(in_h + pad_y0, 2 * p.out_h + 2), pitch = (max(in_w + pad_x0, 2 * p.out_w + 2) + 3) & ~3;
-    const int fsz = rows * pitch, nb = (p.out_h / 2) * (p.out_w / 2);
-    auto lds_of = [&](int ppb) { return (size_t)ppb * fsz * sizeof(float); };
-    // whole rounds of 256 output blocks per group where the shape allows it (no idle lanes in the last round of a group)
-    auto full_rounds = [&](int ppb) {
-      if (nb >= 256 || 256 % nb != 0) return true;
-      const int unit = 256 / nb;                                     // planes per round of 256 blocks
-      return ppb % unit == 0 || (major < unit && ppb == major);
-    };
-    const GroupPlan g = plan_plane_groups(major, std::min(major, 64), lds_of, full_rounds);
-    hipLaunchKernelGGL(upfirdn2d_planes_down2, dim3(g.grid), dim3(256), lds_of(g.ppb), st, x, k, out, p, g.ppb, rows, pitch, g.ngroups);
-    return launch_status("upfirdn2d_planes_down2");
-  }
-  if (minor == 1 && kh * kw <= kMaxTaps && (int64_t)in_h * in_w <= 8192 && (int64_t)p.out_h * p.out_w <= 16384) {
-    // whole planes in LDS: <= 32 KB per plane; as many planes per workgroup as fit 32 KB / ~16 outputs per thread
-    const int psz = in_h * in_w, osz = p.out_h * p.out_w;
-    int ppb = max(1, min((32 * 1024 / 4) / psz, 4096 / max(osz, 1)));
-    ppb = max(1, min(ppb, max(1, major / 1024)));  // keep >= ~4 workgroups per CU when there are few planes
-    int tx_log2 = 0;
-    while ((1 << tx_log2) < min(p.out_w, 64)) ++tx_log2;
-    const size_t lds_bytes = (kMaxTaps + (size_t)ppb * psz) * sizeof(float);
-    const int uplog = (up_x == up_y && kh <= 4 && kw <= 4) ? (up_x == 1 ? 0 : up_x == 2 ? 1 : -1) : -1;
-    const dim3 grid(ceil_div(major, ppb));
-    if (uplog == 0)
-      hipLaunchKernelGGL(upfirdn2d_planes_whole<0>, grid, dim3(256), lds_bytes, st, x, k, out, p, ppb, tx_log2);
-    else if (uplog == 1)
-      hipLaunchKernelGGL(upfirdn2d_planes_whole<1>, grid, dim3(256), lds_bytes, st, x, k, out, p, ppb, tx_log2);
-    else
-      hipLaunchKernelGGL(upfirdn2d_planes_whole<-1>, grid, dim3(256), lds_bytes, st, x, k, out, p, ppb, tx_log2);
-    return launch_status("upfirdn2d_planes_whole");
-  }
-  if (minor == 1 && kh * kw <= kMaxTaps) {
-    // output tile: up to 32 x 64 pixels, several planes per workgroup when planes are small
-    const int tow = min(p.out_w, 64), toh = min(p.out_h, 32);
-    const int tih = ((toh - 1) * down_y + kh - 1) / up_y + 2;
-    const int tiw = ((tow - 1) * down_x + kw - 1) / up_x + 2;
-    const int tile_elems = toh * tow;
-    int ppb = max(1, 2048 / tile_elems);                      // ~8 outputs per thread
-    const int max_ppb_lds = max(1, (int)((48 * 1024 / sizeof(float) - kMaxTaps) / (tih * (tiw + 1))));
-    ppb = min(min(ppb, max_ppb_lds), major);
-    const size_t lds_bytes = (kMaxTaps + (size_t)ppb * tih * (tiw + 1)) * sizeof(float);
-    if (lds_bytes <= 64 * 1024) {
-      const int tiles_x = ceil_div(p.out_w, tow), tiles_y = ceil_div(p.out_h, toh);
-      dim3 grid(ceil_div(major, ppb), tiles_x * tiles_y);
-      if (grid.y <= 65535) {
-        hipLaunchKernelGGL(upfirdn2d_planes_lds, grid, dim3(256), lds_bytes, st, x, k, out, p, toh, tow, tih, tiw,
-                           ppb, tiles_x);
-        return launch_status("upfirdn2d_planes_lds");
-      }
-    }
-  }
-  if (minor % 4 == 0 && minor <= 1024 && kh * kw <= kMaxTaps && ((uintptr_t)x % 16 == 0) && ((uintptr_t)out % 16 == 0) &&
-      (int64_t)major * p.out_h <= 0x7fffffff) {
-    const int cv = minor / 4, col_step = 256 / cv;
-    // enough rows to fill the chip: one workgroup per output row (each thread walks out_w / col_step pixels);
-    // otherwise split rows over up to 8 workgroups
-    const int gx = (int64_t)major * p.out_h >= 2048 ? 1 : max(1, min(ceil_div(p.out_w, col_step), 8));
-    if (up_x == 2 && up_y == 2 && down_x == 1 && down_y == 1 && kh == 4 && kw == 4 && pad_x0 == 2 && pad_y0 == 2 &&
-        p.out_h == 2 * in_h && p.out_w == 2 * in_w && (int64_t)major * in_h <= 0x7fffffff && !idiff::option(idiff::OPT_UFD_ROWS)) {
-      hipLaunchKernelGGL(upfirdn2d_nhwc_up2_block, dim3(major * in_h), dim3(256), 0, st, x, k, out, p, cv, col_step);
+  const dim3 blk(256);
+  switch (c.route) {
+    case UFD_NONE: return 0;
+    case UFD_PLANES_FIR4:
+      hipLaunchKernelGGL(upfirdn2d_planes_fir4, c.grid, blk, c.lds, st, x, k, out, p, c.ppb, c.rows, c.pitch, c.ngroups);
+      return launch_status("upfirdn2d_planes_fir4");
+    case UFD_PLANES_ROWSLIDE:
+      hipLaunchKernelGGL(upfirdn2d_planes_rowslide, c.grid, blk, c.lds, st, x, k, out, p, c.ppb, c.ngroups);
+      return launch_status("upfirdn2d_planes_rowslide");
+    case UFD_PLANES_DOWN2:
+      hipLaunchKernelGGL(upfirdn2d_planes_down2, c.grid, blk, c.lds, st, x, k, out, p, c.ppb, c.rows, c.pitch, c.ngroups);
+      return launch_status("upfirdn2d_planes_down2");
+    case UFD_PLANES_WHOLE0:
+      hipLaunchKernelGGL(upfirdn2d_planes_whole<0>, c.grid, blk, c.lds, st, x, k, out, p, c.ppb, c.tx_log2);
+      return launch_status("upfirdn2d_planes_whole");
+    case UFD_PLANES_WHOLE1:
+      hipLaunchKernelGGL(upfirdn2d_planes_whole<1>, c.grid, blk, c.lds, st, x, k, out, p, c.ppb, c.tx_log2);
+      return launch_status("upfirdn2d_planes_whole");
+    case UFD_PLANES_WHOLE_ANY:
+      hipLaunchKernelGGL(upfirdn2d_planes_whole<-1>, c.grid, blk, c.lds, st, x, k, out, p, c.ppb, c.tx_log2);
+      return launch_status("upfirdn2d_planes_whole");
+    case UFD_PLANES_LDS:
+      hipLaunchKernelGGL(upfirdn2d_planes_lds, c.grid, blk, c.lds, st, x, k, out, p, c.toh, c.tow, c.tih, c.tiw, c.ppb, c.tiles_x);
+      return launch_status("upfirdn2d_planes_lds");
+    case UFD_NHWC_UP2_BLOCK:
+      hipLaunchKernelGGL(upfirdn2d_nhwc_up2_block, c.grid, blk, 0, st, x, k, out, p, c.cv, c.col_step);
       return launch_status("upfirdn2d_nhwc_up2_block");
-    }
-    const int uplog = (up_x == up_y && kh <= 4 && kw <= 4) ? (up_x == 1 ? 0 : up_x == 2 ? 1 : -1) : -1;
-    const dim3 grid(major * p.out_h, gx);
-    if (uplog == 0)
-      hipLaunchKernelGGL(upfirdn2d_nhwc_rows<0>, grid, dim3(256), 0, st, x, k, out, p, cv, col_step);
-    else if (uplog == 1)
-      hipLaunchKernelGGL(upfirdn2d_nhwc_rows<1>, grid, dim3(256), 0, st, x, k, out, p, cv, col_step);
-    else
-      hipLaunchKernelGGL(upfirdn2d_nhwc_rows<-1>, grid, dim3(256), 0, st, x, k, out, p, cv, col_step);
-    return launch_status("upfirdn2d_nhwc_rows");
+    case UFD_NHWC_ROWS0:
+      hipLaunchKernelGGL(upfirdn2d_nhwc_rows<0>, c.grid, blk, 0, st, x, k, out, p, c.cv, c.col_step);
+      return launch_status("upfirdn2d_nhwc_rows");
+    case UFD_NHWC_ROWS1:
+      hipLaunchKernelGGL(upfirdn2d_nhwc_rows<1>, c.grid, blk, 0, st, x, k, out, p, c.cv, c.col_step);
+      return launch_status("upfirdn2d_nhwc_rows");
+    case UFD_NHWC_ROWS_ANY:
+      hipLaunchKernelGGL(upfirdn2d_nhwc_rows<-1>, c.grid, blk, 0, st, x, k, out, p, c.cv, c.col_step);
+      return launch_status("upfirdn2d_nhwc_rows");
+    case UFD_NHWC_VEC4:
+      hipLaunchKernelGGL(upfirdn2d_nhwc_vec4, c.grid, blk, 0, st, x, k, out, p, c.total);
+      return launch_status("upfirdn2d_nhwc_vec4");
+    case UFD_GENERIC:
+      hipLaunchKernelGGL(upfirdn2d_generic, c.grid, blk, 0, st, x, k, out, p, c.total);
+      return launch_status("upfirdn2d_generic");
   }
-  if (minor % 4 == 0 && kh * kw <= kMaxTaps && ((uintptr_t)x % 16 == 0) && ((uintptr_t)out % 16 == 0)) {
-    const int64_t total_vec = total / 4;
-    hipLaunchKernelGGL(upfirdn2d_nhwc_vec4, dim3(streaming_grid(total_vec, 256)), dim3(256), 0, st, x, k, out, p,
-                       total_vec);
-    return launch_status("upfirdn2d_nhwc_vec4");
-  }
-  hipLaunchKernelGGL(upfirdn2d_generic, dim3(streaming_grid(total, 256)), dim3(256), 0, st, x, k, out, p, total);
-  return launch_status("upfirdn2d_generic");
+  return fail("upfirdn2d: no route");
+}
+
+IDIFF_API const char *idiff_upfirdn2d_route(const void *x, const void *out, int major, int in_h, int in_w, int minor, int kh, int kw,
+                                            int up_x, int up_y, int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0,
+                                            int pad_y1) {
+  UfdParams p;
+  UfdPlan c;
+  if (ufd_choose(x, out, major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1, p, c)) return nullptr;
+  return kUfdRouteNames[c.route];
 }

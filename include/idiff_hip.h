@@ -69,10 +69,19 @@ int idiff_set_thread_option(const char *name, int value, int set);
  * x is [major, in_h, in_w, minor] fp32 contiguous, k is [kh, kw] fp32 (NOT flipped: the op is a true
  * convolution, the kernel flips), out is [major, out_h, out_w, minor] with
  * out_h = (in_h*up_y + pad_y0 + pad_y1 - kh)/down_y + 1 (op/upfirdn2d_kernel.cu:237-240).
- * minor = 1 is the NCHW view the reference uses (op/upfirdn2d.py:99); minor = C serves NHWC activations. */
+ * minor = 1 is the NCHW view the reference uses (op/upfirdn2d.py:99); minor = C serves NHWC activations.
+ * major = 0 (an empty batch) launches nothing and accepts null pointers. */
 int idiff_upfirdn2d_f32(const float *x, const float *k, float *out, int major, int in_h, int in_w, int minor,
                         int kh, int kw, int up_x, int up_y, int down_x, int down_y, int pad_x0, int pad_x1,
                         int pad_y0, int pad_y1, void *stream);
+
+/* The kernel idiff_upfirdn2d_f32 would launch for these arguments (same admission code, same thread options such as
+ * IDIFF_UFD_ROWS; x and out are only inspected for 16-byte alignment): "planes_fir4", "planes_rowslide", "planes_down2",
+ * "planes_whole<0>" / "<1>" / "<-1>", "planes_lds", "nhwc_up2_block", "nhwc_rows<0>" / "<1>" / "<-1>", "nhwc_vec4",
+ * "generic", or "none" when major == 0 (nothing to launch).  NULL for arguments the launcher refuses (idiff_last_error says
+ * why).  Launches nothing; no reference counterpart. */
+const char *idiff_upfirdn2d_route(const void *x, const void *out, int major, int in_h, int in_w, int minor, int kh, int kw,
+                                  int up_x, int up_y, int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1);
 
 /* Replaces `fused_bias_act(input, bias, refer, act, grad, alpha, scale)` of op/fused_bias_act.cpp:11-17
  * (kernel op/fused_bias_act_kernel.cu:18-49).  out[i] = f(x[i] + b[(i/step_b) % size_b]) * scale with

@@ -61,6 +61,7 @@ def test_upfirdn2d_nchw_vs_oracle(shape, up, down, pad):
     ((2, 9, 16, 16), (3, 1), 4),       # asymmetric pads (even output still)
     ((2, 9, 12, 16), (0, 0), 2),       # 2 x 2 taps, no padding
     ((2, 5, 16, 16), (1, 2), 3),       # 3 x 3 asymmetric taps
+    ((2, 3, 16, 16), (2, 40), 4),      # a large trailing pad: the frame grows with the output
 ])
 def test_upfirdn2d_down2_block_kernel_vs_oracle(shape, pad, ksz):
     """upfirdn2d_planes_down2 (2 x 2 output blocks from zero-framed planes in LDS): every geometry that takes it, asymmetric random
@@ -85,6 +86,7 @@ def test_upfirdn2d_down2_block_kernel_vs_oracle(shape, pad, ksz):
     ((2, 9, 12, 16), (0, 0), 3),       # valid convolution with 3 x 3 taps
     ((2, 5, 16, 16), (3, 0), 2),
     ((1, 1, 4, 4), (2, 2), 4),
+    ((2, 3, 16, 16), (2, 40), 4),      # a large trailing pad: the frame grows with the output
 ])
 def test_upfirdn2d_fir_strip_kernel_vs_oracle(shape, pad, ksz):
     """upfirdn2d_planes_fir4 (strips of four outputs from zero-framed planes in LDS) against the oracle's restatement of
