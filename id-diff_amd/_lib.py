@@ -109,6 +109,8 @@ _SIGNATURES = {
     "idiff_symtridiag_f64": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_p]),
     "idiff_symtridiag_plan": (c_i, [c_i]),
     "idiff_tridiag_eigvals_f64": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p]),
+    "idiff_knn_workspace_bytes": (c_i64, [c_i, c_i, c_i]),
+    "idiff_knn_f32": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -809,3 +811,24 @@ def sym_eigvals(G):
            "idiff_symtridiag_f64")
     _check(lib().idiff_tridiag_eigvals_f64(diag.data_ptr(), offd.data_ptr(), 1, D, eig.data_ptr(), _stream()), "idiff_tridiag_eigvals_f64")
     return eig
+
+
+# ------------------------------------------------------------------------------------------- k nearest neighbours
+def knn(X, k, workspace=None):
+    """Exact k nearest OTHER rows of every row of X [N, D] (CUDA fp32, contiguous): ``(dist, idx, n_exact_rows)`` with
+    dist [N, k] fp64 (Euclidean, ascending; equal distances by lower index), idx [N, k] int64 and n_exact_rows a 0-d int32
+    device tensor (rows the kernel settled by fp64 brute force).  No host sync."""
+    _dev(X, "X")
+    if X.ndim != 2:
+        raise RuntimeError(f"knn: X must be [N, D], got {tuple(X.shape)}")
+    N, D = X.shape
+    k = int(k)
+    need = lib().idiff_knn_workspace_bytes(N, D, k)
+    if need > 0 and (workspace is None or workspace.numel() * workspace.element_size() < need):
+        workspace = torch.empty((need + 7) // 8, dtype=torch.float64, device=X.device)
+    dist = torch.empty(N, k, dtype=torch.float64, device=X.device) if N > 0 and k > 0 else torch.empty(0, device=X.device)
+    idx = torch.empty(N, k, dtype=torch.int64, device=X.device) if N > 0 and k > 0 else torch.empty(0, device=X.device)
+    n_exact = torch.zeros((), dtype=torch.int32, device=X.device)
+    _check(lib().idiff_knn_f32(X.data_ptr(), N, D, k, _ptr(workspace), 0 if workspace is None else workspace.numel() * 8,
+                               dist.data_ptr(), idx.data_ptr(), n_exact.data_ptr(), _stream()), "idiff_knn_f32")
+    return dist, idx, n_exact

@@ -424,6 +424,21 @@ int idiff_symtridiag_f64(double *G, int P, int D, double *diag, double *offdiag,
 int idiff_symtridiag_plan(int D);
 int idiff_tridiag_eigvals_f64(const double *diag, const double *offdiag, int P, int D, double *eig, void *stream);
 
+/* ------------------------------------------------------------------ exact k nearest neighbours */
+
+/* Replaces `NearestNeighbors(n_neighbors=k+1, algorithm='ball_tree').fit(X).kneighbors(X)` of mle.py:19-20 / :47-48 /
+ * :80-81 (without the self column).  X is [N, D] fp32, row-major, contiguous.  For every row i: the k nearest OTHER rows
+ * (self excluded by index), by ascending Euclidean distance, equal distances by lower index; dist [N, k] fp64 holds
+ * sqrt(sum_d (x_id - x_jd)^2) evaluated in fp64 from the fp32 inputs, idx [N, k] the row indices.  Exact: candidates from
+ * an fp32 pass on v_mfma_f32_32x32x2_f32 (centred data, K' = min(N - 1, k + 16) per row), refined in fp64, with a bound
+ * on the fp32 pass's error deciding per row whether the candidates are provably enough; rows where they are not are done
+ * again by fp64 brute force, and *n_exact_rows (device int) receives their count.  Needs 2 <= N, 1 <= D, 1 <= k <= 64,
+ * k <= N - 1 (IDIFF_EINVAL otherwise).  workspace: idiff_knn_workspace_bytes(N, D, k) bytes, 256-byte aligned (0 for
+ * arguments the call refuses). */
+int64_t idiff_knn_workspace_bytes(int N, int D, int k);
+int idiff_knn_f32(const float *X, int N, int D, int k, void *workspace, int64_t workspace_bytes, double *dist, int64_t *idx,
+                  int *n_exact_rows, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
