@@ -433,6 +433,32 @@ def conv2d_nhwc(x, wt, out, B, H, W, Cin, Cout, KH, KW, stride, pad, epilogue=No
     return out
 
 
+# ---- Winograd convolutions.  Five kernel forms, named by the stem of their entry points (idiff_<stem>_weight_floats,
+# idiff_<stem>_pack_f32, idiff_conv2d_<stem>_f32): winograd / winograd_split = F(2x2, 3x3) on the fp32 matrix cores / on three bf16 per
+# operand, winograd43 / winograd43h = F(4x4, 3x3) on fp32 / on fp16 pairs, wino1d = F(4, 3) along the rows on fp16 pairs.
+def _wino_pack(stem, name, wt, Cin, Cout):
+    """wt [Cout, 3, 3, Cin] (the direct kernel's panel) -> the transformed filter bank of idiff_conv2d_<stem>_f32."""
+    _dev(wt, "wt")
+    if tuple(wt.shape) != (Cout, 3, 3, Cin):
+        raise RuntimeError(f"{name}: expected {Cout}x3x3x{Cin} weights, got {tuple(wt.shape)}")
+    entry = "idiff_winograd_pack_split_f32" if stem == "winograd_split" else f"idiff_{stem}_pack_f32"
+    u = torch.empty(getattr(lib(), f"idiff_{stem}_weight_floats")(Cin, Cout), device=wt.device, dtype=torch.float32)
+    _check(getattr(lib(), entry)(wt.data_ptr(), u.data_ptr(), Cin, Cout, _stream()), entry)
+    return u
+
+
+def _wino_conv(stem, packed_by, x, u, out, B, H, W, Cin, Cout, epilogue):
+    """One launch of idiff_conv2d_<stem>_f32.  The forms' banks differ in size, so a bank of another form is refused here
+    (never reinterpreted) with the ``packed_by`` call that makes the right one."""
+    want = getattr(lib(), f"idiff_{stem}_weight_floats")(Cin, Cout)
+    if u.numel() != want:
+        raise RuntimeError(f"conv2d_{stem}: a filter bank of {u.numel()} floats ({want} expected): pack it with {packed_by}")
+    ep = ctypes.byref(epilogue) if epilogue is not None else None
+    entry = f"idiff_conv2d_{stem}_f32"
+    _check(getattr(lib(), entry)(x.data_ptr(), u.data_ptr(), out.data_ptr(), B, H, W, Cin, Cout, ep, _stream()), entry)
+    return out
+
+
 def conv2d_winograd_ok(B, H, W, Cin, Cout):
     return bool(lib().idiff_conv2d_winograd_ok(B, H, W, Cin, Cout))
 
@@ -443,35 +469,18 @@ def conv2d_winograd_split_ok(B, H, W, Cin, Cout):
     return bool(lib().idiff_conv2d_winograd_split_ok(B, H, W, Cin, Cout))
 
 
+def conv2d_winograd_colstats_split(B, H, W, Cin, Cout):
+    return lib().idiff_conv2d_winograd_colstats_split(B, H, W, Cin, Cout)
+
+
 def winograd_pack(wt, Cin, Cout, split=False):
-    """wt [Cout, 3, 3, Cin] (the direct kernel's panel) -> the transformed filter bank of idiff_conv2d_winograd_f32, or --
-    ``split=True`` -- of idiff_conv2d_winograd_split_f32 (three bf16 per weight)."""
-    _dev(wt, "wt")
-    if wt.numel() != Cout * 9 * Cin:
-        raise RuntimeError(f"winograd_pack: expected {Cout}x3x3x{Cin} weights, got {tuple(wt.shape)}")
-    if split:
-        u = torch.empty(lib().idiff_winograd_split_weight_floats(Cin, Cout), device=wt.device, dtype=torch.float32)
-        _check(lib().idiff_winograd_pack_split_f32(wt.data_ptr(), u.data_ptr(), Cin, Cout, _stream()), "idiff_winograd_pack_split_f32")
-        return u
-    u = torch.empty(lib().idiff_winograd_weight_floats(Cin, Cout), device=wt.device, dtype=torch.float32)
-    _check(lib().idiff_winograd_pack_f32(wt.data_ptr(), u.data_ptr(), Cin, Cout, _stream()), "idiff_winograd_pack_f32")
-    return u
+    """The filter bank of idiff_conv2d_winograd_f32, or -- ``split=True`` -- of idiff_conv2d_winograd_split_f32 (three bf16 per weight)."""
+    return _wino_pack("winograd_split" if split else "winograd", "winograd_pack", wt, Cin, Cout)
 
 
 def conv2d_winograd(x, u, out, B, H, W, Cin, Cout, epilogue=None, split=False):
-    """``split`` names the kernel; the bank must be the one ``winograd_pack(..., split=split)`` made (sizes differ: checked)."""
-    ep = ctypes.byref(epilogue) if epilogue is not None else None
-    want = (lib().idiff_winograd_split_weight_floats if split else lib().idiff_winograd_weight_floats)(Cin, Cout)
-    if u.numel() != want:
-        raise RuntimeError(f"conv2d_winograd: a filter bank of {u.numel()} floats for the {'split' if split else 'fp32'} kernel "
-                           f"({want} expected): pack it with winograd_pack(..., split={split})")
-    if split:
-        _check(lib().idiff_conv2d_winograd_split_f32(x.data_ptr(), u.data_ptr(), out.data_ptr(), B, H, W, Cin, Cout, ep, _stream()),
-               "idiff_conv2d_winograd_split_f32")
-        return out
-    _check(lib().idiff_conv2d_winograd_f32(x.data_ptr(), u.data_ptr(), out.data_ptr(), B, H, W, Cin, Cout, ep, _stream()),
-           "idiff_conv2d_winograd_f32")
-    return out
+    """``split`` names the kernel; the bank must be the one ``winograd_pack(..., split=split)`` made."""
+    return _wino_conv("winograd_split" if split else "winograd", f"winograd_pack(..., split={split})", x, u, out, B, H, W, Cin, Cout, epilogue)
 
 
 def conv2d_winograd43_ok(B, H, W, Cin, Cout):
@@ -479,45 +488,26 @@ def conv2d_winograd43_ok(B, H, W, Cin, Cout):
     return bool(lib().idiff_conv2d_winograd43_ok(B, H, W, Cin, Cout))
 
 
-def conv2d_winograd43_colstats_split(B, H, W, Cin, Cout):
-    return lib().idiff_conv2d_winograd43_colstats_split(B, H, W, Cin, Cout)
-
-
 def conv2d_winograd43h_ok(B, H, W, Cin, Cout):
     """True when the fp16-pair F(4x4, 3x3) kernel serves this geometry (IDIFF_NO_WINO43H and the fp32 form's switches turn it off)."""
     return bool(lib().idiff_conv2d_winograd43h_ok(B, H, W, Cin, Cout))
 
 
+def conv2d_winograd43_colstats_split(B, H, W, Cin, Cout):
+    return lib().idiff_conv2d_winograd43_colstats_split(B, H, W, Cin, Cout)
+
+
 def winograd43_pack(wt, Cin, Cout, pairs=False):
-    """wt [Cout, 3, 3, Cin] -> the transformed filter bank of idiff_conv2d_winograd43_f32 (36 * Cin * Cout floats), or with
-    pairs=True that of idiff_conv2d_winograd43h_f32 (scaled fp16 pairs, 36 * Cin * Cout + 4 floats)."""
-    _dev(wt, "wt")
-    if wt.numel() != Cout * 9 * Cin:
-        raise RuntimeError(f"winograd43_pack: expected {Cout}x3x3x{Cin} weights, got {tuple(wt.shape)}")
-    if pairs:
-        u = torch.empty(lib().idiff_winograd43h_weight_floats(Cin, Cout), device=wt.device, dtype=torch.float32)
-        _check(lib().idiff_winograd43h_pack_f32(wt.data_ptr(), u.data_ptr(), Cin, Cout, _stream()), "idiff_winograd43h_pack_f32")
-        return u
-    u = torch.empty(lib().idiff_winograd43_weight_floats(Cin, Cout), device=wt.device, dtype=torch.float32)
-    _check(lib().idiff_winograd43_pack_f32(wt.data_ptr(), u.data_ptr(), Cin, Cout, _stream()), "idiff_winograd43_pack_f32")
-    return u
+    """The filter bank of idiff_conv2d_winograd43_f32 (36 * Cin * Cout floats), or with pairs=True that of idiff_conv2d_winograd43h_f32
+    (scaled fp16 pairs, 36 * Cin * Cout + 4 floats)."""
+    return _wino_pack("winograd43h" if pairs else "winograd43", "winograd43_pack", wt, Cin, Cout)
 
 
 def conv2d_winograd43(x, u, out, B, H, W, Cin, Cout, epilogue=None, pairs=False):
     """pairs: `u` is a bank of fp16 pairs (winograd43_pack(..., pairs=True)) and the contraction runs on the fp16 matrix cores."""
-    ep = ctypes.byref(epilogue) if epilogue is not None else None
     if pairs:
-        if u.numel() != 36 * Cin * Cout + 4:
-            raise RuntimeError(f"conv2d_winograd43: a bank of {u.numel()} floats ({36 * Cin * Cout + 4} expected): pack it with "
-                               "winograd43_pack(..., pairs=True)")
-        _check(lib().idiff_conv2d_winograd43h_f32(x.data_ptr(), u.data_ptr(), out.data_ptr(), B, H, W, Cin, Cout, ep, _stream()),
-               "idiff_conv2d_winograd43h_f32")
-        return out
-    if u.numel() != 36 * Cin * Cout:
-        raise RuntimeError(f"conv2d_winograd43: a filter bank of {u.numel()} floats ({36 * Cin * Cout} expected): pack it with winograd43_pack")
-    _check(lib().idiff_conv2d_winograd43_f32(x.data_ptr(), u.data_ptr(), out.data_ptr(), B, H, W, Cin, Cout, ep, _stream()),
-           "idiff_conv2d_winograd43_f32")
-    return out
+        return _wino_conv("winograd43h", "winograd43_pack(..., pairs=True)", x, u, out, B, H, W, Cin, Cout, epilogue)
+    return _wino_conv("winograd43", "winograd43_pack", x, u, out, B, H, W, Cin, Cout, epilogue)
 
 
 def conv2d_wino1d_ok(B, H, W, Cin, Cout):
@@ -531,24 +521,12 @@ def conv2d_wino1d_colstats_split(B, H, W, Cin, Cout):
 
 
 def wino1d_pack(wt, Cin, Cout):
-    """wt [Cout, 3, 3, Cin] -> the filter bank of idiff_conv2d_wino1d_f32 (scaled fp16 pairs of (G g[ky])[i], 18 * Cin * Cout + 4 floats)."""
-    if wt.dtype != torch.float32 or not wt.is_contiguous() or tuple(wt.shape) != (Cout, 3, 3, Cin):
-        raise RuntimeError(f"wino1d_pack: expected contiguous float32 {Cout}x3x3x{Cin} weights, got {wt.dtype} {tuple(wt.shape)}")
-    u = torch.empty(lib().idiff_wino1d_weight_floats(Cin, Cout), device=wt.device, dtype=torch.float32)
-    _check(lib().idiff_wino1d_pack_f32(wt.data_ptr(), u.data_ptr(), Cin, Cout, _stream()), "idiff_wino1d_pack_f32")
-    return u
+    """The filter bank of idiff_conv2d_wino1d_f32 (scaled fp16 pairs of (G g[ky])[i], 18 * Cin * Cout + 4 floats)."""
+    return _wino_pack("wino1d", "wino1d_pack", wt, Cin, Cout)
 
 
 def conv2d_wino1d(x, u, out, B, H, W, Cin, Cout, epilogue=None):
-    ep = ctypes.byref(epilogue) if epilogue is not None else None
-    if u.numel() != 18 * Cin * Cout + 4:
-        raise RuntimeError(f"conv2d_wino1d: a bank of {u.numel()} floats ({18 * Cin * Cout + 4} expected): pack it with wino1d_pack")
-    _check(lib().idiff_conv2d_wino1d_f32(x.data_ptr(), u.data_ptr(), out.data_ptr(), B, H, W, Cin, Cout, ep, _stream()), "idiff_conv2d_wino1d_f32")
-    return out
-
-
-def conv2d_winograd_colstats_split(B, H, W, Cin, Cout):
-    return lib().idiff_conv2d_winograd_colstats_split(B, H, W, Cin, Cout)
+    return _wino_conv("wino1d", "wino1d_pack", x, u, out, B, H, W, Cin, Cout, epilogue)
 
 
 # ------------------------------------------------------------------------------------------- norm / pointwise

@@ -2,7 +2,7 @@
 BeatGANsblocks.py:80-491, BeatGANs_nn.py:23-125; configuration family of
 configs/dimension_estimation/extra_experiments/styleGAN/style_gan_BeatGAN.py:29-82).
 
-Same execution model as ``ncsnpp.py`` (NHWC activations, one fp32-MFMA implicit-GEMM kernel for every
+Same executor as ``ncsnpp.py`` (``nhwc.py``: NHWC activations, one fp32-MFMA implicit-GEMM kernel for every
 contraction, fused epilogues, two-source GroupNorm instead of a materialised ``th.cat([x, lateral])``).  Specific
 to this network:
 
@@ -20,8 +20,7 @@ import torch.nn as nn
 
 from .. import _lib
 from . import utils
-from .base import HipScoreModel
-from .ncsnpp import NCSNpp, _T, _pad4
+from .nhwc import NhwcExecutor, _T, _pad4
 
 
 def _normalization(ch):
@@ -81,17 +80,7 @@ class Block(nn.Sequential):
 
 
 @utils.register_model(name='BeatGANsUNetModel')
-class BeatGANsUNetModel(HipScoreModel):
-    # shared NHWC primitives (defined once in ncsnpp.py)
-    _new = NCSNpp._new
-    _gn_act = NCSNpp._gn_act
-    _conv = NCSNpp._conv
-    _pointwise = NCSNpp._pointwise
-    _pointwise_pairs = NCSNpp._pointwise_pairs
-    _box = NCSNpp._box
-    _cat = NCSNpp._cat
-    _pack_conv = staticmethod(NCSNpp._pack_conv)
-
+class BeatGANsUNetModel(NhwcExecutor):
     def __init__(self, config):
         super().__init__()
         m = config.model
@@ -207,9 +196,8 @@ class BeatGANsUNetModel(HipScoreModel):
 
     def _attn(self, mod, x, pk):
         """AttentionBlock._forward (BeatGANsblocks.py:433-443) with QKVAttentionLegacy (:466-491), one head."""
-        B, HW, C = x.buf.shape[0], x.H * x.W, x.C
+        C = x.C
         n = self._gn_act(x, mod.norm, None)
-        pairs = self.pairs_admissible(mod.norm, n.norm[1], transform=False)
         key = (id(mod), "qkv")
         if key not in pk["lin"]:
             w = mod.qkv.weight.detach().float().view(3 * C, C)
@@ -217,31 +205,7 @@ class BeatGANsUNetModel(HipScoreModel):
             pk["lin"][key] = (w[:2 * C].contiguous(), b[:2 * C].contiguous(), w[2 * C:].contiguous(), b[2 * C:].contiguous(),
                               mod.proj_out.weight.detach().float().view(C, C).contiguous(),
                               mod.proj_out.bias.detach().float().contiguous())
-        wqk, bqk, wv, bv, wo, bo = pk["lin"][key]
-        dev = x.buf.device
-        qk = torch.empty(B * HW, 2 * C, device=dev, dtype=torch.float32)
-        _lib.gemm_normed(pk, n.buf.view(-1, C), wqk, qk, epilogue=_lib.make_epilogue(bias=bqk), pairs=pairs)    # n: a GroupNorm's output
-        vt = torch.empty(B, C, HW, device=dev, dtype=torch.float32)
-        _lib.gemm_weight_times_normed_t(pk, wv, n.buf, vt, B, HW, C, pairs=pairs)
-        mixed = torch.empty(B, HW, C, device=dev, dtype=torch.float32)
-        if pairs and _lib.attention256_ok(B, HW, C):
-            # one launch, the logits never written (csrc/attention.hip); (q * s) . (k * s) with s = ch^-1/4  ==  q . k * ch^-1/2
-            skey = (id(mod), "attn_scale")
-            if skey not in pk["lin"]:
-                gam = float(torch.sqrt((mod.norm.weight.detach().double() ** 2).mean() + (mod.norm.bias.detach().double() ** 2).mean()))
-                pk["lin"][skey] = (_lib.pairs_scale_from_rows(wqk, bqk, gam), _lib.pairs_scale_from_rows(wv, bv, gam))
-            s_qk, s_v = pk["lin"][skey]
-            _lib.attention256(qk, vt, mixed, B, C, s_qk, s_v, float(C) ** (-0.5), bias_v=bv)
-            return self._pointwise_pairs(pk, _T(mixed, x.H, x.W, C), wo, bo, s_v, residual=x.buf, stats=True)
-        else:
-            logits = torch.empty(B, HW, HW, device=dev, dtype=torch.float32)
-            _lib.gemm(qk, qk[:, C:], out=logits, M=HW, N=HW, K=C, lda=2 * C, ldb=2 * C, ldc=HW, batch=B,
-                      stride_a=HW * 2 * C, stride_b=HW * 2 * C, stride_c=HW * HW)
-            # (q * s) . (k * s) with s = ch^-1/4  ==  q . k * ch^-1/2
-            _lib.softmax_rows(logits, logits, B * HW, HW, float(C) ** (-0.5))
-            _lib.gemm(logits, vt, out=mixed, M=HW, N=C, K=HW, lda=HW, ldb=HW, ldc=C, batch=B, stride_a=HW * HW,
-                      stride_b=C * HW, stride_c=HW * C, epilogue=_lib.make_epilogue(bias=bv))  # V bias after P.V: rows of P sum to 1
-        return self._pointwise(_T(mixed, x.H, x.W, C), wo, bo, residual=x.buf, stats=True)
+        return self._attention(pk, x, n, mod.norm, *pk["lin"][key], pk["lin"], (id(mod), "attn_scale"))
 
     def _resample(self, mod, x, pk):
         if mod.up:

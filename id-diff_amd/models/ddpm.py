@@ -4,7 +4,7 @@ configs/dimension_estimation/paper/image_data/MNIST/config.py:121); SURVEY.md li
 
 The architecture is NCSN++ with its extras removed -- sinusoidal embedding, ``ResnetBlockDDPM`` (GroupNorm with 32
 groups, NIN shortcut, plain residual sum), ``AttnBlock``, nearest / average-pool or conv resampling, no FIR, no
-progressive paths -- so it reuses the NCSN++ executor (``ncsnpp.py``) unchanged: only the module list (= the
+progressive paths -- so it reuses the NCSN++ blocks (``ncsnpp.py``, on the executor of ``nhwc.py``) unchanged: only the module list (= the
 checkpoint key layout ``all_modules.<i>.*``) and the recorded plan are built here.
 """
 import torch.nn as nn

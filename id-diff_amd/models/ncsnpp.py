@@ -29,7 +29,7 @@ import torch.nn as nn
 
 from .. import _lib
 from . import utils
-from .base import HipScoreModel
+from .nhwc import NhwcExecutor, _T, _pad4
 
 _INV_SQRT2 = float(1.0 / np.sqrt(2.0))
 
@@ -152,57 +152,8 @@ class Combine(nn.Module):
 _ACT_NAMES = {"swish": "silu", "elu": "elu", "relu": "relu", "lrelu": "lrelu"}
 
 
-def _pad4(c):
-    return (c + 3) // 4 * 4
-
-
-class _T:
-    """An NHWC activation: buffer [B, H*W, C] + geometry (+ the per-tile column sums [B, nsplit, C, 2] its producing
-    contraction wrote through epilogue.colstats, which let the consuming GroupNorm skip its statistics pass)."""
-    __slots__ = ("buf", "H", "W", "C", "stats", "norm")
-
-    def __init__(self, buf, H, W, C, stats=None, norm=None):
-        self.buf, self.H, self.W, self.C, self.stats = buf, H, W, C, stats
-        # set on the output of a GroupNorm (and kept through the resamplers): (module, elements per normalised group, absolute gain of
-        # what followed, modulated?) -- what HipScoreModel.pairs_admissible needs to decide whether the consumer may run on fp16 pairs
-        self.norm = norm
-
-
-# ------------------------------------------------------------------------------------------------------------
-# launches of fewer workgroups than this stay on the F(2x2, 3x3) kernel (tests set it to 1 to send small batches through F(4x4, 3x3))
-WINO43_MIN_WORKGROUPS = 512
-WINO43_PAIRS_MIN_WORKGROUPS = 256
-
-
-def _winograd43_pays(B, H, W, cin, cout, normed=False):
-    """F(4x4, 3x3) where it is served AND faster than F(2x2, 3x3): a workgroup takes 32 tiles of 4x4 pixels x 64 channels and a
-    CU holds one.  With the contraction on the fp32 matrix cores, maps of 4x4 pixels (one tile per sample) or launches of fewer
-    than two workgroups per CU stay on the 2x2 form (measured 0.87x there, 1.2-1.33x elsewhere: profiles/r04_wino43_time.txt);
-    on fp16 pairs (``normed`` inputs, see _conv) it wins from one workgroup per CU on, 4x4 maps included (127 us against 207,
-    209 against 370 at B = 2240, 256 / 512 -> 256 channels)."""
-    if normed and _lib.conv2d_winograd43h_ok(B, H, W, cin, cout):
-        return ((B * (H // 4) * (W // 4) + 31) // 32) * (cout // 64) >= WINO43_PAIRS_MIN_WORKGROUPS
-    if H < 8 or W < 8 or not _lib.conv2d_winograd43_ok(B, H, W, cin, cout):
-        return False
-    return ((B * (H // 4) * (W // 4) + 31) // 32) * (cout // 64) >= WINO43_MIN_WORKGROUPS
-
-
-# launches of fewer workgroups than this, and maps narrower than this, stay on the 2-D pair kernel (tests set the first to 1)
-WINO1D_MIN_WORKGROUPS = 256
-WINO1D_MIN_WIDTH = 4
-
-
-def _wino1d_pays(B, H, W, cin, cout):
-    """The row-wise F(4, 3) pair kernel (csrc/wino1d.hip: twice the matrix work of F(4x4, 3x3) for half the operand traffic) where it is served
-    and measured at least as fast as the 2-D pair kernel: at one workgroup (512 pixels x 64 channels) per CU and more -- 1.08-1.23x on 16 x 16
-    and 32 x 32 maps, 1.03-1.06x on 8 x 8, 1.00-1.01x on 4 x 4 (profiles/r05_wino1d_probe.txt, B = 2240); 64-pixel rows (config 5) likewise."""
-    if W < WINO1D_MIN_WIDTH or not _lib.conv2d_wino1d_ok(B, H, W, cin, cout):
-        return False
-    return ((B * H * W + 511) // 512) * (cout // 64) >= WINO1D_MIN_WORKGROUPS
-
-
 @utils.register_model(name='ncsnpp')
-class NCSNpp(HipScoreModel):
+class NCSNpp(NhwcExecutor):
     def __init__(self, config):
         super().__init__()
         m = config.model
@@ -311,20 +262,6 @@ class NCSNpp(HipScoreModel):
 
     # -------------------------------------------------------------------------------------------- packing
     @staticmethod
-    def _pack_conv(conv, cin_split=None):
-        """[Cout, Cin, KH, KW] -> K-contiguous panel [Cout, KH, KW, Cin_pad]; optional split of Cin in two."""
-        w = conv.weight.detach().float()
-        cout, cin, kh, kw = w.shape
-        parts = [w] if cin_split is None else [w[:, :cin_split], w[:, cin_split:]]
-        out = []
-        for part in parts:
-            c = part.shape[1]
-            buf = torch.zeros(cout, kh, kw, _pad4(c), device=w.device)
-            buf[..., :c] = part.permute(0, 2, 3, 1)
-            out.append(buf.contiguous())
-        return out if cin_split is not None else out[0]
-
-    @staticmethod
     def _pack_nin(nin, cin_split=None):
         w = nin.W.detach().float().t().contiguous()  # [cout, cin]
         if cin_split is None:
@@ -369,143 +306,6 @@ class NCSNpp(HipScoreModel):
         return pk["nin"][key]
 
     # -------------------------------------------------------------------------------------------- primitive steps
-    def _new(self, B, H, W, C, like):
-        return _T(torch.empty(B, H * W, C, device=like.device, dtype=torch.float32), H, W, C)
-
-    def _gn_act(self, x, gn, act, x2=None, mod=None):
-        """GroupNorm (+ scale-shift modulation ``mod`` [B, 2*Ctot]) (+activation) of x (or of cat[x, x2])."""
-        B = x.buf.shape[0]
-        HW = x.H * x.W
-        C2 = x2.C if x2 is not None else 0
-        G = gn.num_groups
-        norm = (gn, ((x.C + C2) // G) * HW, 1.0, mod is not None)
-        if x.stats is not None and (x2 is None or x2.stats is not None) and x.C + C2 <= 1024 and B <= 65535:
-            # both sources carry the column sums their producing contraction wrote: no pass over the activations, and the
-            # statistics are finished inside the apply kernel (one launch per GroupNorm)
-            ws2, ns2 = x2.stats if x2 is not None else (None, 0)
-            y = self._new(B, x.H, x.W, x.C + C2, x.buf)
-            _lib.groupnorm_apply_colstats(x.buf, x.C, x2.buf if x2 is not None else None, C2, B, HW, G, x.stats[0], x.stats[1],
-                                          ws2, ns2, gn.eps, gn.weight.detach(), gn.bias.detach(), act, y.buf, mod=mod)
-            y.norm = norm
-            return y
-        stats = torch.empty(B * G * 2, device=x.buf.device, dtype=torch.float32)
-        if x.stats is not None and (x2 is None or x2.stats is not None):
-            ws2, ns2 = x2.stats if x2 is not None else (None, 0)
-            _lib.groupnorm_finalize(x.stats[0], x.stats[1], x.C, ws2, ns2, C2, B, HW, G, gn.eps, stats)
-        else:
-            nsplit = _lib.groupnorm_nsplit(B, HW, x.C + C2)
-            ws = torch.empty(B * nsplit * (x.C + C2) * 2, device=x.buf.device, dtype=torch.float64)
-            _lib.groupnorm_stats(x.buf, x.C, x2.buf if x2 is not None else None, C2, B, HW, G, gn.eps, ws, stats)
-        y = self._new(B, x.H, x.W, x.C + C2, x.buf)
-        _lib.groupnorm_apply(x.buf, x.C, x2.buf if x2 is not None else None, C2, B, HW, G, stats,
-                             gn.weight.detach(), gn.bias.detach(), act, y.buf, mod=mod)
-        y.norm = norm
-        return y
-
-    def _conv(self, x, wt, bias, stride=1, pad=1, pad_hi=None, stats=False, normed=False, **ep):
-        """``stats=True``: the output feeds a GroupNorm -> ask the epilogue for its per-tile column sums.
-        ``normed=True``: the input is the output of a GroupNorm (+ activation, + FIR resampling), i.e. bounded by
-        sqrt(group size) * |gamma| + |beta| -- only then may the F(4x4, 3x3) contraction run on fp16 pairs, whose transformed input
-        must stay below 65504 (include/idiff_hip.h), and only if THIS checkpoint's gamma / beta keep that bound inside the range
-        (base.HipScoreModel.pairs_admissible, decided once per layer at pack time); any other input takes the fp32 contraction."""
-        B = x.buf.shape[0]
-        cout, kh, kw, cin = wt.shape
-        assert cin == x.C, (cin, x.C)
-        if normed:
-            assert x.norm is not None, "normed=True on a tensor that is not a GroupNorm's (resampled) output"
-            gn, group_elems, gain, modulated = x.norm
-            normed = self.pairs_admissible(gn, group_elems, gain=gain, transform=True, modulated=modulated)
-        ph = pad if pad_hi is None else pad_hi
-        OH = (x.H + pad + ph - kh) // stride + 1
-        OW = (x.W + pad + ph - kw) // stride + 1
-        y = self._new(B, OH, OW, cout, x.buf)
-        if "rows_per_group" not in ep:
-            ep["rows_per_group"] = OH * OW
-        if (kh, kw, stride, pad, ph) == (3, 3, 1, 1, 1) and ep["rows_per_group"] == OH * OW and normed and _wino1d_pays(B, x.H, x.W, cin, cout):
-            # Winograd F(4, 3) along the rows on fp16 pairs: 4.5 multiplications per output, half the operand traffic of the 2-D form
-            bank = self._packed.setdefault("wino1d", {})
-            key = id(wt)
-            if key not in bank:
-                bank[key] = (wt, _lib.wino1d_pack(wt, cin, cout))
-            if stats:
-                ns = _lib.conv2d_wino1d_colstats_split(B, x.H, x.W, cin, cout)
-                if ns > 0:
-                    y.stats = (torch.empty(B * ns * cout * 2, device=x.buf.device, dtype=torch.float64), ns)
-                    ep["colstats"] = y.stats[0]
-            _lib.conv2d_wino1d(x.buf, bank[key][1], y.buf, B, x.H, x.W, cin, cout, epilogue=_lib.make_epilogue(bias=bias, **ep))
-            return y
-        if (kh, kw, stride, pad, ph) == (3, 3, 1, 1, 1) and ep["rows_per_group"] == OH * OW and _winograd43_pays(B, x.H, x.W, cin, cout, normed):
-            # Winograd F(4x4, 3x3): 2.25 multiplications per output (F(2x2, 3x3) below: 4, the implicit GEMM: 9)
-            bank = self._packed.setdefault("wino43", {})
-            pairs = normed and _lib.conv2d_winograd43h_ok(B, x.H, x.W, cin, cout)
-            key = (id(wt), pairs)
-            if key not in bank:
-                bank[key] = (wt, _lib.winograd43_pack(wt, cin, cout, pairs=pairs))
-            if stats:
-                ns = _lib.conv2d_winograd43_colstats_split(B, x.H, x.W, cin, cout)
-                if ns > 0:
-                    y.stats = (torch.empty(B * ns * cout * 2, device=x.buf.device, dtype=torch.float64), ns)
-                    ep["colstats"] = y.stats[0]
-            _lib.conv2d_winograd43(x.buf, bank[key][1], y.buf, B, x.H, x.W, cin, cout, epilogue=_lib.make_epilogue(bias=bias, **ep), pairs=pairs)
-            return y
-        if (kh, kw, stride, pad, ph) == (3, 3, 1, 1, 1) and _lib.conv2d_winograd_ok(B, x.H, x.W, cin, cout):
-            # Winograd F(2x2, 3x3): 2.25x fewer MFMA flops; the transformed filter bank is cached beside the panel
-            # (keyed by the kernel form too: the split-precision form is asked for per call, so a switch flipped later or
-            # another geometry through this layer picks its own bank instead of inheriting the first one packed)
-            bank = self._packed.setdefault("wino", {})
-            split = _lib.conv2d_winograd_split_ok(B, x.H, x.W, cin, cout)
-            key = (id(wt), split)
-            if key not in bank:
-                bank[key] = (wt, _lib.winograd_pack(wt, cin, cout, split=split))
-            if stats:
-                ns = _lib.conv2d_winograd_colstats_split(B, x.H, x.W, cin, cout)
-                if ns > 0:
-                    y.stats = (torch.empty(B * ns * cout * 2, device=x.buf.device, dtype=torch.float64), ns)
-                    ep["colstats"] = y.stats[0]
-            _lib.conv2d_winograd(x.buf, bank[key][1], y.buf, B, x.H, x.W, cin, cout,
-                                 epilogue=_lib.make_epilogue(bias=bias, **ep), split=split)
-            return y
-        if stats:
-            ns = _lib.conv2d_colstats_split(B, x.H, x.W, cin, cout, kh, kw, stride, pad, pad_hi)
-            if ns > 0:
-                y.stats = (torch.empty(B * ns * cout * 2, device=x.buf.device, dtype=torch.float64), ns)
-                ep["colstats"] = y.stats[0]
-        _lib.conv2d_nhwc(x.buf, wt, y.buf, B, x.H, x.W, cin, cout, kh, kw, stride, pad,
-                         epilogue=_lib.make_epilogue(bias=bias, **ep), pad_hi=pad_hi)
-        return y
-
-    def _pointwise(self, x, w, bias, stats=False, **ep):
-        """1x1 conv / NIN on NHWC = plain GEMM over [B*HW, Cin]; w is [Cout, Cin]."""
-        B = x.buf.shape[0]
-        cout, cin = w.shape
-        assert cin == x.C, (cin, x.C)
-        y = self._new(B, x.H, x.W, cout, x.buf)
-        if stats:
-            ns = _lib.gemm_colstats_split(B * x.H * x.W, cout, cin, cin, w.stride(0), x.H * x.W)
-            if ns > 0:
-                y.stats = (torch.empty(B * ns * cout * 2, device=x.buf.device, dtype=torch.float64), ns)
-                ep["colstats"] = y.stats[0]
-        _lib.gemm(x.buf.view(-1, cin), w, out=y.buf.view(-1, cout), epilogue=_lib.make_epilogue(bias=bias, **ep))
-        return y
-
-    def _pointwise_pairs(self, pk, x, w, bias, act_scale, stats=False, **ep):
-        """_pointwise on fp16 pairs for an activation that is NOT a GroupNorm's output but whose scale is known: ``act_scale`` = device
-        {s, 1 / s} (the attention output is a convex combination of the rows of v: never beyond v's range, so v's scale serves)."""
-        B = x.buf.shape[0]
-        cout, cin = w.shape
-        M = B * x.H * x.W
-        if not _lib.gemm_pairs_ok(M, cout, cin):
-            return self._pointwise(x, w, bias, stats=stats, **ep)
-        y = self._new(B, x.H, x.W, cout, x.buf)
-        if stats:
-            ns = _lib.gemm_colstats_split(M, cout, cin, cin, w.stride(0), x.H * x.W)
-            if ns > 0:
-                y.stats = (torch.empty(B * ns * cout * 2, device=x.buf.device, dtype=torch.float64), ns)
-                ep["colstats"] = y.stats[0]
-        _lib.gemm_pairs(x.buf.view(-1, cin), w, _lib._pairs_scale_of(pk, w), y.buf.view(-1, cout),
-                        epilogue=_lib.make_epilogue(bias=bias, **ep), act_scale=act_scale)
-        return y
-
     def _fir(self, x, pk, mode):
         B = x.buf.shape[0]
         n = pk["fir_len"]
@@ -524,24 +324,6 @@ class NCSNpp(HipScoreModel):
         _lib.upfirdn2d_raw(x.buf, k, y.buf, B, x.H, x.W, x.C, up, up, down, down, p0, p1, p0, p1)
         if x.norm is not None:
             y.norm = (x.norm[0], x.norm[1], x.norm[2] * pk["fir_gain"][mode], x.norm[3])
-        return y
-
-    def _box(self, x, up):
-        B = x.buf.shape[0]
-        y = self._new(B, x.H * 2 if up else x.H // 2, x.W * 2 if up else x.W // 2, x.C, x.buf)
-        _lib.resample2x_nhwc(x.buf, y.buf, B, x.H, x.W, x.C, up)
-        y.norm = x.norm                                        # nearest x2 / 2x2 mean: never beyond the input's range
-        return y
-
-    def _add(self, a, b, scale):
-        y = self._new(a.buf.shape[0], a.H, a.W, a.C, a.buf)
-        _lib.add_scale(a.buf, b.buf, y.buf, a.buf.numel(), scale)
-        return y
-
-    def _cat(self, a, b):
-        B = a.buf.shape[0]
-        y = self._new(B, a.H, a.W, a.C + b.C, a.buf)
-        _lib.concat_cols(a.buf, a.C, b.buf, b.C, y.buf, B * a.H * a.W)
         return y
 
     # -------------------------------------------------------------------------------------------- blocks
@@ -590,42 +372,14 @@ class NCSNpp(HipScoreModel):
     def _attn(self, idx, x, pk):
         """AttnBlockpp (layerspp.py:62-91)."""
         mod = self.all_modules[idx]
-        B, HW, C = x.buf.shape[0], x.H * x.W, x.C
         n = self._gn_act(x, mod.GroupNorm_0, None)
-        pairs = self.pairs_admissible(mod.GroupNorm_0, n.norm[1], transform=False)
         if (idx, "qk") not in pk["nin"]:
             wq, bq = self._nin_w(pk, (idx, 0), mod.NIN_0)
             wk, bk = self._nin_w(pk, (idx, 1), mod.NIN_1)
             pk["nin"][(idx, "qk")] = (torch.cat([wq, wk], 0).contiguous(), torch.cat([bq, bk], 0).contiguous())
-        wqk, bqk = pk["nin"][(idx, "qk")]
-        wv, bv = self._nin_w(pk, (idx, 2), mod.NIN_2)
-        w3, b3 = self._nin_w(pk, (idx, 3), mod.NIN_3)
-        dev = x.buf.device
-        qk = torch.empty(B * HW, 2 * C, device=dev, dtype=torch.float32)
-        _lib.gemm_normed(pk, n.buf.view(-1, C), wqk, qk, epilogue=_lib.make_epilogue(bias=bqk), pairs=pairs)    # n: a GroupNorm's output
-        # V^T[b] = Wv^T-panel [C, Cin] x n[b]^T -> [C, HW], K-contiguous for the P.V product (bias deferred)
-        vt = torch.empty(B, C, HW, device=dev, dtype=torch.float32)
-        _lib.gemm_weight_times_normed_t(pk, wv, n.buf, vt, B, HW, C, pairs=pairs)
-        mixed = torch.empty(B, HW, C, device=dev, dtype=torch.float32)
-        rs = _INV_SQRT2 if self.skip_rescale else 1.0
-        if pairs and _lib.attention256_ok(B, HW, C):
-            # QK^T -> softmax -> PV in one launch, the logits never written (csrc/attention.hip); the operands' power-of-two scales from
-            # the projections' row norms (their input n has unit variance times gamma's scale)
-            key = (idx, "attn_scale")
-            if key not in pk["nin"]:
-                gam = float(torch.sqrt((mod.GroupNorm_0.weight.detach().double() ** 2).mean() + (mod.GroupNorm_0.bias.detach().double() ** 2).mean()))
-                pk["nin"][key] = (_lib.pairs_scale_from_rows(wqk, bqk, gam), _lib.pairs_scale_from_rows(wv, bv, gam))
-            s_qk, s_v = pk["nin"][key]
-            _lib.attention256(qk, vt, mixed, B, C, s_qk, s_v, float(int(C) ** (-0.5)), bias_v=bv)
-            return self._pointwise_pairs(pk, _T(mixed, x.H, x.W, C), w3, b3, s_v, residual=x.buf, out_scale=rs, stats=True)
-        else:
-            logits = torch.empty(B, HW, HW, device=dev, dtype=torch.float32)
-            _lib.gemm(qk, qk[:, C:], out=logits, M=HW, N=HW, K=C, lda=2 * C, ldb=2 * C, ldc=HW, batch=B,
-                      stride_a=HW * 2 * C, stride_b=HW * 2 * C, stride_c=HW * HW)
-            _lib.softmax_rows(logits, logits, B * HW, HW, float(int(C) ** (-0.5)))
-            _lib.gemm(logits, vt, out=mixed, M=HW, N=C, K=HW, lda=HW, ldb=HW, ldc=C, batch=B,
-                      stride_a=HW * HW, stride_b=C * HW, stride_c=HW * C, epilogue=_lib.make_epilogue(bias=bv))
-        return self._pointwise(_T(mixed, x.H, x.W, C), w3, b3, residual=x.buf, out_scale=rs, stats=True)
+        return self._attention(pk, x, n, mod.GroupNorm_0, *pk["nin"][(idx, "qk")], *self._nin_w(pk, (idx, 2), mod.NIN_2),
+                               *self._nin_w(pk, (idx, 3), mod.NIN_3), pk["nin"], (idx, "attn_scale"),
+                               out_scale=_INV_SQRT2 if self.skip_rescale else 1.0)
 
     def _downsample(self, idx, x, pk, **ep):
         """layerspp.Downsample (:129-163) for every (fir, with_conv) pair."""

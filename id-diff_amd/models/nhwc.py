@@ -1,0 +1,285 @@
+"""The NHWC executor the image score networks share: the primitive steps that do not know which network they serve.
+
+An activation is a ``_T`` ([B, H*W, C] + geometry); every step is one or a few launches from libidiff_hip.so.  ``NCSNpp`` (and
+``DDPM``) and ``BeatGANsUNetModel`` inherit ``NhwcExecutor`` and add what is theirs: the module list (= the reference's
+``state_dict`` layout), the plan, the weight packing, FIR resampling.  Which kernel serves a 3x3 convolution is decided in one
+place, ``CONV3X3_ROUTES`` / ``conv3x3_route``: host logic only, testable without a GPU.
+"""
+from typing import Callable, NamedTuple
+
+import torch
+
+from .. import _lib
+from .base import HipScoreModel
+
+
+def _pad4(c):
+    return (c + 3) // 4 * 4
+
+
+class _T:
+    """An NHWC activation: buffer [B, H*W, C] + geometry (+ the per-tile column sums [B, nsplit, C, 2] its producing
+    contraction wrote through epilogue.colstats, which let the consuming GroupNorm skip its statistics pass)."""
+    __slots__ = ("buf", "H", "W", "C", "stats", "norm")
+
+    def __init__(self, buf, H, W, C, stats=None, norm=None):
+        self.buf, self.H, self.W, self.C, self.stats = buf, H, W, C, stats
+        # set on the output of a GroupNorm (and kept through the resamplers): (module, elements per normalised group, absolute gain of
+        # what followed, modulated?) -- what HipScoreModel.pairs_admissible needs to decide whether the consumer may run on fp16 pairs
+        self.norm = norm
+
+
+# ------------------------------------------------------------------------------------------------------------
+# The 3x3 stride-1 pad-1 routes.  The thresholds are read at call time (tests set the *_MIN_WORKGROUPS to 1 to send test-sized
+# batches through the large-batch kernels: they are speed rules, not correctness ones) and the ``_lib.*_ok`` predicates are asked
+# per call (a switch flipped by ``thread_option`` between two forwards of one model takes effect).
+# launches of fewer workgroups than this stay on the F(2x2, 3x3) kernel
+WINO43_MIN_WORKGROUPS = 512
+WINO43_PAIRS_MIN_WORKGROUPS = 256
+# launches of fewer workgroups than this, and maps narrower than this, stay on the 2-D pair kernel
+WINO1D_MIN_WORKGROUPS = 256
+WINO1D_MIN_WIDTH = 4
+
+
+def _wino43_workgroups(B, H, W, cout):
+    """A workgroup takes 32 tiles of 4x4 pixels x 64 channels and a CU holds one."""
+    return ((B * (H // 4) * (W // 4) + 31) // 32) * (cout // 64)
+
+
+def _wino1d_serves(B, H, W, cin, cout, normed, per_image):
+    """The row-wise F(4, 3) pair kernel (csrc/wino1d.hip: twice the matrix work of F(4x4, 3x3) for half the operand traffic) where it is served
+    and measured at least as fast as the 2-D pair kernel: at one workgroup (512 pixels x 64 channels) per CU and more -- 1.08-1.23x on 16 x 16
+    and 32 x 32 maps, 1.03-1.06x on 8 x 8, 1.00-1.01x on 4 x 4 (profiles/r05_wino1d_probe.txt, B = 2240); 64-pixel rows (config 5) likewise."""
+    return (per_image and normed and W >= WINO1D_MIN_WIDTH and _lib.conv2d_wino1d_ok(B, H, W, cin, cout)
+            and ((B * H * W + 511) // 512) * (cout // 64) >= WINO1D_MIN_WORKGROUPS)
+
+
+def _wino43_pairs_serves(B, H, W, cin, cout, normed, per_image):
+    """F(4x4, 3x3) on fp16 pairs (``normed`` inputs, see NhwcExecutor._conv): faster than F(2x2, 3x3) from one workgroup per CU on, 4x4
+    maps included (127 us against 207, 209 against 370 at B = 2240, 256 / 512 -> 256 channels)."""
+    return (per_image and normed and _lib.conv2d_winograd43h_ok(B, H, W, cin, cout)
+            and _wino43_workgroups(B, H, W, cout) >= WINO43_PAIRS_MIN_WORKGROUPS)
+
+
+def _wino43_fp32_serves(B, H, W, cin, cout, normed, per_image):
+    """F(4x4, 3x3) with the contraction on the fp32 matrix cores: maps of 4x4 pixels (one tile per sample) or launches of fewer than two
+    workgroups per CU stay on the 2x2 form (measured 0.87x there, 1.2-1.33x elsewhere: profiles/r04_wino43_time.txt)."""
+    return (per_image and H >= 8 and W >= 8 and _lib.conv2d_winograd43_ok(B, H, W, cin, cout)
+            and _wino43_workgroups(B, H, W, cout) >= WINO43_MIN_WORKGROUPS)
+
+
+def _wino22_serves(B, H, W, cin, cout, normed, per_image):
+    return _lib.conv2d_winograd_ok(B, H, W, cin, cout)
+
+
+class Conv3x3Route(NamedTuple):
+    """One kernel family.  ``pack`` / ``split`` / ``launch`` are NAMES of ``_lib`` functions, looked up on the module at the call
+    (the benchmark's probe and the tests replace them by attribute).  ``form(B, H, W, cin, cout)``: the keyword that names the
+    kernel form to both pack and launch; its value keys the bank beside ``id(wt)``."""
+    name: str
+    bank: str                # self._packed[bank]: dropped with the weights by _invalidate()
+    serves: Callable         # (B, H, W, cin, cout, normed, per_image) -> bool; launches nothing
+    pack: str
+    split: str
+    launch: str
+    form: Callable
+
+
+# first match wins; none of them: the implicit GEMM (conv2d_nhwc, any kernel size / stride / pad)
+CONV3X3_ROUTES = (
+    # Winograd F(4, 3) along the rows on fp16 pairs: 4.5 multiplications per output, half the operand traffic of the 2-D form
+    Conv3x3Route("wino1d", "wino1d", _wino1d_serves, "wino1d_pack", "conv2d_wino1d_colstats_split", "conv2d_wino1d",
+                 lambda *geom: {}),
+    # Winograd F(4x4, 3x3): 2.25 multiplications per output (F(2x2, 3x3) below: 4, the implicit GEMM: 9)
+    Conv3x3Route("wino43_pairs", "wino43", _wino43_pairs_serves, "winograd43_pack", "conv2d_winograd43_colstats_split",
+                 "conv2d_winograd43", lambda *geom: {"pairs": True}),
+    Conv3x3Route("wino43_fp32", "wino43", _wino43_fp32_serves, "winograd43_pack", "conv2d_winograd43_colstats_split",
+                 "conv2d_winograd43", lambda *geom: {"pairs": False}),
+    # Winograd F(2x2, 3x3): 2.25x fewer MFMA flops than the implicit GEMM.  The bank is keyed by the kernel form too: the
+    # split-precision form is asked for per call, so a switch flipped later or another geometry through this layer picks its
+    # own bank instead of inheriting the first one packed
+    Conv3x3Route("wino22", "wino", _wino22_serves, "winograd_pack", "conv2d_winograd_colstats_split", "conv2d_winograd",
+                 lambda *geom: {"split": _lib.conv2d_winograd_split_ok(*geom)}),
+)
+
+
+def conv3x3_route(B, H, W, cin, cout, normed, per_image):
+    """The route of a 3x3 stride-1 pad-1 convolution of [B, H, W, cin] to cout channels, or None for the implicit GEMM.
+    ``normed``: the input is a GroupNorm's output admitted to the fp16-pair kernels; ``per_image``: the epilogue's row groups are
+    whole images (the per-sample time-embedding bias of the residual blocks)."""
+    for route in CONV3X3_ROUTES:
+        if route.serves(B, H, W, cin, cout, normed, per_image):
+            return route
+    return None
+
+
+class NhwcExecutor(HipScoreModel):
+    @staticmethod
+    def _pack_conv(conv, cin_split=None):
+        """[Cout, Cin, KH, KW] -> K-contiguous panel [Cout, KH, KW, Cin_pad]; optional split of Cin in two."""
+        w = conv.weight.detach().float()
+        cout, cin, kh, kw = w.shape
+        parts = [w] if cin_split is None else [w[:, :cin_split], w[:, cin_split:]]
+        out = []
+        for part in parts:
+            c = part.shape[1]
+            buf = torch.zeros(cout, kh, kw, _pad4(c), device=w.device)
+            buf[..., :c] = part.permute(0, 2, 3, 1)
+            out.append(buf.contiguous())
+        return out if cin_split is not None else out[0]
+
+    def _new(self, B, H, W, C, like):
+        return _T(torch.empty(B, H * W, C, device=like.device, dtype=torch.float32), H, W, C)
+
+    @staticmethod
+    def _colstats(y, ns, ep):
+        """``y`` feeds a GroupNorm and the kernel that produces it writes ``ns`` per-tile column sums per sample (0: it cannot): allocate
+        them, hand them to the epilogue ``ep``, keep them beside the activation."""
+        if ns > 0:
+            y.stats = (torch.empty(y.buf.shape[0] * ns * y.C * 2, device=y.buf.device, dtype=torch.float64), ns)
+            ep["colstats"] = y.stats[0]
+
+    def _gn_act(self, x, gn, act, x2=None, mod=None):
+        """GroupNorm (+ scale-shift modulation ``mod`` [B, 2*Ctot]) (+activation) of x (or of cat[x, x2])."""
+        B = x.buf.shape[0]
+        HW = x.H * x.W
+        C2 = x2.C if x2 is not None else 0
+        G = gn.num_groups
+        norm = (gn, ((x.C + C2) // G) * HW, 1.0, mod is not None)
+        if x.stats is not None and (x2 is None or x2.stats is not None) and x.C + C2 <= 1024 and B <= 65535:
+            # both sources carry the column sums their producing contraction wrote: no pass over the activations, and the
+            # statistics are finished inside the apply kernel (one launch per GroupNorm)
+            ws2, ns2 = x2.stats if x2 is not None else (None, 0)
+            y = self._new(B, x.H, x.W, x.C + C2, x.buf)
+            _lib.groupnorm_apply_colstats(x.buf, x.C, x2.buf if x2 is not None else None, C2, B, HW, G, x.stats[0], x.stats[1],
+                                          ws2, ns2, gn.eps, gn.weight.detach(), gn.bias.detach(), act, y.buf, mod=mod)
+            y.norm = norm
+            return y
+        stats = torch.empty(B * G * 2, device=x.buf.device, dtype=torch.float32)
+        if x.stats is not None and (x2 is None or x2.stats is not None):
+            ws2, ns2 = x2.stats if x2 is not None else (None, 0)
+            _lib.groupnorm_finalize(x.stats[0], x.stats[1], x.C, ws2, ns2, C2, B, HW, G, gn.eps, stats)
+        else:
+            nsplit = _lib.groupnorm_nsplit(B, HW, x.C + C2)
+            ws = torch.empty(B * nsplit * (x.C + C2) * 2, device=x.buf.device, dtype=torch.float64)
+            _lib.groupnorm_stats(x.buf, x.C, x2.buf if x2 is not None else None, C2, B, HW, G, gn.eps, ws, stats)
+        y = self._new(B, x.H, x.W, x.C + C2, x.buf)
+        _lib.groupnorm_apply(x.buf, x.C, x2.buf if x2 is not None else None, C2, B, HW, G, stats,
+                             gn.weight.detach(), gn.bias.detach(), act, y.buf, mod=mod)
+        y.norm = norm
+        return y
+
+    def _conv(self, x, wt, bias, stride=1, pad=1, pad_hi=None, stats=False, normed=False, **ep):
+        """``stats=True``: the output feeds a GroupNorm -> ask the epilogue for its per-tile column sums.
+        ``normed=True``: the input is the output of a GroupNorm (+ activation, + FIR resampling), i.e. bounded by
+        sqrt(group size) * |gamma| + |beta| -- only then may the Winograd contraction run on fp16 pairs, whose transformed input
+        must stay below 65504 (include/idiff_hip.h), and only if THIS checkpoint's gamma / beta keep that bound inside the range
+        (base.HipScoreModel.pairs_admissible, decided once per layer at pack time); any other input takes the fp32 contraction."""
+        B = x.buf.shape[0]
+        cout, kh, kw, cin = wt.shape
+        assert cin == x.C, (cin, x.C)
+        if normed:
+            assert x.norm is not None, "normed=True on a tensor that is not a GroupNorm's (resampled) output"
+            gn, group_elems, gain, modulated = x.norm
+            normed = self.pairs_admissible(gn, group_elems, gain=gain, transform=True, modulated=modulated)
+        ph = pad if pad_hi is None else pad_hi
+        OH = (x.H + pad + ph - kh) // stride + 1
+        OW = (x.W + pad + ph - kw) // stride + 1
+        y = self._new(B, OH, OW, cout, x.buf)
+        if "rows_per_group" not in ep:
+            ep["rows_per_group"] = OH * OW
+        geom = (B, x.H, x.W, cin, cout)
+        route = None
+        if (kh, kw, stride, pad, ph) == (3, 3, 1, 1, 1):
+            route = conv3x3_route(*geom, normed, ep["rows_per_group"] == OH * OW)
+        if route is None:
+            if stats:
+                self._colstats(y, _lib.conv2d_colstats_split(*geom, kh, kw, stride, pad, pad_hi), ep)
+            _lib.conv2d_nhwc(x.buf, wt, y.buf, *geom, kh, kw, stride, pad, epilogue=_lib.make_epilogue(bias=bias, **ep), pad_hi=pad_hi)
+            return y
+        # the transformed filter bank is cached beside the panel; the entry keeps `wt` so that its id cannot be reused while it lives
+        form = route.form(*geom)
+        bank = self._packed.setdefault(route.bank, {})
+        key = (id(wt), *form.values()) if form else id(wt)
+        if key not in bank:
+            bank[key] = (wt, getattr(_lib, route.pack)(wt, cin, cout, **form))
+        if stats:
+            self._colstats(y, getattr(_lib, route.split)(*geom), ep)
+        getattr(_lib, route.launch)(x.buf, bank[key][1], y.buf, *geom, epilogue=_lib.make_epilogue(bias=bias, **ep), **form)
+        return y
+
+    def _pointwise(self, x, w, bias, stats=False, **ep):
+        """1x1 conv / NIN on NHWC = plain GEMM over [B*HW, Cin]; w is [Cout, Cin]."""
+        B = x.buf.shape[0]
+        cout, cin = w.shape
+        assert cin == x.C, (cin, x.C)
+        y = self._new(B, x.H, x.W, cout, x.buf)
+        if stats:
+            self._colstats(y, _lib.gemm_colstats_split(B * x.H * x.W, cout, cin, cin, w.stride(0), x.H * x.W), ep)
+        _lib.gemm(x.buf.view(-1, cin), w, out=y.buf.view(-1, cout), epilogue=_lib.make_epilogue(bias=bias, **ep))
+        return y
+
+    def _pointwise_pairs(self, pk, x, w, bias, act_scale, stats=False, **ep):
+        """_pointwise on fp16 pairs for an activation that is NOT a GroupNorm's output but whose scale is known: ``act_scale`` = device
+        {s, 1 / s} (the attention output is a convex combination of the rows of v: never beyond v's range, so v's scale serves)."""
+        B = x.buf.shape[0]
+        cout, cin = w.shape
+        M = B * x.H * x.W
+        if not _lib.gemm_pairs_ok(M, cout, cin):
+            return self._pointwise(x, w, bias, stats=stats, **ep)
+        y = self._new(B, x.H, x.W, cout, x.buf)
+        if stats:
+            self._colstats(y, _lib.gemm_colstats_split(M, cout, cin, cin, w.stride(0), x.H * x.W), ep)
+        _lib.gemm_pairs(x.buf.view(-1, cin), w, _lib._pairs_scale_of(pk, w), y.buf.view(-1, cout),
+                        epilogue=_lib.make_epilogue(bias=bias, **ep), act_scale=act_scale)
+        return y
+
+    def _attention(self, pk, x, n, gn, wqk, bqk, wv, bv, wo, bo, cache, key, out_scale=1.0):
+        """One head of self-attention over ``n`` = GroupNorm ``gn`` of ``x``: q|k projection (``wqk`` [2C, C], the two stacked), V^T,
+        softmax(q k^T / sqrt(C)) v, output projection, (+ x) * out_scale.  The V bias is added after P.V (the rows of P sum to one),
+        so V^T is produced directly in the K-contiguous layout that product wants.  ``cache[key]``: the operands' power-of-two
+        scales, kept as long as the weights."""
+        B, HW, C = x.buf.shape[0], x.H * x.W, x.C
+        pairs = self.pairs_admissible(gn, n.norm[1], transform=False)
+        dev = x.buf.device
+        qk = torch.empty(B * HW, 2 * C, device=dev, dtype=torch.float32)
+        _lib.gemm_normed(pk, n.buf.view(-1, C), wqk, qk, epilogue=_lib.make_epilogue(bias=bqk), pairs=pairs)    # n: a GroupNorm's output
+        # V^T[b] = Wv^T-panel [C, Cin] x n[b]^T -> [C, HW], K-contiguous for the P.V product (bias deferred)
+        vt = torch.empty(B, C, HW, device=dev, dtype=torch.float32)
+        _lib.gemm_weight_times_normed_t(pk, wv, n.buf, vt, B, HW, C, pairs=pairs)
+        mixed = torch.empty(B, HW, C, device=dev, dtype=torch.float32)
+        scale = float(C) ** (-0.5)                # BeatGANs: (q * s) . (k * s) with s = ch^-1/4  ==  q . k * ch^-1/2
+        if pairs and _lib.attention256_ok(B, HW, C):
+            # QK^T -> softmax -> PV in one launch, the logits never written (csrc/attention.hip); the operands' power-of-two scales from
+            # the projections' row norms (their input n has unit variance times gamma's scale)
+            if key not in cache:
+                gam = float(torch.sqrt((gn.weight.detach().double() ** 2).mean() + (gn.bias.detach().double() ** 2).mean()))
+                cache[key] = (_lib.pairs_scale_from_rows(wqk, bqk, gam), _lib.pairs_scale_from_rows(wv, bv, gam))
+            s_qk, s_v = cache[key]
+            _lib.attention256(qk, vt, mixed, B, C, s_qk, s_v, scale, bias_v=bv)
+            return self._pointwise_pairs(pk, _T(mixed, x.H, x.W, C), wo, bo, s_v, residual=x.buf, out_scale=out_scale, stats=True)
+        logits = torch.empty(B, HW, HW, device=dev, dtype=torch.float32)
+        _lib.gemm(qk, qk[:, C:], out=logits, M=HW, N=HW, K=C, lda=2 * C, ldb=2 * C, ldc=HW, batch=B,
+                  stride_a=HW * 2 * C, stride_b=HW * 2 * C, stride_c=HW * HW)
+        _lib.softmax_rows(logits, logits, B * HW, HW, scale)
+        _lib.gemm(logits, vt, out=mixed, M=HW, N=C, K=HW, lda=HW, ldb=HW, ldc=C, batch=B,
+                  stride_a=HW * HW, stride_b=C * HW, stride_c=HW * C, epilogue=_lib.make_epilogue(bias=bv))
+        return self._pointwise(_T(mixed, x.H, x.W, C), wo, bo, residual=x.buf, out_scale=out_scale, stats=True)
+
+    def _box(self, x, up):
+        B = x.buf.shape[0]
+        y = self._new(B, x.H * 2 if up else x.H // 2, x.W * 2 if up else x.W // 2, x.C, x.buf)
+        _lib.resample2x_nhwc(x.buf, y.buf, B, x.H, x.W, x.C, up)
+        y.norm = x.norm                                        # nearest x2 / 2x2 mean: never beyond the input's range
+        return y
+
+    def _add(self, a, b, scale):
+        y = self._new(a.buf.shape[0], a.H, a.W, a.C, a.buf)
+        _lib.add_scale(a.buf, b.buf, y.buf, a.buf.numel(), scale)
+        return y
+
+    def _cat(self, a, b):
+        B = a.buf.shape[0]
+        y = self._new(B, a.H, a.W, a.C + b.C, a.buf)
+        _lib.concat_cols(a.buf, a.C, b.buf, b.C, y.buf, B * a.H * a.W)
+        return y

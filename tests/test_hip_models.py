@@ -385,9 +385,9 @@ def test_wide_ncsnpp_golden(golden):
 def wino43_everywhere(monkeypatch):
     """Send every eligible 3x3 convolution of 8x8 maps and larger through the F(4x4, 3x3) kernel, also at test batch sizes (the
     executor keeps launches of fewer than 512 workgroups on the 2x2 form: a speed rule, not a correctness one)."""
-    from id_diff_amd.models import ncsnpp as hip_ncsnpp
-    monkeypatch.setattr(hip_ncsnpp, "WINO43_MIN_WORKGROUPS", 1)
-    monkeypatch.setattr(hip_ncsnpp, "WINO43_PAIRS_MIN_WORKGROUPS", 1)
+    from id_diff_amd.models import nhwc as hip_nhwc
+    monkeypatch.setattr(hip_nhwc, "WINO43_MIN_WORKGROUPS", 1)
+    monkeypatch.setattr(hip_nhwc, "WINO43_PAIRS_MIN_WORKGROUPS", 1)
     calls = {"n": 0, "pairs": 0, "gemm_pairs": 0}
     orig = _lib.conv2d_winograd43
 
@@ -436,8 +436,8 @@ def test_wide_ncsnpp_golden_through_winograd43(golden, wino43_everywhere):
 @pytest.fixture
 def wino1d_everywhere(monkeypatch, wino43_everywhere):
     """... and the GroupNorm-fed 3x3 convolutions of 8 x 8 maps and larger through the row-wise F(4, 3) pair kernel, at test batch sizes."""
-    from id_diff_amd.models import ncsnpp as hip_ncsnpp
-    monkeypatch.setattr(hip_ncsnpp, "WINO1D_MIN_WORKGROUPS", 1)
+    from id_diff_amd.models import nhwc as hip_nhwc
+    monkeypatch.setattr(hip_nhwc, "WINO1D_MIN_WORKGROUPS", 1)
     calls = {"n": 0}
     orig = _lib.conv2d_wino1d
 

@@ -434,8 +434,10 @@ def test_winograd_form_routing():
     fp16-pair F(4x4, 3x3) kernel from one workgroup per CU on, 4x4 maps included; other inputs keep the fp32 contraction and its
     stricter profitability rule; geometries the pair kernel refuses (Cin % 16) fall back; the switch turns the pair form off."""
     from id_diff_amd import _lib
-    from id_diff_amd.models import ncsnpp as hip_ncsnpp
-    pays = hip_ncsnpp._winograd43_pays
+    from id_diff_amd.models import nhwc
+
+    def pays(B, H, W, cin, cout, normed=False):            # either F(4x4, 3x3) entry of the route table serves the layer
+        return any(r.serves(B, H, W, cin, cout, normed, True) for r in nhwc.CONV3X3_ROUTES if r.name.startswith("wino43"))
     assert pays(2240, 32, 32, 128, 128, normed=True) and pays(2240, 32, 32, 128, 128)
     assert pays(2240, 4, 4, 256, 256, normed=True) and not pays(2240, 4, 4, 256, 256)          # 280 workgroups of one-tile samples
     assert pays(128, 16, 16, 256, 256, normed=True) and not pays(127, 16, 16, 256, 128, normed=True)   # 256 workgroups (one per CU) is the threshold
@@ -445,3 +447,74 @@ def test_winograd_form_routing():
     with _lib.thread_option("IDIFF_NO_WINO43H", 1):
         assert not pays(2240, 4, 4, 256, 256, normed=True) and pays(2240, 32, 32, 128, 128, normed=True)
     assert _lib.lib().idiff_winograd43h_weight_floats(128, 256) == 36 * 128 * 256 + 4
+
+
+# the distinct 3x3 convolutions of the headline forward (H, W, Cin, Cout: the shape keys of profiles/r05_wino1d_traffic.json) ...
+_CFG3_CONVS = ((4, 4, 256, 256), (4, 4, 512, 256), (8, 8, 256, 256), (8, 8, 512, 256), (16, 16, 128, 128), (16, 16, 128, 256),
+               (16, 16, 256, 256), (16, 16, 384, 256), (16, 16, 512, 256), (32, 32, 128, 128), (32, 32, 256, 128), (32, 32, 256, 256),
+               (32, 32, 384, 128))
+# ... and the 64-pixel-row layers of the config-5 U-Net: its stem (3 -> 4 padded channels), the two ResBlock shapes, its head
+_CFG5_CONVS = ((64, 64, 4, 128), (64, 64, 128, 128), (64, 64, 256, 128), (64, 64, 128, 3))
+_ALL = lambda name: (name,) * 13
+_FP32_BUT_4X4 = ("wino22",) * 2 + ("wino43_fp32",) * 11          # 4x4 maps stay on F(2x2, 3x3) with the fp32 contraction
+_CFG5 = lambda name: ("igemm", name, name, "igemm")              # 4-channel stem and 3-channel head: no Winograd form serves them
+# (switch, shapes, B, normed, per_image) -> the route of each shape.  Literals: what the chain of `if`s this table replaced
+# (wino1d, then F(4x4, 3x3) on pairs / fp32, then F(2x2, 3x3), else the implicit GEMM) answered for the same inputs.
+_ROUTES = {
+    (None, "cfg3", 2240, True, True): _ALL("wino1d"),
+    (None, "cfg3", 2240, False, True): _FP32_BUT_4X4,
+    (None, "cfg3", 2240, True, False): _ALL("wino22"),              # row groups that are not whole images: only F(2x2, 3x3)
+    (None, "cfg3", 2240, False, False): _ALL("wino22"),
+    (None, "cfg3", 2, True, True): _ALL("wino22"),
+    (None, "cfg3", 2, False, True): _ALL("wino22"),
+    (None, "cfg5", 128, True, True): _CFG5("wino1d"),
+    (None, "cfg5", 128, False, True): _CFG5("wino43_fp32"),
+    (None, "cfg5", 128, True, False): _CFG5("wino22"),
+    (None, "cfg5", 2, True, True): _CFG5("wino22"),
+    (None, "cfg5", 2, False, True): _CFG5("wino22"),
+    ("IDIFF_NO_WINO1D", "cfg3", 2240, True, True): _ALL("wino43_pairs"),
+    ("IDIFF_NO_WINO1D", "cfg3", 2240, False, True): _FP32_BUT_4X4,
+    ("IDIFF_NO_WINO1D", "cfg3", 2, True, True): _ALL("wino22"),
+    ("IDIFF_NO_WINO1D", "cfg3", 2, False, True): _ALL("wino22"),
+    ("IDIFF_NO_WINO1D", "cfg5", 128, True, True): _CFG5("wino43_pairs"),
+    ("IDIFF_NO_WINO1D", "cfg5", 128, False, True): _CFG5("wino43_fp32"),
+    ("IDIFF_NO_WINO1D", "cfg5", 2, True, True): _CFG5("wino22"),
+    ("IDIFF_NO_WINO43H", "cfg3", 2240, True, True): _FP32_BUT_4X4,
+    ("IDIFF_NO_WINO43H", "cfg3", 2240, False, True): _FP32_BUT_4X4,
+    ("IDIFF_NO_WINO43H", "cfg3", 2, True, True): _ALL("wino22"),
+    ("IDIFF_NO_WINO43H", "cfg3", 2, False, True): _ALL("wino22"),
+    ("IDIFF_NO_WINO43H", "cfg5", 128, True, True): _CFG5("wino43_fp32"),
+    ("IDIFF_NO_WINO43H", "cfg5", 128, False, True): _CFG5("wino43_fp32"),
+    ("IDIFF_NO_WINO43H", "cfg5", 2, True, True): _CFG5("wino22"),
+    ("IDIFF_NO_WINO43", "cfg3", 2240, True, True): _ALL("wino1d"),  # the switch leaves the row-wise pair kernel on
+    ("IDIFF_NO_WINO43", "cfg3", 2240, False, True): _ALL("wino22"),
+    ("IDIFF_NO_WINO43", "cfg3", 2, True, True): _ALL("wino22"),
+    ("IDIFF_NO_WINO43", "cfg3", 2, False, True): _ALL("wino22"),
+    ("IDIFF_NO_WINO43", "cfg5", 128, True, True): _CFG5("wino1d"),
+    ("IDIFF_NO_WINO43", "cfg5", 128, False, True): _CFG5("wino22"),
+    ("IDIFF_NO_WINO43", "cfg5", 2, True, True): _CFG5("wino22"),
+    ("IDIFF_NO_WINOGRAD", "cfg3", 2240, True, True): _ALL("igemm"),
+    ("IDIFF_NO_WINOGRAD", "cfg3", 2240, False, True): _ALL("igemm"),
+    ("IDIFF_NO_WINOGRAD", "cfg3", 2, True, True): _ALL("igemm"),
+    ("IDIFF_NO_WINOGRAD", "cfg3", 2, False, True): _ALL("igemm"),
+    ("IDIFF_NO_WINOGRAD", "cfg5", 128, True, True): _CFG5("igemm"),
+    ("IDIFF_NO_WINOGRAD", "cfg5", 128, False, True): _CFG5("igemm"),
+    ("IDIFF_NO_WINOGRAD", "cfg5", 2, True, True): _CFG5("igemm"),
+}
+
+
+@pytest.mark.parametrize("switch,net,B,normed,per_image", list(_ROUTES), ids=lambda v: str(v))
+def test_conv3x3_route_table(switch, net, B, normed, per_image):
+    """Which kernel serves each 3x3 convolution of the headline forward (launch set B = 2240), of a test-sized batch and of config 5's
+    64-pixel rows, GroupNorm-fed or not, by default and under each routing switch: the rule is host logic over the library's geometry
+    predicates, so it is pinned here without a GPU (the launch counters of the GPU suite see whole networks only)."""
+    import contextlib
+    import os
+    from id_diff_amd import _lib
+    from id_diff_amd.models import nhwc
+    if not os.path.exists(_lib.library_path()):
+        pytest.skip("libidiff_hip.so is not built")
+    shapes = _CFG3_CONVS if net == "cfg3" else _CFG5_CONVS
+    with _lib.thread_option(switch, 1) if switch else contextlib.nullcontext():
+        got = tuple(getattr(nhwc.conv3x3_route(B, *s, normed, per_image), "name", "igemm") for s in shapes)
+    assert got == _ROUTES[(switch, net, B, normed, per_image)]
