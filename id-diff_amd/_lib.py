@@ -74,6 +74,8 @@ _SIGNATURES = {
     "idiff_wino1d_weight_floats": (c_i64, [c_i, c_i]),
     "idiff_wino1d_pack_f32": (c_i, [c_p, c_p, c_i, c_i, c_p]),
     "idiff_conv2d_wino1d_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(Epilogue), c_p]),
+    "idiff_conv2d_wino1d_gn_ok": (c_i, [c_i] * 6),
+    "idiff_conv2d_wino1d_gn_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(Epilogue), c_i, c_p, c_p, c_f, c_i, c_p]),
     "idiff_conv2d_winograd_split_ok": (c_i, [c_i] * 5),
     "idiff_winograd_split_weight_floats": (c_i64, [c_i, c_i]),
     "idiff_winograd_pack_split_f32": (c_i, [c_p, c_p, c_i, c_i, c_p]),
@@ -244,6 +246,24 @@ def make_epilogue(bias=None, rowbias=None, rows_per_group=1, act=None, residual=
     return ep
 
 
+def with_groupnorm(ep, groups, gamma, beta, eps, act):
+    """Ask the contraction that consumes ``ep`` to apply the GroupNorm (``groups`` groups, ``gamma`` / ``beta`` [N], ``eps``) and the
+    activation that read its output in its own tail.  The request rides BESIDE the C struct (idiff_epilogue is shared by every
+    contraction and does not know it): conv2d_wino1d serves it through idiff_conv2d_wino1d_gn_f32, every other wrapper refuses it."""
+    _dev(gamma, "gamma"); _dev(beta, "beta")
+    ep.groupnorm = (int(groups), gamma, beta, float(eps), ACT[act])
+    return ep
+
+
+def _ep_ref(epilogue, what):
+    """The epilogue argument of a launch that has no fused GroupNorm: such a request is an error, never dropped."""
+    if epilogue is None:
+        return None
+    if getattr(epilogue, "groupnorm", None) is not None:
+        raise RuntimeError(f"{what}: the epilogue asks for a fused GroupNorm (with_groupnorm), which only conv2d_wino1d serves")
+    return ctypes.byref(epilogue)
+
+
 # ------------------------------------------------------------------------------------------- native ops
 # the dtypes of the reference's native-op dispatch (AT_DISPATCH_FLOATING_TYPES_AND_HALF) -> entry-point suffix
 OP_DTYPES = {torch.float32: "f32", torch.float16: "f16", torch.float64: "f64"}
@@ -323,7 +343,7 @@ def gemm(a, bt, out=None, epilogue=None, M=None, N=None, K=None, lda=None, ldb=N
     elif ldc is None:
         ldc = out.stride(-2)
     _dev(out, "out", contiguous=not explicit)
-    ep = ctypes.byref(epilogue) if epilogue is not None else None
+    ep = _ep_ref(epilogue, "gemm")
     _check(lib().idiff_gemm_f32(a.data_ptr(), lda, stride_a, bt.data_ptr(), ldb, stride_b, out.data_ptr(), ldc, stride_c,
                                 M, N, K, batch, ep, _stream()), "idiff_gemm_f32")
     return out
@@ -357,7 +377,7 @@ def gemm_pairs(a, bt, w_scale, out, epilogue=None, weight_is_a=False, M=None, N=
         if bt.shape[1] != K or out.shape[0] != M or out.shape[1] != N:
             raise RuntimeError(f"gemm_pairs: shapes {tuple(a.shape)} x {tuple(bt.shape)}^T -> {tuple(out.shape)}")
         lda, ldb, ldc = a.stride(0), bt.stride(0), out.stride(0)
-    ep = ctypes.byref(epilogue) if epilogue is not None else None
+    ep = _ep_ref(epilogue, "gemm_pairs")
     _check(lib().idiff_gemm_pairs_f32(a.data_ptr(), lda, stride_a, bt.data_ptr(), ldb, stride_b, w_scale.data_ptr(), int(bool(weight_is_a)),
                                       _ptr(act_scale), out.data_ptr(), ldc, stride_c, M, N, K, batch, ep, _stream()), "idiff_gemm_pairs_f32")
     return out
@@ -381,7 +401,7 @@ def gemm_pairs_2src(a1, a2, act_scale, bt, w_scale, out, epilogue=None):
     K = K1 + a2.shape[1]
     if a2.shape[0] != M or a1.stride(0) != a2.stride(0) or bt.shape[1] != K:
         raise RuntimeError(f"gemm_pairs_2src: shapes {tuple(a1.shape)} | {tuple(a2.shape)} x {tuple(bt.shape)}^T")
-    ep = ctypes.byref(epilogue) if epilogue is not None else None
+    ep = _ep_ref(epilogue, "gemm_pairs_2src")
     _check(lib().idiff_gemm_pairs_2src_f32(a1.data_ptr(), a2.data_ptr(), a1.stride(0), K1, act_scale.data_ptr(), bt.data_ptr(), bt.stride(0),
                                            w_scale.data_ptr(), out.data_ptr(), out.stride(0), M, bt.shape[0], K, ep, _stream()),
            "idiff_gemm_pairs_2src_f32")
@@ -420,14 +440,14 @@ def gemm_2src(a1, a2, bt, out, epilogue=None):
     K = K1 + a2.shape[1]
     if a2.shape[0] != M or a1.stride(0) != a2.stride(0) or bt.shape[1] != K:
         raise RuntimeError(f"gemm_2src: shapes {tuple(a1.shape)} | {tuple(a2.shape)} x {tuple(bt.shape)}^T")
-    ep = ctypes.byref(epilogue) if epilogue is not None else None
+    ep = _ep_ref(epilogue, "gemm_2src")
     _check(lib().idiff_gemm_2src_f32(a1.data_ptr(), a2.data_ptr(), a1.stride(0), K1, bt.data_ptr(), bt.stride(0), out.data_ptr(),
                                      out.stride(0), M, bt.shape[0], K, ep, _stream()), "idiff_gemm_2src_f32")
     return out
 
 
 def conv2d_nhwc(x, wt, out, B, H, W, Cin, Cout, KH, KW, stride, pad, epilogue=None, pad_hi=None):
-    ep = ctypes.byref(epilogue) if epilogue is not None else None
+    ep = _ep_ref(epilogue, "conv2d_nhwc")
     _check(lib().idiff_conv2d_nhwc_f32(x.data_ptr(), wt.data_ptr(), out.data_ptr(), B, H, W, Cin, Cout, KH, KW, stride,
                                        pad, pad if pad_hi is None else pad_hi, ep, _stream()), "idiff_conv2d_nhwc_f32")
     return out
@@ -453,7 +473,15 @@ def _wino_conv(stem, packed_by, x, u, out, B, H, W, Cin, Cout, epilogue):
     want = getattr(lib(), f"idiff_{stem}_weight_floats")(Cin, Cout)
     if u.numel() != want:
         raise RuntimeError(f"conv2d_{stem}: a filter bank of {u.numel()} floats ({want} expected): pack it with {packed_by}")
-    ep = ctypes.byref(epilogue) if epilogue is not None else None
+    gn = getattr(epilogue, "groupnorm", None)
+    if gn is not None and stem == "wino1d":
+        groups, gamma, beta, eps, act = gn
+        if gamma.numel() != Cout or beta.numel() != Cout:
+            raise RuntimeError(f"conv2d_wino1d: fused GroupNorm with {gamma.numel()} / {beta.numel()} gamma / beta entries for {Cout} channels")
+        _check(lib().idiff_conv2d_wino1d_gn_f32(x.data_ptr(), u.data_ptr(), out.data_ptr(), B, H, W, Cin, Cout, ctypes.byref(epilogue), groups,
+                                                gamma.data_ptr(), beta.data_ptr(), eps, act, _stream()), "idiff_conv2d_wino1d_gn_f32")
+        return out
+    ep = _ep_ref(epilogue, f"conv2d_{stem}")
     entry = f"idiff_conv2d_{stem}_f32"
     _check(getattr(lib(), entry)(x.data_ptr(), u.data_ptr(), out.data_ptr(), B, H, W, Cin, Cout, ep, _stream()), entry)
     return out
@@ -520,12 +548,19 @@ def conv2d_wino1d_colstats_split(B, H, W, Cin, Cout):
     return lib().idiff_conv2d_wino1d_colstats_split(B, H, W, Cin, Cout)
 
 
+def conv2d_wino1d_gn_ok(B, H, W, Cin, Cout, groups):
+    """True when conv2d_wino1d also applies the GroupNorm (``groups`` groups) + activation behind it (with_groupnorm): maps of at most 256
+    pixels in rows of at most 16, group widths that divide 64; off under IDIFF_NO_FUSED_GN and wherever conv2d_wino1d_ok is."""
+    return bool(lib().idiff_conv2d_wino1d_gn_ok(B, H, W, Cin, Cout, groups))
+
+
 def wino1d_pack(wt, Cin, Cout):
     """The filter bank of idiff_conv2d_wino1d_f32 (scaled fp16 pairs of (G g[ky])[i], 18 * Cin * Cout + 4 floats)."""
     return _wino_pack("wino1d", "wino1d_pack", wt, Cin, Cout)
 
 
 def conv2d_wino1d(x, u, out, B, H, W, Cin, Cout, epilogue=None):
+    """``epilogue`` may carry a GroupNorm request (with_groupnorm): the launch then stores act(GroupNorm(conv + bias + rowbias))."""
     return _wino_conv("wino1d", "wino1d_pack", x, u, out, B, H, W, Cin, Cout, epilogue)
 
 

@@ -117,15 +117,18 @@ struct Wino1dParams {
   uint32_t x_bytes, u_bytes, out_bytes, res_bytes;
   idiff_epilogue ep;
   int has_ep;
+  const float *gn_gamma, *gn_beta;                 // the fused GroupNorm of wino1d_gn_kernel: [Cout] each, groups of gn_cpg channels
+  int gn_cpg, gn_act;
+  float gn_eps;
   float c_nb2, c_na2, c_nab2, c_a, c_b;            // the transform's constants as kernel arguments (SGPR operands of plain fmas)
 #ifdef IDIFF_W1D_STAMP
   uint64_t *stamps;                                // diagnostic build (scripts/wino1d_stamps.py): 8 ticks of 100 MHz per workgroup
 #endif
 };
 
-template <int W>
-__global__ void __launch_bounds__(R1_THREADS)
-wino1d_kernel(const Wino1dParams p) {
+// GN: the tail of wino1d_gn_kernel (GroupNorm + activation of the output inside the workgroup) instead of the epilogue's switches
+template <int W, bool GN>
+__device__ __forceinline__ void r1_body(const Wino1dParams &p) {
   using G = R1Geo<W>;
   constexpr int TPR = G::TPR, RB = G::RB, POS = G::POS_BYTES, BRING = R1_BRING;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -473,6 +476,132 @@ wino1d_kernel(const Wino1dParams p) {
   const int ld_res = (int)ep.ld_residual;
   float4 bias4 = make_float4(0.f, 0.f, 0.f, 0.f);
   if (has_ep && ep.bias) bias4 = *reinterpret_cast<const float4 *>(ep.bias + n);
+  // (the last step ended with a barrier: nobody reads the stages any more)
+  if constexpr (GN) {
+    // The fused GroupNorm (GN): a round is 256 consecutive pixels = whole images (H W divides 256, checked by the launcher) and the tile's 64
+    // channels are whole groups, so every (image, group) the norm needs is inside this round of this workgroup.  The thread keeps its 16 pixels
+    // x 4 channels of descale * A^T m + bias + rowbias in registers (the residual's 64 are free: no residual here), and the sets are reduced
+    // twice -- the sum for the mean, then the sum of squares about that mean over the same registers (no cancellation whatever the channels'
+    // offset), both in fp64 as the column sums are: the thread's 16 pixels; the group's channels in neighbouring lanes (cq = lane & 15); the
+    // image's thread rows tl = 4 wave + (lane >> 4): two lane exchanges inside the wave, and for images of 128 / 256 pixels (two / four waves)
+    // one exchange through the LDS the parked accumulators leave free.  Every lane of a set adds the same values in the same order, so all
+    // of them normalise with the same bits.  Then y = act((v - mean) * (rstd * gamma) + beta), gn_apply_rows_kernel's expression, and the
+    // same 16-byte stores.  Samples beyond B in a partial last block are computed on zeros and their stores dropped (ooff: R1_INVALID).
+    const int gn_cpg = p.gn_cpg;
+    const int gn_span = (p.H * W) >> 4;                               // thread rows per image: 1, 2, 4 (one wave), 8, 16
+    double *const gn_red = reinterpret_cast<double *>(ldsb + 6 * R1_RT / 2 * R1_COUT * 4);        // behind a round's parked accumulators (98,304 B)
+    static_assert(6 * R1_RT / 2 * R1_COUT * 4 + 2 * 4 * 16 * 4 * 8 <= R1_Z_BYTES, "the statistics' exchange inside the allocation");
+    // t[0 .. N - 1] summed over the lanes of my (image, group); N = 1: one group per thread (gn_cpg >= 4), N = 4: a value per channel (gn_cpg 1, 2)
+    auto gn_reduce = [&](auto n_c, double *t, int pass) __attribute__((always_inline)) {
+      constexpr int N = decltype(n_c)::value;
+      if (N == 1) { for (int o = 1; o < (gn_cpg >> 2); o <<= 1) t[0] += __shfl_xor(t[0], o, 64); }
+      else if (gn_cpg == 2) { t[0] += t[1]; t[1] = t[0]; t[2] += t[3]; t[3] = t[2]; }
+      if (gn_span >= 2) {
+#pragma unroll
+        for (int e = 0; e < N; ++e) t[e] += __shfl_xor(t[e], 16, 64);
+      }
+      if (gn_span >= 4) {
+#pragma unroll
+        for (int e = 0; e < N; ++e) t[e] += __shfl_xor(t[e], 32, 64);
+      }
+      if (gn_span >= 8) {                                              // (uniform over the workgroup: H is a kernel argument)
+        double *area = gn_red + pass * (4 * 16 * 4);                   // one area per pass: the next pass writes while this one is still read
+        if (lane < 16) {
+#pragma unroll
+          for (int e = 0; e < N; ++e) area[(wave * 16 + lane) * 4 + e] = t[e];
+        }
+        __syncthreads();
+        const int nw = gn_span >> 2, w0 = wave & ~(nw - 1);            // the image's waves
+#pragma unroll
+        for (int e = 0; e < N; ++e) {
+          double a = area[(w0 * 16 + cq) * 4 + e];
+          for (int k = 1; k < nw; ++k) a += area[((w0 + k) * 16 + cq) * 4 + e];
+          t[e] = a;
+        }
+      }
+    };
+    auto finish_gn = [&](auto round_c, auto act_c, auto n_c) __attribute__((always_inline)) {
+      constexpr int RND = decltype(round_c)::value, ACT = decltype(act_c)::value, N = decltype(n_c)::value;
+      const uint32_t pxl = (uint32_t)(4 * (64 * RND + 4 * tl));
+      const int orow = row0 + (int)(pxl / W);
+      const bool ook = orow < p.rows_total;
+      const uint32_t px0 = (uint32_t)row0 * (uint32_t)W + pxl;
+      const uint32_t ooff = ook ? (px0 * (uint32_t)p.Cout + (uint32_t)n) * 4u : R1_INVALID;
+      float4 badd = bias4;
+      if (has_ep && ook && ep.rowbias) {
+        const float4 rb = *reinterpret_cast<const float4 *>(ep.rowbias + (int64_t)(orow / p.H) * ep.ld_rowbias + n);
+        badd.x += rb.x; badd.y += rb.y; badd.z += rb.z; badd.w += rb.w;
+      }
+      float v[16][4];
+      double s[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float *zr = lds + (size_t)(4 * tl + j) * 6 * R1_COUT + 4 * cq;
+        float4 z[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) z[i] = *reinterpret_cast<const float4 *>(zr + i * R1_COUT);
+#define IDIFF_R1_AT(cmp, e, b)                                                                               \
+        {                                                                                                      \
+          const float s12 = z[1].cmp + z[2].cmp, d12 = z[1].cmp - z[2].cmp, s34 = z[3].cmp + z[4].cmp, d34 = z[3].cmp - z[4].cmp; \
+          v[4 * j + 0][e] = fmaf(z[0].cmp + (s12 + s34), descale, b);                                           \
+          v[4 * j + 1][e] = fmaf(fmaf(R1_b, d34, R1_a * d12), descale, b);                                      \
+          v[4 * j + 2][e] = fmaf(fmaf(R1_b2, s34, R1_a2 * s12), descale, b);                                    \
+          v[4 * j + 3][e] = fmaf(fmaf(R1_b3, d34, fmaf(R1_a3, d12, z[5].cmp)), descale, b);                     \
+        }
+        IDIFF_R1_AT(x, 0, badd.x) IDIFF_R1_AT(y, 1, badd.y) IDIFF_R1_AT(z, 2, badd.z) IDIFF_R1_AT(w, 3, badd.w)
+#undef IDIFF_R1_AT
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) s[e] += (double)v[4 * j + a][e];
+      }
+      const double inv_n = 1.0 / (double)(gn_cpg * p.H * W);
+      double mean[4], q[4] = {0.0, 0.0, 0.0, 0.0};
+      if (N == 1) s[0] = (s[0] + s[1]) + (s[2] + s[3]);
+      gn_reduce(n_c, s, 0);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) mean[e] = s[e < N ? e : 0] * inv_n;
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { const double d = (double)v[i][e] - mean[e]; q[e] = fma(d, d, q[e]); }
+      if (N == 1) q[0] = (q[0] + q[1]) + (q[2] + q[3]);
+      gn_reduce(n_c, q, 1);
+      const float4 ga = *reinterpret_cast<const float4 *>(p.gn_gamma + n), be = *reinterpret_cast<const float4 *>(p.gn_beta + n);
+      const float gam[4] = {ga.x, ga.y, ga.z, ga.w}, bet[4] = {be.x, be.y, be.z, be.w};
+      float mu[4], sc[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (e < N) sc[e] = (float)(1.0 / sqrt(q[e] * inv_n + (double)p.gn_eps)); else sc[e] = sc[0];
+        mu[e] = (float)mean[e];
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) sc[e] *= gam[e];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        float y[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) y[e] = idiff::act_apply((v[i][e] - mu[e]) * sc[e] + bet[e], ACT < 0 ? p.gn_act : ACT);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uintx4, make_float4(y[0], y[1], y[2], y[3])), rO, (int)ooff, i * p.Cout * 4,
+                                               IDIFF_W1D_STORE_AUX);
+      }
+    };
+    auto finish_gn_round = [&](auto round_c) __attribute__((always_inline)) {
+      using ASilu = std::integral_constant<int, (int)IDIFF_ACT_SILU>; using AAny = std::integral_constant<int, -1>;
+      using N1 = std::integral_constant<int, 1>; using N4 = std::integral_constant<int, 4>;
+      auto by_n = [&](auto a) __attribute__((always_inline)) { if (gn_cpg >= 4) finish_gn(round_c, a, N1()); else finish_gn(round_c, a, N4()); };
+      if (p.gn_act == (int)IDIFF_ACT_SILU) by_n(ASilu()); else by_n(AAny());
+    };
+    park(I0()); park(I1());
+    __syncthreads();
+    IDIFF_W1D_T(4)
+    finish_gn_round(I0());
+    __syncthreads();
+    park(I2()); park(I3());
+    __syncthreads();
+    finish_gn_round(I1());
+    IDIFF_W1D_T(5)
+  } else {   // the plain kernel's tail, as it was (not indented: the lines are the ones wino1d_kernel always had)
   // the residual's 16 pixels of a round are requested one phase ahead (round 0: before the first park, round 1: behind round 0's outputs) and
   // arrive behind the parks and barriers
   float4 res[16];
@@ -556,7 +685,6 @@ wino1d_kernel(const Wino1dParams p) {
     auto by_res = [&](auto a) __attribute__((always_inline)) { if (has_res) by_scale(a, T()); else by_scale(a, F()); };
     if (act == (int)IDIFF_ACT_NONE) by_res(ANone()); else by_res(AAny());
   };
-  // the last step ended with a barrier: nobody reads the stages any more
   if (has_res) request_res(0);
   park(I0()); park(I1());
   __syncthreads();
@@ -593,6 +721,7 @@ wino1d_kernel(const Wino1dParams p) {
       dst[0] = a; dst[1] = b;
     }
   }
+  }
 #ifdef IDIFF_W1D_STAMP
   IDIFF_W1D_T(6)
   if (tid == 0 && p.stamps) {
@@ -603,6 +732,15 @@ wino1d_kernel(const Wino1dParams p) {
 #endif
 #undef IDIFF_W1D_T
 }
+
+template <int W>
+__global__ void __launch_bounds__(R1_THREADS)
+wino1d_kernel(const Wino1dParams p) { r1_body<W, false>(p); }
+
+// the same convolution with the GroupNorm (+ activation) that reads its output applied in the tail: maps of at most 256 pixels
+template <int W>
+__global__ void __launch_bounds__(R1_THREADS)
+wino1d_gn_kernel(const Wino1dParams p) { r1_body<W, true>(p); }
 
 // U[i][ky] = sum_kx G[i][kx] g[ky][kx] in fp64 for one (cin, cout) pair
 __device__ __forceinline__ void r1_u_of_pair(const float *wt, int Cin, int cin, int cout, double (&U)[18]) {
@@ -673,6 +811,23 @@ int r1_launch(const Wino1dParams &p, hipStream_t stream) {
   hipLaunchKernelGGL(wino1d_kernel<W>, dim3(p.blocks_m * p.tiles_n), dim3(R1_THREADS), R1_LDS_BYTES, stream, p);
   return idiff::launch_status("conv2d_wino1d");
 }
+
+template <int W>
+int r1_launch_gn(const Wino1dParams &p, hipStream_t stream) {
+  static idiff::AttrGuard guard;
+  const void *fn = reinterpret_cast<const void *>(wino1d_gn_kernel<W>);
+  if (int rc = idiff::set_dynamic_lds_once(guard, &fn, 1, (int)R1_LDS_BYTES, "conv2d_wino1d_gn")) return rc;
+  hipLaunchKernelGGL(wino1d_gn_kernel<W>, dim3(p.blocks_m * p.tiles_n), dim3(R1_THREADS), R1_LDS_BYTES, stream, p);
+  return idiff::launch_status("conv2d_wino1d_gn");
+}
+
+// the fused GroupNorm's own conditions (the convolution's: r1_geometry_ok): a tail round of 256 pixels holds whole images, a tile of 64
+// channels whole groups; the kernel is built for the rows of 4, 8 and 16 pixels such maps have in the networks
+bool r1_gn_geometry_ok(int H, int W, int Cout, int groups) {
+  if (W > 16 || H * W > 256 || 256 % (H * W)) return false;
+  if (groups <= 0 || Cout % groups) return false;
+  return R1_COUT % (Cout / groups) == 0;
+}
 }  // namespace
 
 IDIFF_API int idiff_conv2d_wino1d_ok(int B, int H, int W, int Cin, int Cout) {
@@ -707,8 +862,12 @@ IDIFF_API int idiff_wino1d_pack_f32(const float *wt, float *u, int Cin, int Cout
   return launch_status("wino1d_pack");
 }
 
-IDIFF_API int idiff_conv2d_wino1d_f32(const float *x, const float *u, float *out, int B, int H, int W, int Cin, int Cout,
-                                      const idiff_epilogue *ep, void *stream) {
+namespace {
+struct R1GroupNorm { int groups; const float *gamma, *beta; float eps; int act; };
+
+// both entry points: gn == nullptr is idiff_conv2d_wino1d_f32
+int r1_run(const float *x, const float *u, float *out, int B, int H, int W, int Cin, int Cout, const idiff_epilogue *ep, const R1GroupNorm *gn,
+           void *stream) {
   using namespace idiff;
   if (B == 0) return 0;
   if (!r1_geometry_ok(B, H, W, Cin, Cout))
@@ -721,6 +880,21 @@ IDIFF_API int idiff_conv2d_wino1d_f32(const float *x, const float *u, float *out
     return fail("conv2d_wino1d: per-row-group bias / scale only per image (rows_per_group = H * W = %d, got %d)", H * W, ep->rows_per_group);
   if (ep && ep->residual && (((uintptr_t)ep->residual & 15) || ep->ld_residual % 4 || ep->ld_residual < Cout || ep->ld_residual > 0x7fffffff / 4))
     return fail("conv2d_wino1d: residual must be 16-byte aligned with a row pitch >= Cout that is a multiple of 4");
+  if (gn) {
+    // nothing is launched unless the tail can finish every (image, group) inside one round of one workgroup and store act(GN(.)) alone
+    if (!r1_gn_geometry_ok(H, W, Cout, gn->groups))
+      return fail("conv2d_wino1d_gn: H * W = %d must divide 256 (rows of at most 16 pixels) and Cout / groups = %d / %d must divide 64 "
+                  "(ask idiff_conv2d_wino1d_gn_ok)", H * W, Cout, gn->groups);
+    if (!gn->gamma || !gn->beta || (((uintptr_t)gn->gamma | (uintptr_t)gn->beta) & 15))
+      return fail("conv2d_wino1d_gn: gamma and beta are required, 16-byte aligned");
+    if (gn->act < IDIFF_ACT_NONE || gn->act > IDIFF_ACT_LRELU) return fail("conv2d_wino1d_gn: unknown activation code %d", gn->act);
+    if (ep && ep->residual) return fail("conv2d_wino1d_gn: a residual cannot be combined with the fused GroupNorm (its registers hold the image)");
+    if (ep && ep->colstats) return fail("conv2d_wino1d_gn: colstats together with the fused GroupNorm: the convolution's own output is never stored");
+    if (ep && (ep->act != IDIFF_ACT_NONE || ep->out_scale != 1.f || ep->rowscale))
+      return fail("conv2d_wino1d_gn: the epilogue in front of the fused GroupNorm is bias + per-image bias only (no activation, no scale)");
+    if (ep && ep->rows_per_group != H * W)
+      return fail("conv2d_wino1d_gn: rows_per_group must be H * W = %d (got %d)", H * W, ep->rows_per_group);
+  }
   const int64_t res_bytes = (ep && ep->residual) ? (int64_t)B * H * W * ep->ld_residual * 4 : 0;
   if (res_bytes >= R1_X_LIMIT) return fail("conv2d_wino1d: residual beyond one buffer descriptor");
   Wino1dParams p = {};
@@ -745,6 +919,14 @@ IDIFF_API int idiff_conv2d_wino1d_f32(const float *x, const float *u, float *out
 #ifdef IDIFF_W1D_STAMP
   { const char *e = getenv("IDIFF_W1D_STAMP_PTR"); p.stamps = e ? reinterpret_cast<uint64_t *>(strtoull(e, nullptr, 0)) : nullptr; }
 #endif
+  if (gn) {
+    p.gn_gamma = gn->gamma; p.gn_beta = gn->beta; p.gn_cpg = Cout / gn->groups; p.gn_act = gn->act; p.gn_eps = gn->eps;
+    switch (W) {
+      case 4: return r1_launch_gn<4>(p, (hipStream_t)stream);
+      case 8: return r1_launch_gn<8>(p, (hipStream_t)stream);
+      default: return r1_launch_gn<16>(p, (hipStream_t)stream);       // (r1_gn_geometry_ok: W <= 16)
+    }
+  }
   switch (W) {
     case 4: return r1_launch<4>(p, (hipStream_t)stream);
     case 8: return r1_launch<8>(p, (hipStream_t)stream);
@@ -752,4 +934,22 @@ IDIFF_API int idiff_conv2d_wino1d_f32(const float *x, const float *u, float *out
     case 64: return r1_launch<64>(p, (hipStream_t)stream);
     default: return r1_launch<32>(p, (hipStream_t)stream);
   }
+}
+}  // namespace
+
+IDIFF_API int idiff_conv2d_wino1d_f32(const float *x, const float *u, float *out, int B, int H, int W, int Cin, int Cout,
+                                      const idiff_epilogue *ep, void *stream) {
+  return r1_run(x, u, out, B, H, W, Cin, Cout, ep, nullptr, stream);
+}
+
+IDIFF_API int idiff_conv2d_wino1d_gn_ok(int B, int H, int W, int Cin, int Cout, int groups) {
+  if (!idiff_conv2d_wino1d_ok(B, H, W, Cin, Cout) || idiff::option(idiff::OPT_NO_FUSED_GN)) return 0;
+  return r1_gn_geometry_ok(H, W, Cout, groups) ? 1 : 0;
+}
+
+IDIFF_API int idiff_conv2d_wino1d_gn_f32(const float *x, const float *u, float *out, int B, int H, int W, int Cin, int Cout,
+                                         const idiff_epilogue *ep, int groups, const float *gamma, const float *beta, float eps, int act,
+                                         void *stream) {
+  const R1GroupNorm gn = {groups, gamma, beta, eps, act};
+  return r1_run(x, u, out, B, H, W, Cin, Cout, ep, &gn, stream);
 }

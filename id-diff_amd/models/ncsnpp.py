@@ -342,8 +342,7 @@ class NCSNpp(NhwcExecutor):
                 h, x = self._box(h, mod.up), self._box(x, mod.up)
         w0, b0 = self._conv_w(pk, (idx, 0), mod.Conv_0)
         off = pk["dense_off"][idx]
-        h = self._conv(h, w0, b0, rowbias=temb_all[:, off:off + mod.out_ch], stats=True, normed=True)
-        h = self._gn_act(h, mod.GroupNorm_1, self.act_name)
+        h = self._conv_gn_act(h, w0, b0, mod.GroupNorm_1, self.act_name, rowbias=temb_all[:, off:off + mod.out_ch], normed=True)
         # shortcut
         if hasattr(mod, "Conv_2") or hasattr(mod, "NIN_0"):
             # cat[x, x2] with equal row pitch: one two-source contraction; otherwise two K-slices through the residual epilogue

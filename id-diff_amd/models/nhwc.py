@@ -169,8 +169,11 @@ class NhwcExecutor(HipScoreModel):
         y.norm = norm
         return y
 
-    def _conv(self, x, wt, bias, stride=1, pad=1, pad_hi=None, stats=False, normed=False, **ep):
+    def _conv(self, x, wt, bias, stride=1, pad=1, pad_hi=None, stats=False, normed=False, fuse_gn=None, **ep):
         """``stats=True``: the output feeds a GroupNorm -> ask the epilogue for its per-tile column sums.
+        ``fuse_gn=(gn, act)`` (instead of ``stats``; _conv_gn_act's argument): that GroupNorm is unmodulated and reads nothing else.
+        Returns ``(y, fused)``: where the row-wise kernel applies the norm in its own tail, ``y`` is the GroupNorm's output (``norm``
+        set, no ``stats``) and ``fused`` is True; otherwise ``y`` is the convolution's output with its column sums.
         ``normed=True``: the input is the output of a GroupNorm (+ activation, + FIR resampling), i.e. bounded by
         sqrt(group size) * |gamma| + |beta| -- only then may the Winograd contraction run on fp16 pairs, whose transformed input
         must stay below 65504 (include/idiff_hip.h), and only if THIS checkpoint's gamma / beta keep that bound inside the range
@@ -193,20 +196,39 @@ class NhwcExecutor(HipScoreModel):
         if (kh, kw, stride, pad, ph) == (3, 3, 1, 1, 1):
             route = conv3x3_route(*geom, normed, ep["rows_per_group"] == OH * OW)
         if route is None:
-            if stats:
+            if stats or fuse_gn is not None:
                 self._colstats(y, _lib.conv2d_colstats_split(*geom, kh, kw, stride, pad, pad_hi), ep)
             _lib.conv2d_nhwc(x.buf, wt, y.buf, *geom, kh, kw, stride, pad, epilogue=_lib.make_epilogue(bias=bias, **ep), pad_hi=pad_hi)
-            return y
+            return (y, False) if fuse_gn is not None else y
         # the transformed filter bank is cached beside the panel; the entry keeps `wt` so that its id cannot be reused while it lives
         form = route.form(*geom)
         bank = self._packed.setdefault(route.bank, {})
         key = (id(wt), *form.values()) if form else id(wt)
         if key not in bank:
             bank[key] = (wt, getattr(_lib, route.pack)(wt, cin, cout, **form))
-        if stats:
+        # the fused tail takes bias and the per-image bias only: an activation or a scale in front of the norm stays two launches
+        if (fuse_gn is not None and route.name == "wino1d" and _lib.conv2d_wino1d_gn_ok(*geom, fuse_gn[0].num_groups)
+                and not (set(ep) - {"rowbias", "ld_rowbias", "rows_per_group"})):
+            gn, act = fuse_gn
+            epilogue = _lib.with_groupnorm(_lib.make_epilogue(bias=bias, **ep), gn.num_groups, gn.weight.detach(), gn.bias.detach(), gn.eps, act)
+            getattr(_lib, route.launch)(x.buf, bank[key][1], y.buf, *geom, epilogue=epilogue, **form)
+            y.norm = (gn, (cout // gn.num_groups) * OH * OW, 1.0, False)     # what _gn_act sets: the consumer may run on fp16 pairs
+            return y, True
+        if stats or fuse_gn is not None:
             self._colstats(y, getattr(_lib, route.split)(*geom), ep)
         getattr(_lib, route.launch)(x.buf, bank[key][1], y.buf, *geom, epilogue=_lib.make_epilogue(bias=bias, **ep), **form)
-        return y
+        return (y, False) if fuse_gn is not None else y
+
+    def _conv_gn_act(self, x, wt, bias, gn, act, mod=None, **conv_args):
+        """3x3 conv followed by GroupNorm ``gn`` (+ modulation ``mod``) + activation, the convolution's output read by nothing else
+        (Conv_0 -> GroupNorm_1 of a residual block).  One launch where the convolution takes the ``wino1d`` route, the kernel's query admits
+        the geometry and group count (maps of at most 256 pixels; IDIFF_NO_FUSED_GN answers no), the norm is unmodulated and the
+        epilogue in front of it is bias + per-image bias only: the convolution's output then never reaches memory.  Otherwise the
+        convolution with column sums and _gn_act, as two launches."""
+        if mod is not None:
+            return self._gn_act(self._conv(x, wt, bias, stats=True, **conv_args), gn, act, mod=mod)
+        y, fused = self._conv(x, wt, bias, fuse_gn=(gn, act), **conv_args)
+        return y if fused else self._gn_act(y, gn, act)
 
     def _pointwise(self, x, w, bias, stats=False, **ep):
         """1x1 conv / NIN on NHWC = plain GEMM over [B*HW, Cin]; w is [Cout, Cin]."""

@@ -50,7 +50,8 @@ const char *idiff_variant_flags(void);
  * stream beside the next panel's factorisation; 5 % at D = 12288 when the helper gets a hardware queue of its own, 50 %
  * SLOWER when the runtime maps it onto the caller's queue, which happens once a process has made a few streams),
  * IDIFF_NO_WINO43 (3x3 convolutions on the F(2x2,3x3) kernel instead of F(4x4,3x3)), IDIFF_NO_WINO43H (F(4x4,3x3) with its
- * contractions on the fp32 matrix cores instead of fp16 pairs), IDIFF_NO_FUSED_ATTN (idiff_attention256_ok answers 0), IDIFF_NO_WINO1D (idiff_conv2d_wino1d_ok answers 0), IDIFF_NO_PAIRS (idiff_gemm_pairs_ok answers 0: the 1x1
+ * contractions on the fp32 matrix cores instead of fp16 pairs), IDIFF_NO_FUSED_ATTN (idiff_attention256_ok answers 0), IDIFF_NO_WINO1D (idiff_conv2d_wino1d_ok answers 0),
+ * IDIFF_NO_FUSED_GN (idiff_conv2d_wino1d_gn_ok answers 0: the GroupNorm behind a row-wise convolution stays a launch of its own), IDIFF_NO_PAIRS (idiff_gemm_pairs_ok answers 0: the 1x1
  * projections behind a GroupNorm stay on idiff_gemm_f32's six-product form), IDIFF_PAIRS_MIN_TILES (tests: the number of 128 x 128
  * tiles from which idiff_gemm_pairs_ok answers 1; default 256).
  * Returns the previous value, -1 for an unknown name.  No reference counterpart. */
@@ -288,6 +289,21 @@ int64_t idiff_wino1d_weight_floats(int Cin, int Cout);
 int idiff_wino1d_pack_f32(const float *wt, float *u, int Cin, int Cout, void *stream);
 int idiff_conv2d_wino1d_f32(const float *x, const float *u, float *out, int B, int H, int W, int Cin, int Cout,
                             const idiff_epilogue *ep, void *stream);
+/* The same convolution with the GroupNorm (+ activation) that reads its output applied in the kernel's tail, for maps of at most 256
+ * pixels (Conv_0 -> GroupNorm_1 -> act of a residual block, models/layerspp.py:256-262): a workgroup finishes 256 consecutive pixels x 64
+ * channels at a time, which are whole images and whole groups, so mean and variance of every (image, group) are formed on chip -- the mean
+ * first, then the sum of squares about it, both in fp64 -- and
+ *     out = act(((conv + bias + rowbias) - mean) * rstd * gamma[c] + beta[c])
+ * is stored instead of the convolution's output, which never reaches memory: one launch and one pass over the activations less.
+ *   idiff_conv2d_wino1d_gn_ok   1 when idiff_conv2d_wino1d_ok and W <= 16, H * W divides 256, groups divides Cout and Cout / groups
+ *                               divides 64; 0 otherwise and under IDIFF_NO_FUSED_GN.
+ *   idiff_conv2d_wino1d_gn_f32  epilogue: bias and the per-image rowbias only (rows_per_group = H * W); a residual, colstats, an
+ *                               activation or a scale in front of the norm are refused (IDIFF_EINVAL, nothing launched), as is a geometry
+ *                               the query does not admit.  gamma, beta: [Cout], 16-byte aligned; act: IDIFF_ACT_*. */
+int idiff_conv2d_wino1d_gn_ok(int B, int H, int W, int Cin, int Cout, int groups);
+int idiff_conv2d_wino1d_gn_f32(const float *x, const float *u, float *out, int B, int H, int W, int Cin, int Cout,
+                               const idiff_epilogue *ep, int groups, const float *gamma, const float *beta, float eps, int act,
+                               void *stream);
 
 /* Split-precision form of the same convolution: the 16 position-wise contractions run on the bf16 matrix cores with every
  * fp32 operand cut exactly into three bf16 pieces and six of the nine partial products kept (fp32 accumulation; what is
