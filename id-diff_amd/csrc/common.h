@@ -52,6 +52,15 @@ bool conv3x3_narrow_ok(int B, int H, int W, int Cin, int Cout, int KH, int KW, i
 int conv3x3_narrow(const float *x, const float *wt, float *out, int B, int H, int W, int Cin, int Cout,
                    const idiff_epilogue *ep, hipStream_t stream);
 
+// Every launcher's "the caller's epilogue, or none" into its kernel arguments (P has the fields ep and has_ep): without one the kernels
+// read has_ep alone; the neutral values (no pointers, one row per group, scale 1) are there for the host code that reads p.ep regardless.
+template <class P> inline void set_epilogue(P &p, const idiff_epilogue *ep) {
+  p.has_ep = ep ? 1 : 0;
+  p.ep = ep ? *ep : idiff_epilogue{};
+  if (!ep) p.ep.out_scale = 1.f;
+  if (p.ep.rows_per_group <= 0) p.ep.rows_per_group = 1;
+}
+
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

@@ -182,7 +182,7 @@ int conv3x3_narrow(const float *x, const float *wt, float *out, int B, int H, in
   NarrowParams p = {};
   p.x = x; p.wt = wt; p.out = out; p.B = B; p.H = H; p.W = W; p.Cin = Cin;
   p.x_bytes = (uint32_t)((int64_t)B * H * W * Cin * 4);
-  if (ep) { p.ep = *ep; p.has_ep = 1; if (p.ep.rows_per_group <= 0) p.ep.rows_per_group = 1; }
+  set_epilogue(p, ep);
   const dim3 grid(ceil_div(B * H, 4 * ROWS_PER_WAVE)), block(256);
   switch (Cout) {
     case 1: hipLaunchKernelGGL(conv3x3_narrow_kernel<1>, grid, block, 0, stream, p); break;

@@ -1029,19 +1029,6 @@ int dispatch(IgemmParams &p, int batch, hipStream_t st) {
   return launch_cfg<64, 64, 2, 2, CONV, VEC>(p, batch, st);
 }
 
-void fill_epilogue(IgemmParams &p, const idiff_epilogue *ep) {
-  if (ep) {
-    p.ep = *ep;
-    p.has_ep = 1;
-    if (p.ep.rows_per_group <= 0) p.ep.rows_per_group = 1;
-  } else {
-    p.has_ep = 0;
-    p.ep.bias = nullptr; p.ep.rowbias = nullptr; p.ep.residual = nullptr;
-    p.ep.ld_rowbias = 0; p.ep.ld_residual = 0; p.ep.rows_per_group = 1; p.ep.act = 0; p.ep.out_scale = 1.f;
-    p.ep.rowscale = nullptr;
-  }
-}
-
 // The fast kernel addresses an operand through one 32-bit-offset buffer descriptor (< 4 GiB).  Larger problems
 // are cut into row ranges on the host (rows are independent): this returns the epilogue of the range that
 // starts at row m0, which must be a multiple of rows_per_group.
@@ -1069,7 +1056,7 @@ IDIFF_API int idiff_gemm_f32(const float *A, int64_t lda, int64_t strideA, const
   IgemmParams p = {};
   p.A = A; p.Bt = Bt; p.C = C; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
   p.strideA = strideA; p.strideB = strideB; p.strideC = strideC; p.M = M; p.N = N; p.K = K;
-  fill_epilogue(p, ep);
+  idiff::set_epilogue(p, ep);
   const bool vec = (K % 4 == 0) && (lda % 4 == 0) && (ldb % 4 == 0) && (strideA % 4 == 0) && (strideB % 4 == 0) &&
                    aligned16(A) && aligned16(Bt);
   hipStream_t st = (hipStream_t)stream;
@@ -1157,7 +1144,7 @@ IDIFF_API int idiff_gemm_pairs_f32(const float *A, int64_t lda, int64_t strideA,
   p.strideA = strideA; p.strideB = strideB; p.strideC = strideC;
   p.a_bytes = (uint32_t)a_bytes; p.b_bytes = (uint32_t)b_bytes;
   p.scale_a = weight_is_a ? w_scale : act_scale; p.scale_b = weight_is_a ? act_scale : w_scale;
-  fill_epilogue(p, ep);
+  idiff::set_epilogue(p, ep);
   return launch_pipe<128, 128, 2, 2, false, false, 2>(p, batch, (hipStream_t)stream);
 }
 
@@ -1180,7 +1167,7 @@ IDIFF_API int idiff_gemm_pairs_2src_f32(const float *A1, const float *A2, int64_
   p.A = A1; p.A2 = A2; p.K1 = K1; p.Bt = Bt; p.C = C; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
   p.a_bytes = (uint32_t)a1_bytes; p.a2_bytes = (uint32_t)a2_bytes; p.b_bytes = (uint32_t)b_bytes;
   p.scale_a = act_scale; p.scale_b = w_scale;
-  fill_epilogue(p, ep);
+  idiff::set_epilogue(p, ep);
   return launch_pipe<128, 128, 2, 2, false, false, 2>(p, 1, (hipStream_t)stream);
 }
 
@@ -1265,7 +1252,7 @@ IDIFF_API int idiff_gemm_2src_f32(const float *A1, const float *A2, int64_t lda,
   IgemmParams p = {};
   p.A = A1; p.A2 = A2; p.K1 = K1; p.Bt = Bt; p.C = C; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
   p.a_bytes = (uint32_t)a1_bytes; p.a2_bytes = (uint32_t)a2_bytes; p.b_bytes = (uint32_t)b_bytes;
-  fill_epilogue(p, ep);
+  idiff::set_epilogue(p, ep);
   return dispatch_pipe<false>(p, 1, (hipStream_t)stream);
 }
 
@@ -1292,7 +1279,7 @@ IDIFF_API int idiff_conv2d_nhwc_f32(const float *x, const float *wt, float *out,
   p.M = (int)M64; p.N = Cout; p.K = KH * KW * Cin;
   p.lda = 0; p.ldb = p.K; p.ldc = Cout;
   p.H = H; p.W = W; p.Cin = Cin; p.OH = OH; p.OW = OW; p.KW = KW; p.stride = stride; p.pad = pad;
-  fill_epilogue(p, ep);
+  idiff::set_epilogue(p, ep);
   const int64_t a_bytes = (int64_t)B * H * W * Cin * 4, b_bytes = (int64_t)Cout * p.K * 4;
   const bool fast_ok = (Cin % BK == 0 || Cin == 4) && KH * KW <= 32 && b_bytes < BUF_LIMIT && !idiff::option(idiff::OPT_NO_PIPE);
   if (ep && ep->colstats && !(fast_ok && a_bytes < BUF_LIMIT))

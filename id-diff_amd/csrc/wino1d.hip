@@ -41,7 +41,7 @@
 //   idiff_conv2d_nhwc_f32 -- its switches as compile-time constants -- and stores 16 bytes per pixel.
 // Measured (profiles/r05_wino1d_*.txt, HISTORY_r05.md 5): 1.03 - 1.23x winograd43h_kernel by shape, matrix cores 52 % busy, 1,120 lines from L2 per
 // workgroup and step.
-#include "common.h"
+#include "wino_host.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -63,17 +63,14 @@ __device__ __forceinline__ halfx8 r1_lds_read16(uint32_t at) { return *(const r1
 __device__ __forceinline__ void r1_lds_write4(uint32_t at, uint32_t v) { *(r1_lds_u32 *)at = v; }
 #pragma clang diagnostic pop
 
-constexpr double R1_A = 2.0 / 3.0, R1_B = 1.5;                     // the interpolation points of winograd43_shared.h
-constexpr float R1_a = (float)R1_A, R1_b = (float)R1_B, R1_a2 = (float)(R1_A * R1_A), R1_b2 = (float)(R1_B * R1_B),
-                R1_a3 = (float)(R1_A * R1_A * R1_A), R1_b3 = (float)(R1_B * R1_B * R1_B), R1_ab2 = (float)(R1_A * R1_A + R1_B * R1_B);
 constexpr int R1_THREADS = 256;
-constexpr int R1_COUT = 64;
-constexpr int R1_KC = 16;
+constexpr int R1_COUT = PAIR_COUT;                                  // 64, 16: the bank is pair_bank_pack's (wino_host.h)
+constexpr int R1_KC = PAIR_KC;
 constexpr int R1_PIXELS = 512;                                     // output pixels of a workgroup
 constexpr int R1_RT = R1_PIXELS / 4;                               // its row-tiles
 constexpr int R1_NSLOT = 18;                                       // (position, filter row)
-constexpr int R1_SLOT_BYTES = 2 * 64 * R1_KC * 2;                  // 4096
-constexpr int R1_PLANE_BYTES = 64 * R1_KC * 2;                     // 2048
+constexpr int R1_SLOT_BYTES = PAIR_SLOT_BYTES;                     // 4096
+constexpr int R1_PLANE_BYTES = PAIR_PLANE_BYTES;                   // 2048
 constexpr int R1_Z_BYTES = R1_RT * 4 * R1_COUT * 4;                // the tail's exchange: 131,072
 constexpr size_t R1_LDS_BYTES = R1_Z_BYTES;
 constexpr uint32_t R1_STAGE_STRIDE = 0x10000;                      // the two stages 64 KB apart: the other stage is one XOR away
@@ -544,9 +541,9 @@ __device__ __forceinline__ void r1_body(const Wino1dParams &p) {
         {                                                                                                      \
           const float s12 = z[1].cmp + z[2].cmp, d12 = z[1].cmp - z[2].cmp, s34 = z[3].cmp + z[4].cmp, d34 = z[3].cmp - z[4].cmp; \
           v[4 * j + 0][e] = fmaf(z[0].cmp + (s12 + s34), descale, b);                                           \
-          v[4 * j + 1][e] = fmaf(fmaf(R1_b, d34, R1_a * d12), descale, b);                                      \
-          v[4 * j + 2][e] = fmaf(fmaf(R1_b2, s34, R1_a2 * s12), descale, b);                                    \
-          v[4 * j + 3][e] = fmaf(fmaf(R1_b3, d34, fmaf(R1_a3, d12, z[5].cmp)), descale, b);                     \
+          v[4 * j + 1][e] = fmaf(fmaf(F4_b, d34, F4_a * d12), descale, b);                                      \
+          v[4 * j + 2][e] = fmaf(fmaf(F4_b2, s34, F4_a2 * s12), descale, b);                                    \
+          v[4 * j + 3][e] = fmaf(fmaf(F4_b3, d34, fmaf(F4_a3, d12, z[5].cmp)), descale, b);                     \
         }
         IDIFF_R1_AT(x, 0, badd.x) IDIFF_R1_AT(y, 1, badd.y) IDIFF_R1_AT(z, 2, badd.z) IDIFF_R1_AT(w, 3, badd.w)
 #undef IDIFF_R1_AT
@@ -646,9 +643,9 @@ __device__ __forceinline__ void r1_body(const Wino1dParams &p) {
       {                                                                                                      \
         const float s12 = z[1].cmp + z[2].cmp, d12 = z[1].cmp - z[2].cmp, s34 = z[3].cmp + z[4].cmp, d34 = z[3].cmp - z[4].cmp; \
         y[0][e] = z[0].cmp + (s12 + s34);                                                                     \
-        y[1][e] = fmaf(R1_b, d34, R1_a * d12);                                                                \
-        y[2][e] = fmaf(R1_b2, s34, R1_a2 * s12);                                                              \
-        y[3][e] = fmaf(R1_b3, d34, fmaf(R1_a3, d12, z[5].cmp));                                               \
+        y[1][e] = fmaf(F4_b, d34, F4_a * d12);                                                                \
+        y[2][e] = fmaf(F4_b2, s34, F4_a2 * s12);                                                              \
+        y[3][e] = fmaf(F4_b3, d34, fmaf(F4_a3, d12, z[5].cmp));                                               \
       }
       IDIFF_R1_AT(x, 0) IDIFF_R1_AT(y, 1) IDIFF_R1_AT(z, 2) IDIFF_R1_AT(w, 3)
 #undef IDIFF_R1_AT
@@ -744,52 +741,13 @@ wino1d_gn_kernel(const Wino1dParams p) { r1_body<W, true>(p); }
 
 // U[i][ky] = sum_kx G[i][kx] g[ky][kx] in fp64 for one (cin, cout) pair
 __device__ __forceinline__ void r1_u_of_pair(const float *wt, int Cin, int cin, int cout, double (&U)[18]) {
-  const double a = R1_A, b = R1_B, na = 1.0 / (2.0 * a * a * (a * a - b * b)), nb = 1.0 / (2.0 * b * b * (b * b - a * a)), n0 = 1.0 / (a * a * b * b);
-  const double Gm[6][3] = {{n0, 0.0, 0.0}, {na, a * na, a * a * na}, {na, -a * na, a * a * na}, {nb, b * nb, b * b * nb}, {nb, -b * nb, b * b * nb},
-                           {0.0, 0.0, 1.0}};
+  double Gm[6][3];
+  wino_G(F4_A, F4_B, Gm);
   for (int ky = 0; ky < 3; ++ky) {
     double g[3];
     for (int kx = 0; kx < 3; ++kx) g[kx] = (double)wt[((int64_t)cout * 9 + ky * 3 + kx) * Cin + cin];
     for (int i = 0; i < 6; ++i) U[3 * i + ky] = Gm[i][0] * g[0] + Gm[i][1] * g[1] + Gm[i][2] * g[2];
   }
-}
-
-// pass 1: max |U| over the layer (bits of a non-negative float order like unsigned integers; the word was zeroed by the launcher)
-__global__ void wino1d_absmax_kernel(const float *wt, unsigned int *absmax_bits, int Cin, int Cout) {
-  const int64_t total = (int64_t)Cin * Cout;
-  float m = 0.f;
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    double U[18];
-    r1_u_of_pair(wt, Cin, (int)(idx % Cin), (int)(idx / Cin), U);
-    for (int k = 0; k < 18; ++k) m = fmaxf(m, fabsf((float)U[k]));
-  }
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-  if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(absmax_bits, __float_as_uint(m));
-}
-
-// pass 2: the pairs.  The scale 2^k brings max |U| into [2^11, 2^12); header[0] receives 2^-k.
-__global__ void wino1d_pack_kernel(const float *wt, _Float16 *u, float *header, int Cin, int Cout) {
-  const float amax = __uint_as_float(*reinterpret_cast<const unsigned int *>(header + 1));
-  int e = 0;
-  if (amax > 0.f && isfinite(amax)) { (void)frexpf(amax, &e); }          // amax = f 2^e, f in [0.5, 1)
-  const int k = (amax > 0.f && isfinite(amax)) ? 12 - e : 0;
-  const double scale = ldexp(1.0, k);
-  const int64_t total = (int64_t)Cin * Cout;
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    const int cin = (int)(idx % Cin), cout = (int)(idx / Cin);
-    double U[18];
-    r1_u_of_pair(wt, Cin, cin, cout, U);
-    const int s = cin / R1_KC, c16 = cin % R1_KC, nt = cout / R1_COUT, co = cout % R1_COUT;
-    _Float16 *dst = u + ((int64_t)(s * (Cout / R1_COUT) + nt) * R1_NSLOT) * (R1_SLOT_BYTES / 2) + co * R1_KC + c16;
-    for (int q = 0; q < 18; ++q) {
-      const float v = (float)(U[q] * scale);                                   // rounded once to fp32, then cut
-      const _Float16 hi = (_Float16)v;
-      const _Float16 lo = (_Float16)(v - (float)hi);
-      dst[(int64_t)q * (R1_SLOT_BYTES / 2)] = hi;
-      dst[(int64_t)q * (R1_SLOT_BYTES / 2) + R1_PLANE_BYTES / 2] = lo;
-    }
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) header[0] = (float)ldexp(1.0, -k);
 }
 
 bool r1_geometry_ok(int B, int H, int W, int Cin, int Cout) {
@@ -803,22 +761,14 @@ bool r1_geometry_ok(int B, int H, int W, int Cin, int Cout) {
   return true;
 }
 
-template <int W>
-int r1_launch(const Wino1dParams &p, hipStream_t stream) {
+// one AttrGuard per kernel: the static lives in the instantiation
+template <void (*KERNEL)(const Wino1dParams)>
+int r1_launch(const Wino1dParams &p, const char *name, hipStream_t stream) {
   static idiff::AttrGuard guard;
-  const void *fn = reinterpret_cast<const void *>(wino1d_kernel<W>);
-  if (int rc = idiff::set_dynamic_lds_once(guard, &fn, 1, (int)R1_LDS_BYTES, "conv2d_wino1d")) return rc;
-  hipLaunchKernelGGL(wino1d_kernel<W>, dim3(p.blocks_m * p.tiles_n), dim3(R1_THREADS), R1_LDS_BYTES, stream, p);
-  return idiff::launch_status("conv2d_wino1d");
-}
-
-template <int W>
-int r1_launch_gn(const Wino1dParams &p, hipStream_t stream) {
-  static idiff::AttrGuard guard;
-  const void *fn = reinterpret_cast<const void *>(wino1d_gn_kernel<W>);
-  if (int rc = idiff::set_dynamic_lds_once(guard, &fn, 1, (int)R1_LDS_BYTES, "conv2d_wino1d_gn")) return rc;
-  hipLaunchKernelGGL(wino1d_gn_kernel<W>, dim3(p.blocks_m * p.tiles_n), dim3(R1_THREADS), R1_LDS_BYTES, stream, p);
-  return idiff::launch_status("conv2d_wino1d_gn");
+  const void *fn = reinterpret_cast<const void *>(KERNEL);
+  if (int rc = idiff::set_dynamic_lds_once(guard, &fn, 1, (int)R1_LDS_BYTES, name)) return rc;
+  hipLaunchKernelGGL(KERNEL, dim3(p.blocks_m * p.tiles_n), dim3(R1_THREADS), R1_LDS_BYTES, stream, p);
+  return idiff::launch_status(name);
 }
 
 // the fused GroupNorm's own conditions (the convolution's: r1_geometry_ok): a tail round of 256 pixels holds whole images, a tile of 64
@@ -846,20 +796,7 @@ IDIFF_API int idiff_conv2d_wino1d_colstats_split(int B, int H, int W, int Cin, i
 IDIFF_API int64_t idiff_wino1d_weight_floats(int Cin, int Cout) { return (int64_t)R1_NSLOT * Cin * Cout + 4; }
 
 IDIFF_API int idiff_wino1d_pack_f32(const float *wt, float *u, int Cin, int Cout, void *stream) {
-  using namespace idiff;
-  if (Cin <= 0 || Cout <= 0 || Cin % R1_KC || Cout % R1_COUT)
-    return fail("wino1d_pack: Cin must be a multiple of %d and Cout of %d (got %d, %d)", R1_KC, R1_COUT, Cin, Cout);
-  if (!wt || !u) return fail("wino1d_pack: null pointer");
-  if ((uintptr_t)u & 15) return fail("wino1d_pack: u must be 16-byte aligned");
-  const int64_t total = (int64_t)Cin * Cout;
-  float *header = u + (int64_t)R1_NSLOT * Cin * Cout;
-  hipError_t e = hipMemsetAsync(header, 0, 16, (hipStream_t)stream);
-  if (e != hipSuccess) return fail("wino1d_pack: hipMemsetAsync: %s", hipGetErrorString(e));
-  hipLaunchKernelGGL(wino1d_absmax_kernel, dim3(streaming_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, wt,
-                     reinterpret_cast<unsigned int *>(header + 1), Cin, Cout);
-  hipLaunchKernelGGL(wino1d_pack_kernel, dim3(streaming_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, wt,
-                     reinterpret_cast<_Float16 *>(u), header, Cin, Cout);
-  return launch_status("wino1d_pack");
+  return pair_bank_pack<R1_NSLOT, r1_u_of_pair>("wino1d_pack", wt, u, Cin, Cout, stream);
 }
 
 namespace {
@@ -872,14 +809,10 @@ int r1_run(const float *x, const float *u, float *out, int B, int H, int W, int 
   if (B == 0) return 0;
   if (!r1_geometry_ok(B, H, W, Cin, Cout))
     return fail("conv2d_wino1d: geometry B=%d H=%d W=%d Cin=%d Cout=%d not supported (ask idiff_conv2d_wino1d_ok)", B, H, W, Cin, Cout);
-  if (!x || !u || !out) return fail("conv2d_wino1d: null pointer");
-  if (((uintptr_t)x & 15) || ((uintptr_t)u & 15) || ((uintptr_t)out & 15)) return fail("conv2d_wino1d: x, u and out must be 16-byte aligned");
+  int64_t res_bytes = 0;
+  if (int rc = wino_check_call("conv2d_wino1d", x, u, out, ep, B, H, W, Cout, R1_X_LIMIT, res_bytes)) return rc;
   if (ep && ep->colstats && idiff_conv2d_wino1d_colstats_split(B, H, W, Cin, Cout) <= 0)
     return fail("conv2d_wino1d: colstats are switched off (IDIFF_NO_COLSTATS): ask idiff_conv2d_wino1d_colstats_split");
-  if (ep && (ep->rowbias || ep->rowscale) && ep->rows_per_group != H * W)
-    return fail("conv2d_wino1d: per-row-group bias / scale only per image (rows_per_group = H * W = %d, got %d)", H * W, ep->rows_per_group);
-  if (ep && ep->residual && (((uintptr_t)ep->residual & 15) || ep->ld_residual % 4 || ep->ld_residual < Cout || ep->ld_residual > 0x7fffffff / 4))
-    return fail("conv2d_wino1d: residual must be 16-byte aligned with a row pitch >= Cout that is a multiple of 4");
   if (gn) {
     // nothing is launched unless the tail can finish every (image, group) inside one round of one workgroup and store act(GN(.)) alone
     if (!r1_gn_geometry_ok(H, W, Cout, gn->groups))
@@ -895,44 +828,29 @@ int r1_run(const float *x, const float *u, float *out, int B, int H, int W, int 
     if (ep && ep->rows_per_group != H * W)
       return fail("conv2d_wino1d_gn: rows_per_group must be H * W = %d (got %d)", H * W, ep->rows_per_group);
   }
-  const int64_t res_bytes = (ep && ep->residual) ? (int64_t)B * H * W * ep->ld_residual * 4 : 0;
-  if (res_bytes >= R1_X_LIMIT) return fail("conv2d_wino1d: residual beyond one buffer descriptor");
   Wino1dParams p = {};
-  p.x = x; p.u = u; p.out = out; p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
+  // all cout tiles of a row block next to each other in the launch order (same XCD, same K step at about the same time: the block's pixels come
+  // from HBM once): 1.49x -> 1.39x algorithmic bytes over a forward at equal time (pairs of tiles: 73.0 ms, all four: 72.9, one: 74.1)
+  wino_fill(p, x, u, out, B, H, W, Cin, Cout, (int64_t)R1_NSLOT * Cin * Cout, res_bytes, ep, R1_COUT, false);
   p.rows_total = B * H;
-  p.blocks_m = ceil_div(p.rows_total, R1_PIXELS / W); p.tiles_n = Cout / R1_COUT;
-  {
-    // all cout tiles of a row block next to each other in the launch order (same XCD, same K step at about the same time: the block's pixels come
-    // from HBM once): 1.49x -> 1.39x algorithmic bytes over a forward at equal time (pairs of tiles: 73.0 ms, all four: 72.9, one: 74.1)
-    const int want = option_value(OPT_WINO_NGROUP);
-    p.ngroup = (want > 0 && p.tiles_n % want == 0) ? want : p.tiles_n;
-  }
-  p.x_bytes = (uint32_t)((int64_t)B * H * W * Cin * 4); p.u_bytes = (uint32_t)((int64_t)R1_NSLOT * Cin * Cout * 4);
-  p.out_bytes = (uint32_t)((int64_t)B * H * W * Cout * 4); p.res_bytes = (uint32_t)res_bytes;
-  if (ep) {
-    p.ep = *ep; p.has_ep = 1;
-    if (p.ep.rows_per_group <= 0) p.ep.rows_per_group = 1;
-  } else {
-    p.has_ep = 0; p.ep.rows_per_group = 1; p.ep.out_scale = 1.f;
-  }
-  p.c_nb2 = -R1_b2; p.c_na2 = -R1_a2; p.c_nab2 = -R1_ab2; p.c_a = R1_a; p.c_b = R1_b;
+  p.blocks_m = ceil_div(p.rows_total, R1_PIXELS / W);
 #ifdef IDIFF_W1D_STAMP
   { const char *e = getenv("IDIFF_W1D_STAMP_PTR"); p.stamps = e ? reinterpret_cast<uint64_t *>(strtoull(e, nullptr, 0)) : nullptr; }
 #endif
   if (gn) {
     p.gn_gamma = gn->gamma; p.gn_beta = gn->beta; p.gn_cpg = Cout / gn->groups; p.gn_act = gn->act; p.gn_eps = gn->eps;
     switch (W) {
-      case 4: return r1_launch_gn<4>(p, (hipStream_t)stream);
-      case 8: return r1_launch_gn<8>(p, (hipStream_t)stream);
-      default: return r1_launch_gn<16>(p, (hipStream_t)stream);       // (r1_gn_geometry_ok: W <= 16)
+      case 4: return r1_launch<wino1d_gn_kernel<4>>(p, "conv2d_wino1d_gn", (hipStream_t)stream);
+      case 8: return r1_launch<wino1d_gn_kernel<8>>(p, "conv2d_wino1d_gn", (hipStream_t)stream);
+      default: return r1_launch<wino1d_gn_kernel<16>>(p, "conv2d_wino1d_gn", (hipStream_t)stream);       // (r1_gn_geometry_ok: W <= 16)
     }
   }
   switch (W) {
-    case 4: return r1_launch<4>(p, (hipStream_t)stream);
-    case 8: return r1_launch<8>(p, (hipStream_t)stream);
-    case 16: return r1_launch<16>(p, (hipStream_t)stream);
-    case 64: return r1_launch<64>(p, (hipStream_t)stream);
-    default: return r1_launch<32>(p, (hipStream_t)stream);
+    case 4: return r1_launch<wino1d_kernel<4>>(p, "conv2d_wino1d", (hipStream_t)stream);
+    case 8: return r1_launch<wino1d_kernel<8>>(p, "conv2d_wino1d", (hipStream_t)stream);
+    case 16: return r1_launch<wino1d_kernel<16>>(p, "conv2d_wino1d", (hipStream_t)stream);
+    case 64: return r1_launch<wino1d_kernel<64>>(p, "conv2d_wino1d", (hipStream_t)stream);
+    default: return r1_launch<wino1d_kernel<32>>(p, "conv2d_wino1d", (hipStream_t)stream);
   }
 }
 }  // namespace

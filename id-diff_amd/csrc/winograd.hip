@@ -42,7 +42,7 @@
 //   Y[1][b] = z1b - z2b - z3b, fused epilogue (bias, per-sample bias, activation, residual, scales, optional per-tile
 //   column statistics), 16-byte stores -- the one-dword-per-lane store tail of the first version was store-issue bound
 //   (29.8k of 131k cycles per workgroup at Cin = 128).
-#include "common.h"
+#include "wino_host.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -875,14 +875,8 @@ int conv2d_winograd_impl(const float *x, const float *u, float *out, int B, int 
   if (B == 0) return 0;
   if (!geometry_ok(B, H, W, Cin, Cout))
     return fail("conv2d_winograd: geometry B=%d H=%d W=%d Cin=%d Cout=%d not supported (ask idiff_conv2d_winograd_ok)", B, H, W, Cin, Cout);
-  if (!x || !u || !out) return fail("conv2d_winograd: null pointer");
-  if (((uintptr_t)x & 15) || ((uintptr_t)u & 15) || ((uintptr_t)out & 15)) return fail("conv2d_winograd: x, u and out must be 16-byte aligned");
-  if (ep && ep->residual && (((uintptr_t)ep->residual & 15) || ep->ld_residual % 4))
-    return fail("conv2d_winograd: residual must be 16-byte aligned with a row pitch that is a multiple of 4");
-  const int64_t x_bytes = (int64_t)B * H * W * Cin * 4, out_bytes = (int64_t)B * H * W * Cout * 4;
-  if (ep && ep->residual && (ep->ld_residual < Cout || ep->ld_residual > 0x7fffffff / 4))
-    return fail("conv2d_winograd: ld_residual %lld is not a row pitch for %d channels", (long long)ep->ld_residual, Cout);
-  const int64_t res_bytes = (ep && ep->residual) ? (int64_t)B * H * W * ep->ld_residual * 4 : 0;
+  if (int rc = wino_check_operands("conv2d_winograd", x, u, out, ep, Cout)) return rc;
+  const int64_t x_bytes = (int64_t)B * H * W * Cin * 4, out_bytes = (int64_t)B * H * W * Cout * 4, res_bytes = wino_residual_bytes(ep, B, H, W);
   // the kernel addresses x, out and residual through one buffer descriptor each (32-bit byte offsets)
   if (x_bytes >= X_LIMIT || out_bytes >= X_LIMIT || res_bytes >= X_LIMIT) {
     if (ep && ep->colstats) return fail("conv2d_winograd: colstats is not available for inputs beyond one buffer descriptor");
@@ -904,30 +898,13 @@ int conv2d_winograd_impl(const float *x, const float *u, float *out, int B, int 
     return conv2d_winograd_impl(x + m_lo * Cin, u, out + m_lo * Cout, B - b_lo, H, W, Cin, Cout, ep ? &hi : nullptr, stream, split);
   }
   WinoParams p = {};
-  p.x = x; p.u = u; p.out = out; p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
-  p.tiles_x = W / 2; p.tiles_y = H / 2; p.tiles_per_img = (H / 2) * (W / 2); p.total_tiles = B * p.tiles_per_img;
-  p.tx_shift = p.tpi_shift = -1;
-  if ((p.tiles_x & (p.tiles_x - 1)) == 0 && (p.tiles_per_img & (p.tiles_per_img - 1)) == 0) {
-    p.tx_shift = __builtin_ctz((unsigned)p.tiles_x); p.tpi_shift = __builtin_ctz((unsigned)p.tiles_per_img);
-  }
-  p.tiles_m = ceil_div(p.total_tiles, WG_TILES); p.tiles_n = Cout / WG_COUT;
-  {
-    // two output-channel tiles per scheduling group: the workgroups of an XCD then stream two filter slabs instead of
-    // four (1.5-3 % on the Cout = 256 layers; the slabs of four tiles plus the live input lines overflow the 4 MB L2)
-    const int want = option_value(OPT_WINO_NGROUP);
-    p.ngroup = (want > 0 && p.tiles_n % want == 0) ? want : ((p.tiles_n > 2 && p.tiles_n % 2 == 0) ? 2 : p.tiles_n);
-  }
-  p.x_bytes = (uint32_t)x_bytes; p.u_bytes = (uint32_t)((int64_t)(split ? 24 : 16) * Cin * Cout * 4);
-  p.out_bytes = (uint32_t)out_bytes; p.res_bytes = (uint32_t)res_bytes;
-  if (ep) {
-    p.ep = *ep; p.has_ep = 1;
-    if (p.ep.rows_per_group <= 0) p.ep.rows_per_group = 1;
-    if (ep->colstats && p.tiles_per_img % WG_TILES && !(p.tiles_per_img >= 2 && p.tiles_per_img % 2 == 0 && WG_TILES % p.tiles_per_img == 0))
-      return fail("conv2d_winograd: colstats needs whole workgroups per sample or whole samples per workgroup "
-                  "(ask idiff_conv2d_winograd_colstats_split)");
-  } else {
-    p.has_ep = 0; p.ep.rows_per_group = 1; p.ep.out_scale = 1.f;
-  }
+  // two output-channel tiles per scheduling group: the workgroups of an XCD then stream two filter slabs instead of
+  // four (1.5-3 % on the Cout = 256 layers; the slabs of four tiles plus the live input lines overflow the 4 MB L2)
+  wino_fill(p, x, u, out, B, H, W, Cin, Cout, (int64_t)(split ? 24 : 16) * Cin * Cout, res_bytes, ep, WG_COUT, true);
+  wino_fill_tiles(p, 2, WG_TILES);
+  if (ep && ep->colstats && p.tiles_per_img % WG_TILES && !(p.tiles_per_img >= 2 && p.tiles_per_img % 2 == 0 && WG_TILES % p.tiles_per_img == 0))
+    return fail("conv2d_winograd: colstats needs whole workgroups per sample or whole samples per workgroup "
+                "(ask idiff_conv2d_winograd_colstats_split)");
   const void *fns[2] = {reinterpret_cast<const void *>(winograd_kernel<false>), reinterpret_cast<const void *>(winograd_kernel<true>)};
   {
     static AttrGuard guard;

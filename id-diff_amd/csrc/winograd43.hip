@@ -418,34 +418,17 @@ winograd43_kernel(const Wino43Params p) {
 #endif
 }
 
-// U = G g G^T in fp64, rounded once; g[ky][kx] = wt[cout][ky][kx][cin] (the K-contiguous panel of the direct kernel)
+// U = G g G^T in fp64 (f4_u_of_pair), rounded once
 __global__ void winograd43_pack_kernel(const float *wt, float *u, int Cin, int Cout) {
-  // G row of point p: (1, p, p^2) / N(p), N(p) = prod over the other finite points (p - q); N(0) = a^2 b^2 = 1,
-  // N(+-a) = 2 a^2 (a^2 - b^2), N(+-b) = 2 b^2 (b^2 - a^2); the point at infinity picks g[2]
-  const double a = F4_A, b = F4_B, na = 1.0 / (2.0 * a * a * (a * a - b * b)), nb = 1.0 / (2.0 * b * b * (b * b - a * a)), n0 = 1.0 / (a * a * b * b);
-  const double G[6][3] = {{n0, 0.0, 0.0},
-                          {na, a * na, a * a * na},
-                          {na, -a * na, a * a * na},
-                          {nb, b * nb, b * b * nb},
-                          {nb, -b * nb, b * b * nb},
-                          {0.0, 0.0, 1.0}};
   const int64_t total = (int64_t)Cin * Cout;
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
     const int cin = (int)(idx % Cin), cout = (int)(idx / Cin);
-    double g[3][3];
-    for (int ky = 0; ky < 3; ++ky)
-      for (int kx = 0; kx < 3; ++kx) g[ky][kx] = (double)wt[((int64_t)cout * 9 + ky * 3 + kx) * Cin + cin];
-    double gg[6][3];   // G g
-    for (int i = 0; i < 6; ++i)
-      for (int kx = 0; kx < 3; ++kx) gg[i][kx] = G[i][0] * g[0][kx] + G[i][1] * g[1][kx] + G[i][2] * g[2][kx];
+    double U[36];
+    f4_u_of_pair<0>(wt, Cin, cin, cout, U);
     const int s = cin / F4_KC, c8 = cin % F4_KC, nt = cout / F4_COUT, co = cout % F4_COUT;
     const int slot8 = 4 * ((c8 >> 2) ^ ((co >> 3) & 1)) + (c8 & 3);
     float *dst = u + ((int64_t)(s * (Cout / F4_COUT) + nt) * F4_NPOS * 64 + co) * F4_KC + slot8;
-    for (int i = 0; i < 6; ++i)
-      for (int j = 0; j < 6; ++j) {
-        const double v = gg[i][0] * G[j][0] + gg[i][1] * G[j][1] + gg[i][2] * G[j][2];
-        dst[(int64_t)(6 * i + j) * 64 * F4_KC] = (float)v;
-      }
+    for (int q = 0; q < 36; ++q) dst[(int64_t)q * 64 * F4_KC] = (float)U[q];
   }
 }
 
@@ -476,47 +459,22 @@ IDIFF_API int idiff_winograd43_pack_f32(const float *wt, float *u, int Cin, int 
   return launch_status("winograd43_pack");
 }
 
-IDIFF_API int idiff_conv2d_winograd43_colstats_split(int B, int H, int W, int Cin, int Cout);
 IDIFF_API int idiff_conv2d_winograd43_f32(const float *x, const float *u, float *out, int B, int H, int W, int Cin, int Cout,
                                           const idiff_epilogue *ep, void *stream) {
   using namespace idiff;
   if (B == 0) return 0;
   if (!f4_geometry_ok(B, H, W, Cin, Cout))
     return fail("conv2d_winograd43: geometry B=%d H=%d W=%d Cin=%d Cout=%d not supported (ask idiff_conv2d_winograd43_ok)", B, H, W, Cin, Cout);
-  if (!x || !u || !out) return fail("conv2d_winograd43: null pointer");
-  if (((uintptr_t)x & 15) || ((uintptr_t)u & 15) || ((uintptr_t)out & 15)) return fail("conv2d_winograd43: x, u and out must be 16-byte aligned");
+  int64_t res_bytes = 0;
+  if (int rc = wino_check_call("conv2d_winograd43", x, u, out, ep, B, H, W, Cout, F4_X_LIMIT, res_bytes)) return rc;
 #ifndef IDIFF_W43_STAMP
   if (ep && ep->colstats && idiff_conv2d_winograd43_colstats_split(B, H, W, Cin, Cout) <= 0)
     return fail("conv2d_winograd43: colstats needs whole workgroups per sample or whole samples per workgroup "
                 "(ask idiff_conv2d_winograd43_colstats_split)");
 #endif
-  if (ep && (ep->rowbias || ep->rowscale) && ep->rows_per_group != H * W)
-    return fail("conv2d_winograd43: per-row-group bias / scale only per image (rows_per_group = H * W = %d, got %d)", H * W, ep->rows_per_group);
-  if (ep && ep->residual && (((uintptr_t)ep->residual & 15) || ep->ld_residual % 4 || ep->ld_residual < Cout || ep->ld_residual > 0x7fffffff / 4))
-    return fail("conv2d_winograd43: residual must be 16-byte aligned with a row pitch >= Cout that is a multiple of 4");
-  const int64_t res_bytes = (ep && ep->residual) ? (int64_t)B * H * W * ep->ld_residual * 4 : 0;
-  if (res_bytes >= F4_X_LIMIT) return fail("conv2d_winograd43: residual beyond one buffer descriptor");
   Wino43Params p = {};
-  p.x = x; p.u = u; p.out = out; p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
-  p.tiles_x = W / 4; p.tiles_y = H / 4; p.tiles_per_img = p.tiles_x * p.tiles_y; p.total_tiles = B * p.tiles_per_img;
-  p.tx_shift = p.tpi_shift = -1;
-  if ((p.tiles_x & (p.tiles_x - 1)) == 0 && (p.tiles_per_img & (p.tiles_per_img - 1)) == 0) {
-    p.tx_shift = __builtin_ctz((unsigned)p.tiles_x); p.tpi_shift = __builtin_ctz((unsigned)p.tiles_per_img);
-  }
-  p.tiles_m = ceil_div(p.total_tiles, F4_TILES); p.tiles_n = Cout / F4_COUT;
-  {
-    const int want = option_value(OPT_WINO_NGROUP);
-    p.ngroup = (want > 0 && p.tiles_n % want == 0) ? want : ((p.tiles_n > 2 && p.tiles_n % 2 == 0) ? 2 : p.tiles_n);
-  }
-  p.x_bytes = (uint32_t)((int64_t)B * H * W * Cin * 4); p.u_bytes = (uint32_t)((int64_t)36 * Cin * Cout * 4);
-  p.out_bytes = (uint32_t)((int64_t)B * H * W * Cout * 4); p.res_bytes = (uint32_t)res_bytes;
-  if (ep) {
-    p.ep = *ep; p.has_ep = 1;
-    if (p.ep.rows_per_group <= 0) p.ep.rows_per_group = 1;
-  } else {
-    p.has_ep = 0; p.ep.rows_per_group = 1; p.ep.out_scale = 1.f;
-  }
-  p.c_nb2 = -F4_b2; p.c_na2 = -F4_a2; p.c_nab2 = -F4_ab2; p.c_a = F4_a; p.c_b = F4_b;
+  wino_fill(p, x, u, out, B, H, W, Cin, Cout, (int64_t)36 * Cin * Cout, res_bytes, ep, F4_COUT, true);
+  wino_fill_tiles(p, 4, F4_TILES);
   static AttrGuard guard;
   const void *fn = reinterpret_cast<const void *>(winograd43_kernel);
   if (int rc = set_dynamic_lds_once(guard, &fn, 1, (int)F4_LDS_BYTES, "conv2d_winograd43")) return rc;

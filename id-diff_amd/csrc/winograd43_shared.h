@@ -1,8 +1,8 @@
 // Shared by winograd43.hip (fp32 contraction) and winograd43h.hip (contraction on fp16 pairs): the F(4x4, 3x3) geometry, the
-// kernel arguments, the 6-point transforms' constants, the workgroup tail and the fp64 filter transform.  See winograd43.hip's header
-// for the algorithm.
+// kernel arguments, the workgroup tail and the fp64 filter transform (the points and the launchers' host code: wino_host.h).  See
+// winograd43.hip's header for the algorithm.
 #pragma once
-#include "common.h"
+#include "wino_host.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -11,16 +11,6 @@ namespace {
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef unsigned int uintx4 __attribute__((ext_vector_type(4)));
 
-// Interpolation points 0, +-a, +-b, infinity with a b = 1 (reciprocal pairs keep the transforms balanced): a = 2/3, b = 3/2.
-// (scripts/f43_emulation.py on the whole network: rel_err(S) 3.3e-6 for this set, 4.9e-6 for 1/2, 2 -- whose constants are all
-// dyadic -- and 7.0e-6 for Lavin's 1, 2.)  The transforms use these fp32 constants; G is evaluated in fp64 from the same a, b.
-#ifdef IDIFF_W43_DYADIC_POINTS   // A/B builds only (scripts/wino43_ab.py): the dyadic set 1/2, 2
-constexpr double F4_A = 0.5, F4_B = 2.0;
-#else
-constexpr double F4_A = 2.0 / 3.0, F4_B = 1.5;
-#endif
-constexpr float F4_a = (float)F4_A, F4_b = (float)F4_B, F4_a2 = (float)(F4_A * F4_A), F4_b2 = (float)(F4_B * F4_B),
-                F4_a3 = (float)(F4_A * F4_A * F4_A), F4_b3 = (float)(F4_B * F4_B * F4_B), F4_ab2 = (float)(F4_A * F4_A + F4_B * F4_B);
 constexpr int F4_TILES = 32;
 constexpr int F4_THREADS = 512;
 constexpr int F4_COUT = 64;
@@ -278,19 +268,20 @@ __device__ __forceinline__ void f4_tail(const Wino43Params &p, float *lds, float
 }
 
 
-// U = G g G^T in fp64 for one (cin, cout) pair: the 36 values, and their largest magnitude
+// U = G g G^T in fp64 for one (cin, cout) pair: the 36 values; g[ky][kx] = wt[cout][ky][kx][cin] (the K-contiguous panel of the direct kernel).
+// UNFUSED: see wino_dot3
+template <int UNFUSED>
 __device__ __forceinline__ void f4_u_of_pair(const float *wt, int Cin, int cin, int cout, double (&U)[36]) {
-  const double a = F4_A, b = F4_B, na = 1.0 / (2.0 * a * a * (a * a - b * b)), nb = 1.0 / (2.0 * b * b * (b * b - a * a)), n0 = 1.0 / (a * a * b * b);
-  const double G[6][3] = {{n0, 0.0, 0.0}, {na, a * na, a * a * na}, {na, -a * na, a * a * na}, {nb, b * nb, b * b * nb}, {nb, -b * nb, b * b * nb},
-                          {0.0, 0.0, 1.0}};
+  double G[6][3];
+  wino_G(F4_A, F4_B, G);
   double g[3][3];
   for (int ky = 0; ky < 3; ++ky)
     for (int kx = 0; kx < 3; ++kx) g[ky][kx] = (double)wt[((int64_t)cout * 9 + ky * 3 + kx) * Cin + cin];
   double gg[6][3];
   for (int i = 0; i < 6; ++i)
-    for (int kx = 0; kx < 3; ++kx) gg[i][kx] = G[i][0] * g[0][kx] + G[i][1] * g[1][kx] + G[i][2] * g[2][kx];
+    for (int kx = 0; kx < 3; ++kx) gg[i][kx] = wino_dot3<UNFUSED>(G[i][0], g[0][kx], G[i][1], g[1][kx], G[i][2], g[2][kx]);
   for (int i = 0; i < 6; ++i)
-    for (int j = 0; j < 6; ++j) U[6 * i + j] = gg[i][0] * G[j][0] + gg[i][1] * G[j][1] + gg[i][2] * G[j][2];
+    for (int j = 0; j < 6; ++j) U[6 * i + j] = wino_dot3<UNFUSED>(gg[i][0], G[j][0], gg[i][1], G[j][1], gg[i][2], G[j][2]);
 }
 
 

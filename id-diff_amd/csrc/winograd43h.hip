@@ -31,12 +31,12 @@ namespace {
 // U (global): [Cin/16][Cout/64][36 slots][2 planes][64 cout][16 cin] fp16 + one float (the factor that undoes the scaling) at the
 //   end; a wave's 16-byte loads of one plane are 1 KB contiguous.
 typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
-constexpr int H4_KC = 16;
+constexpr int H4_KC = PAIR_KC;                                         // 16: the bank is pair_bank_pack's (wino_host.h)
 constexpr int H4_TILE_BYTES = 64;
 constexpr int H4_POS_BYTES = F4_TILES * H4_TILE_BYTES;                 // 2048
 constexpr int H4_STAGE_BYTES = F4_NPOS * H4_POS_BYTES;                 // 73,728
-constexpr int H4_SLOT_BYTES = 2 * 64 * H4_KC * 2;                      // 4096: one position of one (step, cout tile)
-constexpr int H4_PLANE_BYTES = 64 * H4_KC * 2;                         // 2048
+constexpr int H4_SLOT_BYTES = PAIR_SLOT_BYTES;                         // 4096: one position of one (step, cout tile)
+constexpr int H4_PLANE_BYTES = PAIR_PLANE_BYTES;                       // 2048
 constexpr int H4_TOUCH_BYTES = 1024;                                   // landing zone of the look-ahead touches (see touch() in the kernel)
 constexpr size_t H4_LDS_BYTES = (2 * H4_STAGE_BYTES > (int)sizeof(float) * F4_Z_FLOATS ? 2 * H4_STAGE_BYTES : sizeof(float) * F4_Z_FLOATS) + H4_TOUCH_BYTES;
 #ifndef IDIFF_W43H_TOUCH_AHEAD
@@ -438,44 +438,6 @@ winograd43h_kernel(const Wino43Params p) {
 #endif
 }
 
-// pass 1: max |U| over the layer (bits of a non-negative float order like unsigned integers; the word was zeroed by the launcher)
-__global__ void winograd43h_absmax_kernel(const float *wt, unsigned int *absmax_bits, int Cin, int Cout) {
-  const int64_t total = (int64_t)Cin * Cout;
-  float m = 0.f;
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    double U[36];
-    f4_u_of_pair(wt, Cin, (int)(idx % Cin), (int)(idx / Cin), U);
-    for (int k = 0; k < 36; ++k) m = fmaxf(m, fabsf((float)U[k]));
-  }
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-  if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(absmax_bits, __float_as_uint(m));
-}
-
-// pass 2: the pairs.  The scale 2^k brings max |U| into [2^11, 2^12); header[0] receives 2^-k.
-__global__ void winograd43h_pack_kernel(const float *wt, _Float16 *u, float *header, int Cin, int Cout) {
-  const float amax = __uint_as_float(*reinterpret_cast<const unsigned int *>(header + 1));
-  int e = 0;
-  if (amax > 0.f && isfinite(amax)) { (void)frexpf(amax, &e); }          // amax = f 2^e, f in [0.5, 1)
-  const int k = (amax > 0.f && isfinite(amax)) ? 12 - e : 0;
-  const double scale = ldexp(1.0, k);
-  const int64_t total = (int64_t)Cin * Cout;
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    const int cin = (int)(idx % Cin), cout = (int)(idx / Cin);
-    double U[36];
-    f4_u_of_pair(wt, Cin, cin, cout, U);
-    const int s = cin / H4_KC, c16 = cin % H4_KC, nt = cout / F4_COUT, co = cout % F4_COUT;
-    _Float16 *dst = u + ((int64_t)(s * (Cout / F4_COUT) + nt) * F4_NPOS) * (H4_SLOT_BYTES / 2) + co * H4_KC + c16;
-    for (int q = 0; q < 36; ++q) {
-      const float v = (float)(U[q] * scale);                                   // rounded once to fp32, as the fp32 kernel's U
-      const _Float16 hi = (_Float16)v;
-      const _Float16 lo = (_Float16)(v - (float)hi);
-      dst[(int64_t)q * (H4_SLOT_BYTES / 2)] = hi;
-      dst[(int64_t)q * (H4_SLOT_BYTES / 2) + H4_PLANE_BYTES / 2] = lo;
-    }
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) header[0] = (float)ldexp(1.0, -k);
-}
-
 bool h4_geometry_ok(int B, int H, int W, int Cin, int Cout) {
   if (!f4_geometry_ok(B, H, W, Cin, Cout)) return false;
   if (Cin % H4_KC || Cin < 2 * H4_KC || Cin > 1024) return false;                                // edge-column offsets must not wrap past F4_INVALID
@@ -494,20 +456,7 @@ IDIFF_API int idiff_conv2d_winograd43h_ok(int B, int H, int W, int Cin, int Cout
 IDIFF_API int64_t idiff_winograd43h_weight_floats(int Cin, int Cout) { return (int64_t)36 * Cin * Cout + 4; }
 
 IDIFF_API int idiff_winograd43h_pack_f32(const float *wt, float *u, int Cin, int Cout, void *stream) {
-  using namespace idiff;
-  if (Cin <= 0 || Cout <= 0 || Cin % H4_KC || Cout % F4_COUT)
-    return fail("winograd43h_pack: Cin must be a multiple of %d and Cout of %d (got %d, %d)", H4_KC, F4_COUT, Cin, Cout);
-  if (!wt || !u) return fail("winograd43h_pack: null pointer");
-  if ((uintptr_t)u & 15) return fail("winograd43h_pack: u must be 16-byte aligned");
-  const int64_t total = (int64_t)Cin * Cout;
-  float *header = u + (int64_t)36 * Cin * Cout;
-  hipError_t e = hipMemsetAsync(header, 0, 16, (hipStream_t)stream);
-  if (e != hipSuccess) return fail("winograd43h_pack: hipMemsetAsync: %s", hipGetErrorString(e));
-  hipLaunchKernelGGL(winograd43h_absmax_kernel, dim3(streaming_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, wt,
-                     reinterpret_cast<unsigned int *>(header + 1), Cin, Cout);
-  hipLaunchKernelGGL(winograd43h_pack_kernel, dim3(streaming_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, wt,
-                     reinterpret_cast<_Float16 *>(u), header, Cin, Cout);
-  return launch_status("winograd43h_pack");
+  return pair_bank_pack<F4_NPOS, f4_u_of_pair<1>>("winograd43h_pack", wt, u, Cin, Cout, stream);
 }
 
 IDIFF_API int idiff_conv2d_winograd43h_f32(const float *x, const float *u, float *out, int B, int H, int W, int Cin, int Cout,
@@ -516,38 +465,14 @@ IDIFF_API int idiff_conv2d_winograd43h_f32(const float *x, const float *u, float
   if (B == 0) return 0;
   if (!h4_geometry_ok(B, H, W, Cin, Cout))
     return fail("conv2d_winograd43h: geometry B=%d H=%d W=%d Cin=%d Cout=%d not supported (ask idiff_conv2d_winograd43h_ok)", B, H, W, Cin, Cout);
-  if (!x || !u || !out) return fail("conv2d_winograd43h: null pointer");
-  if (((uintptr_t)x & 15) || ((uintptr_t)u & 15) || ((uintptr_t)out & 15)) return fail("conv2d_winograd43h: x, u and out must be 16-byte aligned");
+  int64_t res_bytes = 0;
+  if (int rc = wino_check_call("conv2d_winograd43h", x, u, out, ep, B, H, W, Cout, F4_X_LIMIT, res_bytes)) return rc;
   if (ep && ep->colstats && idiff_conv2d_winograd43_colstats_split(B, H, W, Cin, Cout) <= 0)
     return fail("conv2d_winograd43h: colstats needs whole workgroups per sample or whole samples per workgroup "
                 "(ask idiff_conv2d_winograd43_colstats_split)");
-  if (ep && (ep->rowbias || ep->rowscale) && ep->rows_per_group != H * W)
-    return fail("conv2d_winograd43h: per-row-group bias / scale only per image (rows_per_group = H * W = %d, got %d)", H * W, ep->rows_per_group);
-  if (ep && ep->residual && (((uintptr_t)ep->residual & 15) || ep->ld_residual % 4 || ep->ld_residual < Cout || ep->ld_residual > 0x7fffffff / 4))
-    return fail("conv2d_winograd43h: residual must be 16-byte aligned with a row pitch >= Cout that is a multiple of 4");
-  const int64_t res_bytes = (ep && ep->residual) ? (int64_t)B * H * W * ep->ld_residual * 4 : 0;
-  if (res_bytes >= F4_X_LIMIT) return fail("conv2d_winograd43h: residual beyond one buffer descriptor");
   Wino43Params p = {};
-  p.x = x; p.u = u; p.out = out; p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
-  p.tiles_x = W / 4; p.tiles_y = H / 4; p.tiles_per_img = p.tiles_x * p.tiles_y; p.total_tiles = B * p.tiles_per_img;
-  p.tx_shift = p.tpi_shift = -1;
-  if ((p.tiles_x & (p.tiles_x - 1)) == 0 && (p.tiles_per_img & (p.tiles_per_img - 1)) == 0) {
-    p.tx_shift = __builtin_ctz((unsigned)p.tiles_x); p.tpi_shift = __builtin_ctz((unsigned)p.tiles_per_img);
-  }
-  p.tiles_m = ceil_div(p.total_tiles, F4_TILES); p.tiles_n = Cout / F4_COUT;
-  {
-    const int want = option_value(OPT_WINO_NGROUP);
-    p.ngroup = (want > 0 && p.tiles_n % want == 0) ? want : ((p.tiles_n > 2 && p.tiles_n % 2 == 0) ? 2 : p.tiles_n);
-  }
-  p.x_bytes = (uint32_t)((int64_t)B * H * W * Cin * 4); p.u_bytes = (uint32_t)((int64_t)36 * Cin * Cout * 4);
-  p.out_bytes = (uint32_t)((int64_t)B * H * W * Cout * 4); p.res_bytes = (uint32_t)res_bytes;
-  if (ep) {
-    p.ep = *ep; p.has_ep = 1;
-    if (p.ep.rows_per_group <= 0) p.ep.rows_per_group = 1;
-  } else {
-    p.has_ep = 0; p.ep.rows_per_group = 1; p.ep.out_scale = 1.f;
-  }
-  p.c_nb2 = -F4_b2; p.c_na2 = -F4_a2; p.c_nab2 = -F4_ab2; p.c_a = F4_a; p.c_b = F4_b;
+  wino_fill(p, x, u, out, B, H, W, Cin, Cout, (int64_t)36 * Cin * Cout, res_bytes, ep, F4_COUT, true);
+  wino_fill_tiles(p, 4, F4_TILES);
 #ifdef IDIFF_W43H_STAMP
   { const char *e = getenv("IDIFF_W43H_STAMP_PTR"); p.stamps = e ? reinterpret_cast<uint64_t *>(strtoull(e, nullptr, 0)) : nullptr; }
 #endif

@@ -123,3 +123,157 @@ def test_diagnostic_builds_cannot_reach_the_production_path(library):
             text = open(os.path.join(scripts, name)).read()
             assert "build.sh" not in text or "_variant" in text, f"scripts/{name} drives build.sh itself"
             assert "IDIFF_SCRATCH_LIMIT" not in text, f"scripts/{name} lifts the scratch limit of a build it does not name"
+
+
+# ---- what the Winograd launchers refuse before any device call (csrc/wino_host.h and the four files in front of it)
+_X, _U, _OUT, _RES, _ROWB, _GAMMA, _BETA = 0x10000, 0x20000, 0x30000, 0x40000, 0x50000, 0x60000, 0x70000   # fabricated, 16-byte aligned
+_B, _H, _W, _CIN, _COUT = 2, 8, 8, 64, 64            # a geometry all five convolution entry points serve
+_CONVS = {"winograd": "conv2d_winograd", "winograd43": "conv2d_winograd43", "winograd43h": "conv2d_winograd43h",
+          "wino1d": "conv2d_wino1d", "wino1d_gn": "conv2d_wino1d"}     # entry -> the name its shared checks report
+_PACKERS = ("winograd43h_pack", "wino1d_pack")
+
+
+def _refusal_cases():
+    """(id, symbol, arguments, epilogue fields or None).  Each call violates exactly one of the launcher's conditions, with one exception
+    the arithmetic forces: a residual pitch above 0x7fffffff / 4 also puts the residual beyond one buffer descriptor for any H * W >= 16."""
+    cases = []
+    for entry in _CONVS:
+        def conv(tag, x=_X, u=_U, out=_OUT, B=_B, H=_H, ep=None, entry=entry):
+            args = [x, u, out, B, H, _W, _CIN, _COUT, ep]
+            if entry == "wino1d_gn":
+                args += [32, _GAMMA, _BETA, 1e-6, 1]
+            cases.append((f"{entry}-{tag}", f"idiff_conv2d_{entry}_f32", args))
+        conv("null_x", x=0); conv("null_u", u=0); conv("null_out", out=0)
+        conv("misaligned_x", x=_X + 4); conv("misaligned_u", u=_U + 8); conv("misaligned_out", out=_OUT + 4)
+        conv("geometry", H=7 if entry == "winograd" else 6)
+        conv("zero_batch", B=0)
+        if entry == "wino1d_gn":          # a residual, or a row group that is not the image, breaks a second condition of the fused GroupNorm
+            continue
+        conv("misaligned_residual", ep=dict(residual=_RES + 4, ld_residual=_COUT))
+        conv("residual_pitch_not_4", ep=dict(residual=_RES, ld_residual=_COUT + 2))
+        conv("residual_pitch_below_cout", ep=dict(residual=_RES, ld_residual=_COUT - 4))
+        conv("residual_pitch_above_int", ep=dict(residual=_RES, ld_residual=0x7fffffff // 4 + 1))
+        if entry != "winograd":           # F(2x2) serves any row group and splits a batch beyond one descriptor
+            conv("not_per_image", ep=dict(rowbias=_ROWB, ld_rowbias=_COUT, rows_per_group=_H * _W // 2))
+            conv("residual_beyond_descriptor", ep=dict(residual=_RES, ld_residual=1 << 23))
+    for name in _PACKERS:
+        def pack(tag, wt=_X, u=_U, Cin=32, Cout=64, name=name):
+            cases.append((f"{name}-{tag}", f"idiff_{name}_f32", [wt, u, Cin, Cout]))
+        pack("cin_granule", Cin=24); pack("cout_granule", Cout=96)
+        pack("null_wt", wt=0); pack("null_u", u=0); pack("misaligned_u", u=_U + 4)
+    return cases
+
+
+def _call_refusal(handle, symbol, args):
+    """The call on the null stream; -> (return code, idiff_last_error() when refused)."""
+    args = list(args)
+    for i, a in enumerate(args):
+        if isinstance(a, dict):
+            args[i] = ctypes.byref(_lib.Epilogue(**dict(dict(rows_per_group=1, out_scale=1.0), **a)))
+    rc = getattr(handle, symbol)(*args, None)
+    return rc, (handle.idiff_last_error().decode() if rc else "")
+
+
+# Return code and idiff_last_error() of every case, recorded from the library of the commit before the launchers' host code was merged.
+# conv2d_winograd reported a bad residual in two texts of its own; it now says what the other three entries say, and for its four residual
+# cases the words its old text has in common with theirs are what is pinned (_UNIFIED; the old text stands above each).
+_REFUSALS = {
+    'winograd-null_x': (1001, 'conv2d_winograd: null pointer'),
+    'winograd-null_u': (1001, 'conv2d_winograd: null pointer'),
+    'winograd-null_out': (1001, 'conv2d_winograd: null pointer'),
+    'winograd-misaligned_x': (1001, 'conv2d_winograd: x, u and out must be 16-byte aligned'),
+    'winograd-misaligned_u': (1001, 'conv2d_winograd: x, u and out must be 16-byte aligned'),
+    'winograd-misaligned_out': (1001, 'conv2d_winograd: x, u and out must be 16-byte aligned'),
+    'winograd-geometry': (1001, 'conv2d_winograd: geometry B=2 H=7 W=8 Cin=64 Cout=64 not supported (ask idiff_conv2d_winograd_ok)'),
+    'winograd-zero_batch': (0, ''),
+    # was: conv2d_winograd: residual must be 16-byte aligned with a row pitch that is a multiple of 4
+    'winograd-misaligned_residual': (1001, 'residual must be 16-byte aligned with a row pitch'),
+    # was: conv2d_winograd: residual must be 16-byte aligned with a row pitch that is a multiple of 4
+    'winograd-residual_pitch_not_4': (1001, 'residual must be 16-byte aligned with a row pitch'),
+    # was: conv2d_winograd: ld_residual 60 is not a row pitch for 64 channels
+    'winograd-residual_pitch_below_cout': (1001, 'row pitch'),
+    # was: conv2d_winograd: ld_residual 536870912 is not a row pitch for 64 channels
+    'winograd-residual_pitch_above_int': (1001, 'row pitch'),
+    'winograd43-null_x': (1001, 'conv2d_winograd43: null pointer'),
+    'winograd43-null_u': (1001, 'conv2d_winograd43: null pointer'),
+    'winograd43-null_out': (1001, 'conv2d_winograd43: null pointer'),
+    'winograd43-misaligned_x': (1001, 'conv2d_winograd43: x, u and out must be 16-byte aligned'),
+    'winograd43-misaligned_u': (1001, 'conv2d_winograd43: x, u and out must be 16-byte aligned'),
+    'winograd43-misaligned_out': (1001, 'conv2d_winograd43: x, u and out must be 16-byte aligned'),
+    'winograd43-geometry': (1001, 'conv2d_winograd43: geometry B=2 H=6 W=8 Cin=64 Cout=64 not supported (ask idiff_conv2d_winograd43_ok)'),
+    'winograd43-zero_batch': (0, ''),
+    'winograd43-misaligned_residual': (1001, 'conv2d_winograd43: residual must be 16-byte aligned with a row pitch >= Cout that is a multiple of 4'),
+    'winograd43-residual_pitch_not_4': (1001, 'conv2d_winograd43: residual must be 16-byte aligned with a row pitch >= Cout that is a multiple of 4'),
+    'winograd43-residual_pitch_below_cout': (1001, 'conv2d_winograd43: residual must be 16-byte aligned with a row pitch >= Cout that is a multiple of 4'),
+    'winograd43-residual_pitch_above_int': (1001, 'conv2d_winograd43: residual must be 16-byte aligned with a row pitch >= Cout that is a multiple of 4'),
+    'winograd43-not_per_image': (1001, 'conv2d_winograd43: per-row-group bias / scale only per image (rows_per_group = H * W = 64, got 32)'),
+    'winograd43-residual_beyond_descriptor': (1001, 'conv2d_winograd43: residual beyond one buffer descriptor'),
+    'winograd43h-null_x': (1001, 'conv2d_winograd43h: null pointer'),
+    'winograd43h-null_u': (1001, 'conv2d_winograd43h: null pointer'),
+    'winograd43h-null_out': (1001, 'conv2d_winograd43h: null pointer'),
+    'winograd43h-misaligned_x': (1001, 'conv2d_winograd43h: x, u and out must be 16-byte aligned'),
+    'winograd43h-misaligned_u': (1001, 'conv2d_winograd43h: x, u and out must be 16-byte aligned'),
+    'winograd43h-misaligned_out': (1001, 'conv2d_winograd43h: x, u and out must be 16-byte aligned'),
+    'winograd43h-geometry': (1001, 'conv2d_winograd43h: geometry B=2 H=6 W=8 Cin=64 Cout=64 not supported (ask idiff_conv2d_winograd43h_ok)'),
+    'winograd43h-zero_batch': (0, ''),
+    'winograd43h-misaligned_residual': (1001, 'conv2d_winograd43h: residual must be 16-byte aligned with a row pitch >= Cout that is a multiple of 4'),
+    'winograd43h-residual_pitch_not_4': (1001, 'conv2d_winograd43h: residual must be 16-byte aligned with a row pitch >= Cout that is a multiple of 4'),
+    'winograd43h-residual_pitch_below_cout': (1001, 'conv2d_winograd43h: residual must be 16-byte aligned with a row pitch >= Cout that is a multiple of 4'),
+    'winograd43h-residual_pitch_above_int': (1001, 'conv2d_winograd43h: residual must be 16-byte aligned with a row pitch >= Cout that is a multiple of 4'),
+    'winograd43h-not_per_image': (1001, 'conv2d_winograd43h: per-row-group bias / scale only per image (rows_per_group = H * W = 64, got 32)'),
+    'winograd43h-residual_beyond_descriptor': (1001, 'conv2d_winograd43h: residual beyond one buffer descriptor'),
+    'wino1d-null_x': (1001, 'conv2d_wino1d: null pointer'),
+    'wino1d-null_u': (1001, 'conv2d_wino1d: null pointer'),
+    'wino1d-null_out': (1001, 'conv2d_wino1d: null pointer'),
+    'wino1d-misaligned_x': (1001, 'conv2d_wino1d: x, u and out must be 16-byte aligned'),
+    'wino1d-misaligned_u': (1001, 'conv2d_wino1d: x, u and out must be 16-byte aligned'),
+    'wino1d-misaligned_out': (1001, 'conv2d_wino1d: x, u and out must be 16-byte aligned'),
+    'wino1d-geometry': (1001, 'conv2d_wino1d: geometry B=2 H=6 W=8 Cin=64 Cout=64 not supported (ask idiff_conv2d_wino1d_ok)'),
+    'wino1d-zero_batch': (0, ''),
+    'wino1d-misaligned_residual': (1001, 'conv2d_wino1d: residual must be 16-byte aligned with a row pitch >= Cout that is a multiple of 4'),
+    'wino1d-residual_pitch_not_4': (1001, 'conv2d_wino1d: residual must be 16-byte aligned with a row pitch >= Cout that is a multiple of 4'),
+    'wino1d-residual_pitch_below_cout': (1001, 'conv2d_wino1d: residual must be 16-byte aligned with a row pitch >= Cout that is a multiple of 4'),
+    'wino1d-residual_pitch_above_int': (1001, 'conv2d_wino1d: residual must be 16-byte aligned with a row pitch >= Cout that is a multiple of 4'),
+    'wino1d-not_per_image': (1001, 'conv2d_wino1d: per-row-group bias / scale only per image (rows_per_group = H * W = 64, got 32)'),
+    'wino1d-residual_beyond_descriptor': (1001, 'conv2d_wino1d: residual beyond one buffer descriptor'),
+    'wino1d_gn-null_x': (1001, 'conv2d_wino1d: null pointer'),
+    'wino1d_gn-null_u': (1001, 'conv2d_wino1d: null pointer'),
+    'wino1d_gn-null_out': (1001, 'conv2d_wino1d: null pointer'),
+    'wino1d_gn-misaligned_x': (1001, 'conv2d_wino1d: x, u and out must be 16-byte aligned'),
+    'wino1d_gn-misaligned_u': (1001, 'conv2d_wino1d: x, u and out must be 16-byte aligned'),
+    'wino1d_gn-misaligned_out': (1001, 'conv2d_wino1d: x, u and out must be 16-byte aligned'),
+    'wino1d_gn-geometry': (1001, 'conv2d_wino1d: geometry B=2 H=6 W=8 Cin=64 Cout=64 not supported (ask idiff_conv2d_wino1d_ok)'),
+    'wino1d_gn-zero_batch': (0, ''),
+    'winograd43h_pack-cin_granule': (1001, 'winograd43h_pack: Cin must be a multiple of 16 and Cout of 64 (got 24, 64)'),
+    'winograd43h_pack-cout_granule': (1001, 'winograd43h_pack: Cin must be a multiple of 16 and Cout of 64 (got 32, 96)'),
+    'winograd43h_pack-null_wt': (1001, 'winograd43h_pack: null pointer'),
+    'winograd43h_pack-null_u': (1001, 'winograd43h_pack: null pointer'),
+    'winograd43h_pack-misaligned_u': (1001, 'winograd43h_pack: u must be 16-byte aligned'),
+    'wino1d_pack-cin_granule': (1001, 'wino1d_pack: Cin must be a multiple of 16 and Cout of 64 (got 24, 64)'),
+    'wino1d_pack-cout_granule': (1001, 'wino1d_pack: Cin must be a multiple of 16 and Cout of 64 (got 32, 96)'),
+    'wino1d_pack-null_wt': (1001, 'wino1d_pack: null pointer'),
+    'wino1d_pack-null_u': (1001, 'wino1d_pack: null pointer'),
+    'wino1d_pack-misaligned_u': (1001, 'wino1d_pack: u must be 16-byte aligned'),
+}
+_UNIFIED = ("winograd-misaligned_residual", "winograd-residual_pitch_not_4", "winograd-residual_pitch_below_cout",
+            "winograd-residual_pitch_above_int")
+
+
+@pytest.mark.parametrize("case", _refusal_cases(), ids=lambda c: c[0])
+def test_winograd_launchers_refuse_before_any_device_call(case):
+    """No GPU needed: every call here is turned away by host code in front of the first HIP call (the addresses are fabricated: a
+    launcher that let one through would fault, not pass)."""
+    ident, symbol, args = case
+    want_rc, want_text = _REFUSALS[ident]
+    rc, text = _call_refusal(_lib.lib(), symbol, args)
+    assert rc == want_rc
+    if ident in _UNIFIED:
+        assert text.startswith("conv2d_winograd: ") and want_text in text
+    else:
+        assert text == want_text
+
+
+def test_refusal_table_is_complete():
+    assert sorted(_REFUSALS) == sorted(c[0] for c in _refusal_cases())
+    for ident, (rc, text) in _REFUSALS.items():
+        assert (rc, text) == (0, "") if ident.endswith("zero_batch") else rc == 1001 and text
