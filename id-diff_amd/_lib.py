@@ -89,6 +89,8 @@ _SIGNATURES = {
     "idiff_softmax_rows_f32": (c_i, [c_p, c_p, c_i64, c_i, c_f, c_p]),
     "idiff_attention256_ok": (c_i, [c_i, c_i, c_i]),
     "idiff_attention256_f32": (c_i, [c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_p]),
+    "idiff_attention_heads_ok": (c_i, [c_i, c_i, c_i, c_i]),
+    "idiff_attention_heads_f32": (c_i, [c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p]),
     "idiff_affine_act_f32": (c_i, [c_p, c_p, c_i64, c_f, c_f, c_i, c_p, c_i64, c_p]),
     "idiff_add_scale_f32": (c_i, [c_p, c_p, c_p, c_i64, c_f, c_p]),
     "idiff_fourier_embed_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_p]),
@@ -631,6 +633,28 @@ def attention256(qk, vt, out, B, C, s_qk, s_v, scale, bias_v=None):
         raise RuntimeError(f"attention256: shapes qk {tuple(qk.shape)}, vt {tuple(vt.shape)}, out {tuple(out.shape)} for B = {B}, C = {C}")
     _check(lib().idiff_attention256_f32(qk.data_ptr(), qk.stride(0), vt.data_ptr(), _ptr(bias_v), s_qk.data_ptr(), s_v.data_ptr(),
                                         out.data_ptr(), B, 256, C, float(scale), _stream()), "idiff_attention256_f32")
+    return out
+
+
+def attention_heads_ok(B, tokens, heads, D):
+    """True when the streaming one-launch attention serves this shape (heads of 32 / 64 / 128 channels, tokens a multiple of 64 up to
+    4096; off under IDIFF_NO_FUSED_ATTN / IDIFF_NO_PAIRS / IDIFF_NO_SPLIT)."""
+    return bool(lib().idiff_attention_heads_ok(B, tokens, heads, D))
+
+
+def attention_heads(qk, vt, out, B, tokens, heads, D, s_qk, s_v, scale, bias_v=None):
+    """out [B * tokens, C] = per head softmax(q_h k_h^T * scale) v_h (+ bias_v), C = heads * D, head h in columns [h D, (h + 1) D) of
+    q, k (qk [B * tokens, 2 C]: q | k) and out, rows [h D, (h + 1) D) of vt [B, C, tokens]."""
+    _dev(qk, "qk"); _dev(vt, "vt"); _dev(out, "out"); _dev(s_qk, "s_qk"); _dev(s_v, "s_v")
+    C = heads * D
+    if bias_v is not None:
+        _dev(bias_v, "bias_v")
+    if (qk.shape != (B * tokens, 2 * C) or vt.shape != (B, C, tokens) or out.numel() != B * tokens * C
+            or (bias_v is not None and bias_v.numel() != C) or s_qk.numel() < 2 or s_v.numel() < 2):
+        raise RuntimeError(f"attention_heads: shapes qk {tuple(qk.shape)}, vt {tuple(vt.shape)}, out {tuple(out.shape)} for B = {B}, "
+                           f"{tokens} tokens, {heads} heads of {D}")
+    _check(lib().idiff_attention_heads_f32(qk.data_ptr(), qk.stride(0), vt.data_ptr(), _ptr(bias_v), s_qk.data_ptr(), s_v.data_ptr(),
+                                           out.data_ptr(), B, tokens, heads, D, float(scale), _stream()), "idiff_attention_heads_f32")
     return out
 
 

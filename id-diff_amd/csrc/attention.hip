@@ -309,6 +309,217 @@ int launch_attention(const AttnParams &p, hipStream_t st) {
   return idiff::launch_status("attention256");
 }
 
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Multi-head self-attention with the keys STREAMED (reference: models/BeatGANsblocks.py:466-526, QKVAttentionLegacy and QKVAttention
+// after the head order has been moved into the projection's rows): heads of D = 32 / 64 / 128 channels over T = 64 .. 4096 tokens.
+// The arithmetic is attention256_kernel's (fp16 pairs, three products, fp32 accumulation, fp32 softmax, probabilities x 2^10 before
+// their cut); T is not bounded by the register file because the softmax runs over chunks of 64 keys with a running maximum and sum
+// per query: when the maximum moves, the output accumulators and the sum are multiplied by exp(old - new); one division at the end.
+//
+// Work split: a workgroup = (sample, head, NW x 16 queries), NW = 8 waves where T is a multiple of 128, else 4.  Per chunk of 64 keys
+//   stage    K [64 keys, D] and V^T [D, 64 keys] of the head: requested from global one chunk ahead (registers), cut into pairs and
+//            stored to LDS in at_swz order between two barriers
+//   phase 1  S^T[key, q] = sum_c K[key, c] Q[q, c]      A = K (LDS), B = Q (registers, cut once per workgroup), 4 key blocks x D / 32
+//   softmax  query q sits in lanes q + 16 g: 16 logits per lane, two shuffles for the chunk's maximum; the sum stays per lane until the end
+//   phase 2  O^T[c, q] += sum_key V^T[c, key] P[key, q]  A = V^T (LDS, keys in the slot order of attention256_kernel), B = P (registers)
+// LDS: K hi | K lo | V hi | V lo, 128 D bytes each: 16 / 32 / 64 KB.  Registers at D = 128: Q pairs 32, S 16, O 32, staging 32 (NW = 8).
+// The workgroups of one (sample, head) take consecutive slots on ONE XCD: its K / V come from HBM once and from that L2 afterwards.
+constexpr int AH_KC = 64;                        // keys per chunk
+
+struct HeadsParams {
+  const float *qk;        // [B * T, ld_qk]: q of head h in columns [h D, (h + 1) D), k in [C + h D, C + (h + 1) D), C = H D
+  const float *vt;        // [B, C, T]
+  const float *bias_v;    // [C] or null
+  const float *s_qk;      // device {s, 1 / s}
+  const float *s_v;       // device {s, 1 / s}
+  float *out;             // [B * T, C]
+  int64_t ld_qk;
+  int B, T, H;
+  float scale;            // softmax scale (D^-1/2)
+};
+
+template <int D, int NW>
+__global__ void __launch_bounds__(64 * NW)
+attention_heads_kernel(const HeadsParams p) {
+  extern __shared__ __attribute__((aligned(16))) char ah_lds[];
+  constexpr int NT = 64 * NW;                    // threads
+  constexpr int BQ = 16 * NW;                    // queries per workgroup
+  constexpr int NKS = D / 32;                    // channel steps of phase 1
+  constexpr int NCB = D / 16;                    // channel blocks of the output
+  constexpr int PLANE = AH_KC * D * 2;           // bytes of one plane: 64 x D halves
+  constexpr int NLD = (AH_KC * D / 4) / NT;      // 16-byte requests per thread and operand per chunk
+  static_assert(D == 32 || D == 64 || D == 128, "head width");
+  static_assert((AH_KC * D / 4) % NT == 0 && NLD >= 1, "the chunk divides over the threads");
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l15 = lane & 15, g = lane >> 4;
+  int bid = blockIdx.x;
+  {
+    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, local = bid >> 3;
+    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
+  }
+  const int T = p.T, C = p.H * D, nqb = T / BQ, nch = T / AH_KC;
+  const int qb = bid % nqb, bh = bid / nqb, h = bh % p.H, b = bh / p.H;
+  const int q0 = qb * BQ + wave * 16;
+  const float s_qk = p.s_qk[0], inv_qk = p.s_qk[1], s_v = p.s_v[0], inv_v = p.s_v[1];
+  char *const lds_k = ah_lds, *const lds_v = ah_lds + 2 * PLANE;
+
+  // ---- staging: request e = tid + i NT of a chunk.  K: row = key (D / 4 requests per row), V^T: row = channel (16 requests per row)
+  const float *k_src[NLD], *v_src[NLD];
+  int k_dst[NLD], v_dst[NLD];
+#pragma unroll
+  for (int i = 0; i < NLD; ++i) {
+    const int e = tid + i * NT;
+    {
+      const int row = e / (D / 4), piece = e % (D / 4), p8 = piece & 7;          // channels 4 piece ..: step piece / 8, 16-byte piece p8 / 2
+      k_src[i] = p.qk + ((int64_t)b * T + row) * p.ld_qk + C + h * D + 4 * piece;
+      k_dst[i] = (piece >> 3) * (AH_KC * 64) + row * 64 + (((p8 >> 1) ^ at_swz(row)) << 4) + (p8 & 1) * 8;
+    }
+    {
+      const int row = e >> 4, piece = e & 15, p8 = piece & 7;                    // keys 4 piece ..: 32-key group piece / 8, slot order as above
+      v_src[i] = p.vt + ((int64_t)b * C + h * D + row) * T + 4 * piece;
+      v_dst[i] = (piece >> 3) * (D * 64) + row * 64 + (((p8 & 3) ^ at_swz(row)) << 4) + (p8 >> 2) * 8;
+    }
+  }
+  float4 kst[NLD], vst[NLD];
+  auto fetch = [&](int c) __attribute__((always_inline)) {       // past the last chunk: re-reads the last one, never stored
+    const int cc = c < nch ? c : nch - 1;
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) {
+      kst[i] = *reinterpret_cast<const float4 *>(k_src[i] + (int64_t)cc * AH_KC * p.ld_qk);
+      vst[i] = *reinterpret_cast<const float4 *>(v_src[i] + cc * AH_KC);
+    }
+  };
+  fetch(0);
+
+  // ---- this wave's queries as the B operand of phase 1: lane (query l15, k group g) holds channels 32 kc + 8 g .. + 7
+  halfx8 qh[NKS], ql[NKS];
+  {
+    const float *q_src = p.qk + ((int64_t)b * T + q0 + l15) * p.ld_qk + h * D + 8 * g;
+#pragma unroll
+    for (int kc = 0; kc < NKS; ++kc) {
+      const float4 qa = *reinterpret_cast<const float4 *>(q_src + 32 * kc), qc = *reinterpret_cast<const float4 *>(q_src + 32 * kc + 4);
+      uintx2 h0, l0, h1, l1;
+      cut4(qa, s_qk, h0, l0); cut4(qc, s_qk, h1, l1);
+      qh[kc] = __builtin_bit_cast(halfx8, uintx4{h0.x, h0.y, h1.x, h1.y});
+      ql[kc] = __builtin_bit_cast(halfx8, uintx4{l0.x, l0.y, l1.x, l1.y});
+    }
+  }
+  floatx4 oacc[NCB];
+#pragma unroll
+  for (int cb = 0; cb < NCB; ++cb) oacc[cb] = floatx4{0.f, 0.f, 0.f, 0.f};
+  // logits = S / s^2 * scale; exp(x) = 2^(x log2 e), as attention256_kernel.  m_run: the running maximum of the query's RAW sums S (the
+  // same in its four lanes); l_run: this lane's share of the running sum.  First chunk: m_run = -inf and m_new is finite for finite
+  // operands, so the rescaling factor is 2^(-inf) = 0 on accumulators that are zero: never inf - inf.
+  const float sc = p.scale * inv_qk * inv_qk * 1.44269504088896340736f;
+  float m_run = -INFINITY, l_run = 0.f;
+  const int a_off = l15 * 64 + ((g ^ at_swz(l15)) << 4);         // operand row 16 rb + l15: the swizzle does not depend on rb
+
+#pragma unroll 1
+  for (int c = 0; c < nch; ++c) {
+    __syncthreads();                             // every wave has read chunk c - 1
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) {
+      uintx2 hi, lo;
+      cut4(kst[i], s_qk, hi, lo);
+      *reinterpret_cast<uintx2 *>(lds_k + k_dst[i]) = hi;
+      *reinterpret_cast<uintx2 *>(lds_k + k_dst[i] + PLANE) = lo;
+      cut4(vst[i], s_v, hi, lo);
+      *reinterpret_cast<uintx2 *>(lds_v + v_dst[i]) = hi;
+      *reinterpret_cast<uintx2 *>(lds_v + v_dst[i] + PLANE) = lo;
+    }
+    __syncthreads();
+    fetch(c + 1);                                // in flight under this chunk's matrix work
+
+    // ---- phase 1
+    floatx4 sacc[4];
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb) sacc[kb] = floatx4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kc = 0; kc < NKS; ++kc)
+#pragma unroll
+      for (int kb = 0; kb < 4; ++kb) {
+        const char *ap = lds_k + kc * (AH_KC * 64) + kb * (16 * 64) + a_off;
+        const halfx8 kh = *reinterpret_cast<const halfx8 *>(ap), kl = *reinterpret_cast<const halfx8 *>(ap + PLANE);
+        sacc[kb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh, qh[kc], sacc[kb], 0, 0, 0);
+        sacc[kb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh, ql[kc], sacc[kb], 0, 0, 0);
+        sacc[kb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kl, qh[kc], sacc[kb], 0, 0, 0);
+      }
+
+    // ---- streaming softmax
+    float m = m_run;
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) m = fmaxf(m, sacc[kb][i]);
+    m = fmaxf(m, __shfl_xor(m, 16, 64));
+    m = fmaxf(m, __shfl_xor(m, 32, 64));
+    const float alpha = __builtin_amdgcn_exp2f((m_run - m) * sc);
+    m_run = m;
+    float sum = 0.f;
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { const float e = __builtin_amdgcn_exp2f((sacc[kb][i] - m) * sc); sacc[kb][i] = e; sum += e; }
+    l_run = l_run * alpha + sum;
+#pragma unroll
+    for (int cb = 0; cb < NCB; ++cb) { oacc[cb][0] *= alpha; oacc[cb][1] *= alpha; oacc[cb][2] *= alpha; oacc[cb][3] *= alpha; }
+    halfx8 ph[2], pl[2];
+#pragma unroll
+    for (int m2 = 0; m2 < 2; ++m2) {
+      uintx2 h0, l0, h1, l1;
+      cut4(make_float4(sacc[2 * m2][0], sacc[2 * m2][1], sacc[2 * m2][2], sacc[2 * m2][3]), AT_PSCALE, h0, l0);
+      cut4(make_float4(sacc[2 * m2 + 1][0], sacc[2 * m2 + 1][1], sacc[2 * m2 + 1][2], sacc[2 * m2 + 1][3]), AT_PSCALE, h1, l1);
+      ph[m2] = __builtin_bit_cast(halfx8, uintx4{h0.x, h0.y, h1.x, h1.y});
+      pl[m2] = __builtin_bit_cast(halfx8, uintx4{l0.x, l0.y, l1.x, l1.y});
+    }
+
+    // ---- phase 2
+#pragma unroll
+    for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+      for (int m2 = 0; m2 < 2; ++m2) {
+        const char *ap = lds_v + m2 * (D * 64) + cb * (16 * 64) + a_off;
+        const halfx8 vh = *reinterpret_cast<const halfx8 *>(ap), vl = *reinterpret_cast<const halfx8 *>(ap + PLANE);
+        oacc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh, ph[m2], oacc[cb], 0, 0, 0);
+        oacc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh, pl[m2], oacc[cb], 0, 0, 0);
+        oacc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vl, ph[m2], oacc[cb], 0, 0, 0);
+      }
+  }
+
+  // ---- output: lane (query l15, g) holds channels 16 cb + 4 g + i of head h
+  l_run += __shfl_xor(l_run, 16, 64);
+  l_run += __shfl_xor(l_run, 32, 64);
+  const float descale = inv_v / (l_run * AT_PSCALE);
+  float *o = p.out + ((int64_t)b * T + q0 + l15) * C + h * D + 4 * g;
+#pragma unroll
+  for (int cb = 0; cb < NCB; ++cb) {
+    float4 y = make_float4(oacc[cb][0] * descale, oacc[cb][1] * descale, oacc[cb][2] * descale, oacc[cb][3] * descale);
+    if (p.bias_v) {
+      const float4 bv = *reinterpret_cast<const float4 *>(p.bias_v + h * D + 16 * cb + 4 * g);
+      y.x += bv.x; y.y += bv.y; y.z += bv.z; y.w += bv.w;
+    }
+    *reinterpret_cast<float4 *>(o + 16 * cb) = y;
+  }
+}
+
+template <int D, int NW>
+int launch_attention_heads(const HeadsParams &p, hipStream_t st) {
+  static idiff::AttrGuard guard;
+  constexpr int lds = 4 * AH_KC * D * 2;
+  const void *fn = reinterpret_cast<const void *>(attention_heads_kernel<D, NW>);
+  if (int rc = idiff::set_dynamic_lds_once(guard, &fn, 1, lds, "attention_heads")) return rc;
+  const int64_t nwg = (int64_t)p.B * p.H * (p.T / (16 * NW));
+  hipLaunchKernelGGL((attention_heads_kernel<D, NW>), dim3((unsigned)nwg), dim3(64 * NW), lds, st, p);
+  return idiff::launch_status("attention_heads");
+}
+
+bool attention_heads_shape_ok(int B, int tokens, int H, int D) {
+  return B > 0 && H >= 1 && (D == 32 || D == 64 || D == 128) && (int64_t)H * D <= 1024 && tokens >= 64 && tokens <= 4096 && tokens % 64 == 0 &&
+         (int64_t)B * H <= (1 << 20);
+}
+
 }  // namespace
 
 IDIFF_API int idiff_attention256_ok(int B, int tokens, int C) {
@@ -328,4 +539,32 @@ IDIFF_API int idiff_attention256_f32(const float *qk, int64_t ld_qk, const float
     return fail("attention256: qk, vt, bias_v and out must be 16-byte aligned");
   AttnParams p = {qk, vt, bias_v, s_qk, s_v, out, ld_qk, B, scale};
   return C == 256 ? launch_attention<256>(p, (hipStream_t)stream) : launch_attention<128>(p, (hipStream_t)stream);
+}
+
+IDIFF_API int idiff_attention_heads_ok(int B, int tokens, int H, int D) {
+  if (idiff::option(idiff::OPT_NO_PAIRS) || idiff::option(idiff::OPT_NO_SPLIT) || idiff::option(idiff::OPT_NO_FUSED_ATTN)) return 0;
+  // every shape class the library serves is admitted: measured 2.0 - 6.1x the three launches per head (profiles/attention_heads_bench.txt)
+  return attention_heads_shape_ok(B, tokens, H, D) ? 1 : 0;
+}
+
+IDIFF_API int idiff_attention_heads_f32(const float *qk, int64_t ld_qk, const float *vt, const float *bias_v, const float *s_qk, const float *s_v,
+                                        float *out, int B, int tokens, int H, int D, float scale, void *stream) {
+  using namespace idiff;
+  if (B == 0) return 0;
+  if (!attention_heads_shape_ok(B, tokens, H, D))
+    return fail("attention_heads: heads of 32, 64 or 128 channels, H D <= 1024, tokens a multiple of 64 in [64, 4096], B H <= 2^20 "
+                "(got batch %d, %d tokens, %d heads of %d)", B, tokens, H, D);
+  const int C = H * D;
+  if (!qk || !vt || !out || !s_qk || !s_v) return fail("attention_heads: null pointer");
+  if (ld_qk < 2 * C || ld_qk % 4) return fail("attention_heads: the q|k row pitch must be >= 2 C and a multiple of 4 (got %lld)", (long long)ld_qk);
+  if (((uintptr_t)qk & 15) || ((uintptr_t)vt & 15) || ((uintptr_t)out & 15) || (bias_v && ((uintptr_t)bias_v & 15)))
+    return fail("attention_heads: qk, vt, bias_v and out must be 16-byte aligned");
+  HeadsParams p = {qk, vt, bias_v, s_qk, s_v, out, ld_qk, B, tokens, H, scale};
+  hipStream_t st = (hipStream_t)stream;
+  const bool wide = tokens % 128 == 0;           // eight waves of 16 queries; four where the token count is an odd multiple of 64
+  switch (D) {
+    case 32: return wide ? launch_attention_heads<32, 8>(p, st) : launch_attention_heads<32, 4>(p, st);
+    case 64: return wide ? launch_attention_heads<64, 8>(p, st) : launch_attention_heads<64, 4>(p, st);
+    default: return wide ? launch_attention_heads<128, 8>(p, st) : launch_attention_heads<128, 4>(p, st);
+  }
 }

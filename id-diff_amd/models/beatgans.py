@@ -9,8 +9,9 @@ to this network:
 * the scale-shift time conditioning ``norm(h) * (1 + scale) + shift`` (BeatGANsblocks.py:316-321) is folded into the
   GroupNorm-apply kernel, and ``emb_layers`` (SiLU -> Linear(E, 2*C)) of ALL residual blocks is one stacked GEMM;
 * resampling is nearest x2 / 2x2 average (no FIR): ``idiff_resample2x_nhwc_f32``;
-* attention uses the 1-D-conv QKV projection; with one head the legacy and the new channel orders coincide
-  (q | k | v thirds of the projection), which is the only case the dimension-estimation configs use.
+* attention uses the 1-D-conv QKV projection; ``num_heads`` / ``num_head_channels`` / ``num_heads_upsample`` and both head
+  orders (``use_new_attention_order``) are served: the order is a row permutation of the projection at pack time
+  (``pack_qkv_heads``), and with one head -- what the dimension-estimation configs use -- both coincide with the plain thirds.
 
 Module nesting (``input_blocks.<k>.<j>...``, ``middle_block``, ``output_blocks``, ``time_embed``, ``out``) reproduces the
 reference's ``state_dict`` keys.
@@ -65,11 +66,39 @@ class ResBlock(nn.Module):
         self.skip_connection = nn.Identity() if out_channels == channels else nn.Conv2d(channels, out_channels, 1)
 
 
+def pack_qkv_heads(weight, bias, heads, new_order):
+    """The qkv projection of an AttentionBlock (``weight`` [3C, C], ``bias`` [3C]) in the executor's head-contiguous order:
+    ``(wqk [2C, C], bqk [2C], wv [C, C], bv [C])`` with q of head h in rows [h D, (h + 1) D) of ``wqk``, k of head h in rows
+    [C + h D, C + (h + 1) D), v of head h in rows [h D, (h + 1) D) of ``wv``, D = C / heads.  A row permutation, done once per pack:
+    QKVAttentionLegacy (BeatGANsblocks.py:466-491) reads the projection as ``heads`` groups of (q | k | v) rows, 3 D each;
+    QKVAttention (:498-526, ``new_order``) as the q, k, v thirds with the heads inside each.  With one head both are the plain
+    thirds, which are sliced as they always were."""
+    C = weight.shape[0] // 3
+    if weight.shape[0] != 3 * C or C % heads:
+        raise ValueError(f"qkv projection of {weight.shape[0]} rows does not split into q, k, v of {heads} heads")
+    if heads == 1 or new_order:
+        q, k, v = slice(0, C), slice(C, 2 * C), slice(2 * C, 3 * C)
+        return (weight[:2 * C].contiguous(), bias[:2 * C].contiguous(), weight[2 * C:].contiguous(), bias[2 * C:].contiguous())
+    D = C // heads
+    rows = torch.arange(3 * C, device=weight.device).view(heads, 3, D)      # legacy: row h 3D + part D + j
+    qk_rows = torch.cat([rows[:, 0].reshape(-1), rows[:, 1].reshape(-1)])
+    v_rows = rows[:, 2].reshape(-1)
+    return (weight[qk_rows].contiguous(), bias[qk_rows].contiguous(), weight[v_rows].contiguous(), bias[v_rows].contiguous())
+
+
 class AttentionBlock(nn.Module):
-    def __init__(self, channels, num_heads=1, num_head_channels=-1):
+    def __init__(self, channels, num_heads=1, num_head_channels=-1, use_new_attention_order=False):
         super().__init__()
         self.channels = channels
-        self.num_heads = num_heads if num_head_channels == -1 else channels // num_head_channels
+        if num_head_channels == -1:
+            self.num_heads = num_heads
+        else:
+            if channels % num_head_channels:
+                raise ValueError(f"q,k,v channels {channels} is not divisible by num_head_channels {num_head_channels}")
+            self.num_heads = channels // num_head_channels
+        if self.num_heads < 1 or channels % self.num_heads:
+            raise ValueError(f"attention over {channels} channels does not split into {self.num_heads} heads")
+        self.use_new_attention_order = use_new_attention_order
         self.norm = _normalization(channels)
         self.qkv = nn.Conv1d(channels, channels * 3, 1)
         self.proj_out = _zero(nn.Conv1d(channels, channels, 1))
@@ -103,10 +132,7 @@ class BeatGANsUNetModel(NhwcExecutor):
             return ResBlock(ch, E, m.dropout, out_channels=out, use_zero_module=zero, **kw)
 
         def attn(ch, heads):
-            blk = AttentionBlock(ch, heads, m.num_head_channels)
-            if blk.num_heads != 1:
-                raise NotImplementedError("multi-head BeatGANs attention is not used by the dimension-estimation configs")
-            return blk
+            return AttentionBlock(ch, heads, m.num_head_channels, m.use_new_attention_order)
 
         ch = input_ch = int(mults[0] * self.mc)
         self.input_blocks = nn.ModuleList([Block(nn.Conv2d(m.in_channels, ch, 3, padding=1))])
@@ -195,17 +221,18 @@ class BeatGANsUNetModel(NhwcExecutor):
         return self._conv(h, w1, b1, residual=sc.buf, stats=True, normed=True)
 
     def _attn(self, mod, x, pk):
-        """AttentionBlock._forward (BeatGANsblocks.py:433-443) with QKVAttentionLegacy (:466-491), one head."""
+        """AttentionBlock._forward (BeatGANsblocks.py:433-443) with QKVAttentionLegacy (:466-491) or QKVAttention (:498-526): the head
+        order lives in the packed weights (pack_qkv_heads), the executor sees head-contiguous q | k and v."""
         C = x.C
         n = self._gn_act(x, mod.norm, None)
         key = (id(mod), "qkv")
         if key not in pk["lin"]:
             w = mod.qkv.weight.detach().float().view(3 * C, C)
             b = mod.qkv.bias.detach().float()
-            pk["lin"][key] = (w[:2 * C].contiguous(), b[:2 * C].contiguous(), w[2 * C:].contiguous(), b[2 * C:].contiguous(),
+            pk["lin"][key] = (*pack_qkv_heads(w, b, mod.num_heads, mod.use_new_attention_order),
                               mod.proj_out.weight.detach().float().view(C, C).contiguous(),
                               mod.proj_out.bias.detach().float().contiguous())
-        return self._attention(pk, x, n, mod.norm, *pk["lin"][key], pk["lin"], (id(mod), "attn_scale"))
+        return self._attention(pk, x, n, mod.norm, *pk["lin"][key], pk["lin"], (id(mod), "attn_scale"), heads=mod.num_heads)
 
     def _resample(self, mod, x, pk):
         if mod.up:

@@ -256,11 +256,14 @@ class NhwcExecutor(HipScoreModel):
                         epilogue=_lib.make_epilogue(bias=bias, **ep), act_scale=act_scale)
         return y
 
-    def _attention(self, pk, x, n, gn, wqk, bqk, wv, bv, wo, bo, cache, key, out_scale=1.0):
-        """One head of self-attention over ``n`` = GroupNorm ``gn`` of ``x``: q|k projection (``wqk`` [2C, C], the two stacked), V^T,
-        softmax(q k^T / sqrt(C)) v, output projection, (+ x) * out_scale.  The V bias is added after P.V (the rows of P sum to one),
-        so V^T is produced directly in the K-contiguous layout that product wants.  ``cache[key]``: the operands' power-of-two
-        scales, kept as long as the weights."""
+    def _attention(self, pk, x, n, gn, wqk, bqk, wv, bv, wo, bo, cache, key, out_scale=1.0, heads=1):
+        """Self-attention over ``n`` = GroupNorm ``gn`` of ``x``: q|k projection (``wqk`` [2C, C], the two stacked), V^T,
+        softmax(q k^T / sqrt(D)) v per head, output projection, (+ x) * out_scale.  The V bias is added after P.V (the rows of P sum
+        to one), so V^T is produced directly in the K-contiguous layout that product wants.  ``cache[key]``: the operands' power-of-two
+        scales, kept as long as the weights.  ``heads`` > 1: head h owns rows [h D, (h + 1) D) of each of q, k (the halves of ``wqk``)
+        and v, D = C / heads -- the callers permute their projection into that order at pack time (_attention_heads)."""
+        if heads != 1:
+            return self._attention_heads(pk, x, n, gn, wqk, bqk, wv, bv, wo, bo, cache, key, out_scale, heads)
         B, HW, C = x.buf.shape[0], x.H * x.W, x.C
         pairs = self.pairs_admissible(gn, n.norm[1], transform=False)
         dev = x.buf.device
@@ -286,6 +289,42 @@ class NhwcExecutor(HipScoreModel):
         _lib.softmax_rows(logits, logits, B * HW, HW, scale)
         _lib.gemm(logits, vt, out=mixed, M=HW, N=C, K=HW, lda=HW, ldb=HW, ldc=C, batch=B,
                   stride_a=HW * HW, stride_b=C * HW, stride_c=HW * C, epilogue=_lib.make_epilogue(bias=bv))
+        return self._pointwise(_T(mixed, x.H, x.W, C), wo, bo, residual=x.buf, out_scale=out_scale, stats=True)
+
+    def _attention_heads(self, pk, x, n, gn, wqk, bqk, wv, bv, wo, bo, cache, key, out_scale, heads):
+        """_attention with more than one head.  The projections and the output projection are the single-head block's (the heads are
+        column ranges of their outputs / input).  Where the streaming kernel serves the shape (csrc/attention.hip,
+        attention_heads_kernel: heads of 32 / 64 / 128 channels over a multiple of 64 tokens -- every class measured faster than the
+        per-head form, profiles/attention_heads_bench.txt) the heads run as ONE launch, the logits never written; otherwise (the
+        16-token middle block, other widths, norms not admitted to fp16 pairs, the safe rebuild under IDIFF_NO_PAIRS) as the
+        three-launch form once per head on column views of the same buffers."""
+        B, HW, C = x.buf.shape[0], x.H * x.W, x.C
+        D = C // heads
+        pairs = self.pairs_admissible(gn, n.norm[1], transform=False)
+        dev = x.buf.device
+        qk = torch.empty(B * HW, 2 * C, device=dev, dtype=torch.float32)
+        _lib.gemm_normed(pk, n.buf.view(-1, C), wqk, qk, epilogue=_lib.make_epilogue(bias=bqk), pairs=pairs)
+        vt = torch.empty(B, C, HW, device=dev, dtype=torch.float32)
+        _lib.gemm_weight_times_normed_t(pk, wv, n.buf, vt, B, HW, C, pairs=pairs)
+        mixed = torch.empty(B, HW, C, device=dev, dtype=torch.float32)
+        scale = float(D) ** (-0.5)                # (q * s) . (k * s) with s = D^-1/4 (BeatGANsblocks.py:482, :517)
+        if pairs and _lib.attention_heads_ok(B, HW, heads, D):
+            if key not in cache:
+                gam = float(torch.sqrt((gn.weight.detach().double() ** 2).mean() + (gn.bias.detach().double() ** 2).mean()))
+                cache[key] = (_lib.pairs_scale_from_rows(wqk, bqk, gam), _lib.pairs_scale_from_rows(wv, bv, gam))
+            s_qk, s_v = cache[key]
+            _lib.attention_heads(qk, vt, mixed, B, HW, heads, D, s_qk, s_v, scale, bias_v=bv)
+            return self._pointwise_pairs(pk, _T(mixed, x.H, x.W, C), wo, bo, s_v, residual=x.buf, out_scale=out_scale, stats=True)
+        if D % 4:
+            raise NotImplementedError(f"attention heads of {D} channels: the GEMM takes a head as a column view only where its width "
+                                      "is a multiple of 4")
+        logits = torch.empty(B, HW, HW, device=dev, dtype=torch.float32)
+        for h in range(heads):
+            _lib.gemm(qk[:, h * D:], qk[:, C + h * D:], out=logits, M=HW, N=HW, K=D, lda=2 * C, ldb=2 * C, ldc=HW, batch=B,
+                      stride_a=HW * 2 * C, stride_b=HW * 2 * C, stride_c=HW * HW)
+            _lib.softmax_rows(logits, logits, B * HW, HW, scale)
+            _lib.gemm(logits, vt[:, h * D:(h + 1) * D], out=mixed[..., h * D:], M=HW, N=D, K=HW, lda=HW, ldb=HW, ldc=C, batch=B,
+                      stride_a=HW * HW, stride_b=C * HW, stride_c=HW * C, epilogue=_lib.make_epilogue(bias=bv[h * D:(h + 1) * D]))
         return self._pointwise(_T(mixed, x.H, x.W, C), wo, bo, residual=x.buf, out_scale=out_scale, stats=True)
 
     def _box(self, x, up):

@@ -50,7 +50,7 @@ const char *idiff_variant_flags(void);
  * stream beside the next panel's factorisation; 5 % at D = 12288 when the helper gets a hardware queue of its own, 50 %
  * SLOWER when the runtime maps it onto the caller's queue, which happens once a process has made a few streams),
  * IDIFF_NO_WINO43 (3x3 convolutions on the F(2x2,3x3) kernel instead of F(4x4,3x3)), IDIFF_NO_WINO43H (F(4x4,3x3) with its
- * contractions on the fp32 matrix cores instead of fp16 pairs), IDIFF_NO_FUSED_ATTN (idiff_attention256_ok answers 0), IDIFF_NO_WINO1D (idiff_conv2d_wino1d_ok answers 0),
+ * contractions on the fp32 matrix cores instead of fp16 pairs), IDIFF_NO_FUSED_ATTN (idiff_attention256_ok and idiff_attention_heads_ok answer 0), IDIFF_NO_WINO1D (idiff_conv2d_wino1d_ok answers 0),
  * IDIFF_NO_FUSED_GN (idiff_conv2d_wino1d_gn_ok answers 0: the GroupNorm behind a row-wise convolution stays a launch of its own), IDIFF_NO_PAIRS (idiff_gemm_pairs_ok answers 0: the 1x1
  * projections behind a GroupNorm stay on idiff_gemm_f32's six-product form), IDIFF_PAIRS_MIN_TILES (tests: the number of 128 x 128
  * tiles from which idiff_gemm_pairs_ok answers 1; default 256).
@@ -364,6 +364,20 @@ int idiff_softmax_rows_f32(const float *x, float *y, int64_t rows, int cols, flo
 int idiff_attention256_ok(int B, int tokens, int C);
 int idiff_attention256_f32(const float *qk, int64_t ld_qk, const float *vt, const float *bias_v, const float *s_qk, const float *s_v,
                            float *out, int B, int tokens, int C, float scale, void *stream);
+
+/* Multi-head self-attention in ONE launch with the keys streamed, the logits never leaving the chip (models/BeatGANsblocks.py:466-526:
+ * QKVAttentionLegacy and QKVAttention; the head ORDER of the qkv projection is the caller's row permutation of its weight):
+ *     out[b, i, h D + c] = sum_j softmax_j(q_h[b, i] . k_h[b, j] * scale) v_h[b, j, c]  (+ bias_v[h D + c])
+ * Head-contiguous operands, C = H D: qk [B * tokens, ld_qk] with q of head h in columns [h D, (h + 1) D) and k of head h in
+ * [C + h D, C + (h + 1) D); vt: V^T as [B, C, tokens], row h D + c; out [B * tokens, C].  Arithmetic and s_qk / s_v as
+ * idiff_attention256_f32 (fp16 pairs, three products, fp32 accumulation, fp32 softmax); the softmax runs over chunks of 64 keys with a
+ * running maximum and sum per query.  s |q|, s |k|, s |v| beyond 65504 give non-finite outputs, never finite-and-wrong.
+ * idiff_attention_heads_ok: 1 for D in {32, 64, 128}, H >= 1 with H D <= 1024, tokens a multiple of 64 in [64, 4096], B H <= 2^20;
+ * 0 otherwise and under IDIFF_NO_FUSED_ATTN / IDIFF_NO_PAIRS / IDIFF_NO_SPLIT (the callers then run the three-launch form per head).
+ * The entry point refuses every other shape and launches nothing.  All pointers 16-byte aligned, ld_qk >= 2 C and a multiple of 4. */
+int idiff_attention_heads_ok(int B, int tokens, int H, int D);
+int idiff_attention_heads_f32(const float *qk, int64_t ld_qk, const float *vt, const float *bias_v, const float *s_qk, const float *s_v,
+                              float *out, int B, int tokens, int H, int D, float scale, void *stream);
 
 /* y = act(a * alpha + beta_const) elementwise; covers `2*x - 1` (models/ncsnpp.py:264-266), SiLU/ELU of the
  * time embedding, and -out/std when `rowscale` ([n / inner]) is given: y = act(...) * rowscale[i / inner]. */
