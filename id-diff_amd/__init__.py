@@ -11,7 +11,8 @@ import sys as _sys
 
 __version__ = "0.1.0"
 
-_DROPIN = ("op", "sde_lib", "models", "dim_reduction", "plot_utils", "configs", "lightning_callbacks")
+_DROPIN = ("op", "sde_lib", "models", "dim_reduction", "plot_utils", "configs", "lightning_callbacks",
+           "lightning_data_modules")
 
 
 def install_dropin():

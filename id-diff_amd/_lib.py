@@ -115,6 +115,8 @@ _SIGNATURES = {
     "idiff_tridiag_eigvals_f64": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p]),
     "idiff_knn_workspace_bytes": (c_i64, [c_i, c_i, c_i]),
     "idiff_knn_f32": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p]),
+    "idiff_render_squares_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
+    "idiff_render_gaussians_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -869,3 +871,64 @@ def knn(X, k, workspace=None):
     _check(lib().idiff_knn_f32(X.data_ptr(), N, D, k, _ptr(workspace), 0 if workspace is None else workspace.numel() * 8,
                                dist.data_ptr(), idx.data_ptr(), n_exact.data_ptr(), _stream()), "idiff_knn_f32")
     return dist, idx, n_exact
+
+
+# ------------------------------------------------------------------------------------------- image manifolds
+def _host_table(table, cols, name):
+    """A host table of integers [K, cols] as contiguous int32 numpy (device tensors are refused: the table is checked here, on the host)."""
+    import numpy as np
+    if isinstance(table, torch.Tensor):
+        if table.device.type != "cpu":
+            raise RuntimeError(f"{name}: the table is checked on the host before upload; pass a host array, got a tensor on {table.device}")
+        table = table.numpy()
+    arr = np.asarray(table)
+    if arr.ndim != 2 or arr.shape[1] != cols or arr.shape[0] < 1 or not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError(f"{name}: expected an integer table [K >= 1, {cols}], got {arr.dtype} {tuple(arr.shape)}")
+    return np.ascontiguousarray(arr.astype(np.int64))
+
+
+def _render(entry, values, table, S, out):
+    N, K = values.shape
+    S = int(S)
+    if table.shape[0] != K:
+        raise ValueError(f"{entry}: {table.shape[0]} table rows for {K} columns of per-image values")
+    if out is None:
+        if N * S * S >= 2 ** 31:
+            raise RuntimeError(f"{entry}: N * S * S = {N * S * S} is not below 2^31; render in slabs")
+        out = torch.empty(N, S, S, device=values.device, dtype=torch.float32)
+    _dev(out, "out")
+    if out.numel() != N * S * S or out.device != values.device:
+        raise RuntimeError(f"{entry}: out holds {out.numel()} values on {out.device} for {N} images of {S} x {S} on {values.device}")
+    tab = torch.from_numpy(table.astype("int32")).to(values.device)
+    _check(getattr(lib(), entry)(values.data_ptr(), tab.data_ptr(), out.data_ptr(), N, K, S, _stream()), entry)
+    return out
+
+
+def render_squares(coef, rects, S, out=None):
+    """out [N, S, S] fp32 with out[n, p] = sum_k coef[n, k] [p in square k], a sequential fp32 chain in ascending k (bit-equal to the
+    reference's FixedSquaresManifold).  coef [N, K] CUDA fp32; rects [K, 3] HOST integers (row0, col0, side), checked against the
+    image here, before upload: a square that leaves it is a ValueError and nothing is launched."""
+    _dev(coef, "coef")
+    if coef.ndim != 2:
+        raise RuntimeError(f"render_squares: coef must be [N, K], got {tuple(coef.shape)}")
+    r = _host_table(rects, 3, "render_squares")
+    bad = (r[:, 2] < 1) | (r[:, 0] < 0) | (r[:, 1] < 0) | (r[:, 0] + r[:, 2] > int(S)) | (r[:, 1] + r[:, 2] > int(S))
+    if bad.any():
+        k = int(bad.nonzero()[0][0])
+        raise ValueError(f"render_squares: square {k} (row0, col0, side) = {tuple(int(v) for v in r[k])} leaves the {S} x {S} image")
+    return _render("idiff_render_squares_f32", coef, r, S, out)
+
+
+def render_gaussians(std, centres, S, out=None):
+    """out [N, S, S] fp32: sum_k of Gaussian blobs of standard deviation std[n, k] around centres[k], each image scaled to [0, 1]
+    (the reference's FixedGaussiansManifold; fp64 accumulation, see idiff_render_gaussians_f32).  std [N, K] CUDA fp64; centres
+    [K, 2] HOST integers (row, column), checked against the image here, before upload."""
+    _dev(std, "std", dtype=torch.float64)
+    if std.ndim != 2:
+        raise RuntimeError(f"render_gaussians: std must be [N, K], got {tuple(std.shape)}")
+    c = _host_table(centres, 2, "render_gaussians")
+    bad = ((c < 0) | (c >= int(S))).any(axis=1)
+    if bad.any():
+        k = int(bad.nonzero()[0][0])
+        raise ValueError(f"render_gaussians: centre {k} = {tuple(int(v) for v in c[k])} is outside the {S} x {S} image")
+    return _render("idiff_render_gaussians_f32", std, c, S, out)

@@ -469,6 +469,23 @@ int64_t idiff_knn_workspace_bytes(int N, int D, int k);
 int idiff_knn_f32(const float *X, int N, int D, int k, void *workspace, int64_t workspace_bytes, double *dist, int64_t *idx,
                   int *n_exact_rows, void *stream);
 
+/* ------------------------------------------------------------------ image manifolds of known dimension */
+
+/* The two fixed image manifolds of lightning_data_modules/SyntheticDataset.py:81-183, one workgroup per image, out
+ * [N, S, S] fp32 (16-byte aligned).  Both need S a multiple of 4 in [4, 64], 1 <= K <= 1024 and N * S * S < 2^31
+ * (IDIFF_EINVAL otherwise, nothing launched; N = 0 is a no-op).  The tables are the caller's: the kernels index pixels
+ * only, so a rectangle or centre outside the image cannot make them leave `out`, but the Python wrapper refuses one.
+ *
+ * squares: rects [K, 3] int32 = (row0, col0, side) of square k, coef [N, K] fp32.  out[n, p] = sum_k coef[n, k] [p in rect_k]
+ * as a sequential fp32 chain in ascending k from +0: bit-equal to FixedSquaresManifold for coef = fl32 of its draws.
+ *
+ * gaussians: centres [K, 2] int32 = (row, column), std [N, K] fp64.  v[i, j] = sum_k exp(d_k ((i - row_k)^2 + (j - col_k)^2))
+ * / (sqrt(2 pi) std_k), d_k = -1 / (2 std_k^2), accumulated in fp64 and rounded once to fp32; out = (v - min v) / (max v - min v)
+ * in fp32 with a correctly rounded division (FixedGaussiansManifold works in fp32 throughout: equal within
+ * (K + 4) 2^-24 max / (max - min), not bit for bit). */
+int idiff_render_squares_f32(const float *coef, const int *rects, float *out, int N, int K, int S, void *stream);
+int idiff_render_gaussians_f32(const double *std, const int *centres, float *out, int N, int K, int S, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
