@@ -113,6 +113,8 @@ _SIGNATURES = {
     "idiff_symtridiag_f64": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_p]),
     "idiff_symtridiag_plan": (c_i, [c_i]),
     "idiff_tridiag_eigvals_f64": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p]),
+    "idiff_sym_lowvecs_scratch_doubles": (c_i64, [c_i, c_i]),
+    "idiff_sym_lowvecs_f64": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "idiff_knn_workspace_bytes": (c_i64, [c_i, c_i, c_i]),
     "idiff_knn_f32": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p]),
     "idiff_render_squares_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
@@ -850,6 +852,43 @@ def sym_eigvals(G):
            "idiff_symtridiag_f64")
     _check(lib().idiff_tridiag_eigvals_f64(diag.data_ptr(), offd.data_ptr(), 1, D, eig.data_ptr(), _stream()), "idiff_tridiag_eigvals_f64")
     return eig
+
+
+TANGENT_MAX = 128      # widest basis idiff_sym_lowvecs_f64 serves
+
+
+def sym_lowvecs(G, k):
+    """``(T, ritz, resid)`` of a symmetric positive semi-definite fp64 matrix G [D, D]: T [D, k] fp64 with orthonormal columns
+    spanning the invariant subspace of the k smallest eigenvalues, ritz [k] fp64 ascending (column i of T belongs to ritz[i]),
+    resid a 0-d fp64 tensor |G T - T diag(ritz)|_F.  1 <= k <= 128, k < D.  G is only read; trouble (G not positive
+    semi-definite to rounding, a NaN in G) comes back as NaN in all three.  No host sync."""
+    _dev(G, "G", dtype=torch.float64)
+    if G.ndim != 2 or G.shape[0] != G.shape[1]:
+        raise RuntimeError(f"sym_lowvecs: G must be [D, D], got {tuple(G.shape)}")
+    D, k = G.shape[0], int(k)
+    scratch = torch.empty(max(1, lib().idiff_sym_lowvecs_scratch_doubles(D, k)), dtype=torch.float64, device=G.device)
+    ok = 1 <= k < D
+    T = torch.empty((D, k) if ok else (1,), dtype=torch.float64, device=G.device)
+    ritz = torch.empty(k if ok else 1, dtype=torch.float64, device=G.device)
+    resid = torch.empty((), dtype=torch.float64, device=G.device)
+    _check(lib().idiff_sym_lowvecs_f64(G.data_ptr(), D, k, T.data_ptr(), ritz.data_ptr(), resid.data_ptr(), scratch.data_ptr(), _stream()),
+           "idiff_sym_lowvecs_f64")
+    return T, ritz, resid
+
+
+def tangent_basis(S, k):
+    """The estimated tangent space at a point from its score matrix S [M, D] (CUDA fp32): the k right singular vectors of the
+    column-centred S with the SMALLEST singular values, through the fp64 Gram matrix the spectrum is computed from
+    (idiff_colmean_f64 -> idiff_centered_gram_f64 -> sym_lowvecs).  Returns what ``sym_lowvecs`` returns; ritz[i] is the
+    square of the singular value that column i of T belongs to."""
+    _dev(S, "scores")
+    if S.ndim != 2 or S.shape[0] < 1:
+        raise RuntimeError(f"tangent_basis: scores must be [M >= 1, D], got {tuple(S.shape)}")
+    M, D = S.shape
+    mean = torch.empty(D, dtype=torch.float64, device=S.device)
+    scratch = torch.empty(32 * D, dtype=torch.float64, device=S.device)
+    _check(lib().idiff_colmean_f64(S.data_ptr(), 1, M, D, mean.data_ptr(), scratch.data_ptr(), _stream()), "idiff_colmean_f64")
+    return sym_lowvecs(centered_gram(S, mean), k)
 
 
 # ------------------------------------------------------------------------------------------- k nearest neighbours

@@ -358,6 +358,77 @@ def checked_spectra(spectra):
     return host
 
 
+def tangent_width(singular_values, ambient_dim, cap=_lib.TANGENT_MAX):
+    """``(d, k)`` for one point, on the host: d its ID by the rule every driver uses (``estimate_dim``; -1 with fewer than three
+    singular values) and k the width of the tangent basis to ask for -- d itself, or None where no basis is served: d < 1,
+    d above ``cap`` (the widest basis idiff_sym_lowvecs_f64 computes) or d not below the ambient dimension."""
+    d = estimate_dim(list(singular_values)) if len(singular_values) >= 3 else -1
+    return d, (d if 1 <= d <= cap and d < ambient_dim else None)
+
+
+def _tangent_refused(config, world):
+    """return_tangent is a one-rank mode: bases have a different width at every point, and their exchange is not built."""
+    if world > 1 or str(config.get('dim_estimation.shard', 'points')) == 'rows':
+        raise NotImplementedError("return_tangent / dim_estimation.save_tangent needs a single rank and dim_estimation.shard = "
+                                  f"'points' (got world size {world}, shard = {config.get('dim_estimation.shard', 'points')!r}): "
+                                  "the exchange of variable-width bases between ranks is not implemented")
+
+
+def _points_with_tangent(config, builder, points, point_seed, device):
+    """The loop of ``get_manifold_dimension(return_tangent=True)``: every point (every launch group of vector points) is taken
+    to completion -- score matrix, spectrum, ID on the host, ``_lib.tangent_basis(S, d)``, S released -- on ONE stream: the width
+    of the basis is known only once the spectrum has reached the host, so nothing of the next point is queued under it.  Score
+    matrices and spectra come from the same launches as without the flag.  -> (spectra [P, D] on the device, dims, tangent)."""
+    import warnings
+    pipe = SpectrumPipeline(device, overlap=False)
+    spectra, dims, tangent, capped = [], [], [], 0
+
+    def finish(S_points, svs, ids):
+        nonlocal capped
+        host = checked_spectra(svs)
+        for S, sv, p in zip(S_points, host, ids):
+            x, b = points[p]
+            d, k = tangent_width(sv[:min(batching(tuple(x.shape), b)[2], x.numel())].tolist(), x.numel())
+            dims.append(d)
+            capped += d > _lib.TANGENT_MAX
+            if k is None:
+                tangent.append(None)
+                continue
+            T, _, resid = _lib.tangent_basis(S, k)
+            if not math.isfinite(float(resid)):
+                raise RuntimeError(f"point {p}: the tangent basis of width {k} came back non-finite (the Gram matrix of the scores is "
+                                   "not positive semi-definite to rounding, or holds non-finite values)")
+            tangent.append(T.to(torch.float32).cpu().numpy())
+        spectra.extend(svs)
+
+    with torch.no_grad():
+        ids_all = list(range(len(points)))
+        small = points[0][0].numel() <= 4096 and len({b for _, b in points}) == 1
+        if small:
+            rows = batching(tuple(points[0][0].shape), points[0][1])[2]
+            group = max(1, min(len(ids_all), int(config.get('dim_estimation.points_per_launch', max(1, 131072 // rows)))))
+            for lo in range(0, len(ids_all), group):
+                ids = ids_all[lo:lo + group]
+                S = build_many(builder, [points[p][0].to(device) for p in ids], points[ids[0]][1], [point_seed(p) for p in ids])
+                pipe.submit(S)
+                finish(S, pipe.results()[0], ids)
+                del S
+        else:
+            for p in ids_all:
+                x, batchsize = points[p]
+                S = builder.build(x.to(device), batchsize, seed=point_seed(p))
+                if not bool(torch.isfinite(S).all()):
+                    warn_non_finite_point()
+                    S = builder.build(x.to(device), batchsize, seed=point_seed(p), safe=True)
+                pipe.submit(S)
+                finish([S], torch.stack(pipe.results()), [p])
+                del S
+    if capped:
+        warnings.warn(f"id-diff_amd: {capped} point(s) have an intrinsic dimension above {_lib.TANGENT_MAX}, the widest tangent "
+                      "basis that is computed: their entry of `tangent` is None")
+    return torch.stack(spectra), dims, tangent
+
+
 def build_many(builder, xs, batchsize, seeds):
     """S [P, M, D] for P small (vector) points with ONE score_fn call over all P*M rows: the k-sphere workload is
     launch-bound one point at a time (M = 1501 rows of a 7-layer MLP), so points are batched (BASELINE config 2)."""
@@ -414,13 +485,28 @@ def collect_points(loader, num_datapoints):
     return pts
 
 
-def get_manifold_dimension(config, name=None, return_svd=False, return_dims=False):
+def get_manifold_dimension(config, name=None, return_svd=False, return_dims=False, return_tangent=False):
     """Drop-in for dim_reduction.py:116-215.  ``return_dims=True`` (not in the reference; needs ``return_svd``) also
     returns the integer ID of every point, computed by the reference's rule on the rank that owns the point and gathered
-    as int32 in the same collective as the spectra."""
+    as int32 in the same collective as the spectra.
+
+    ``return_tangent=True`` (with ``return_svd``; the reference has the same information in the ``v`` it drops at :197) appends
+    ``tangent`` to what is returned: one entry per point, a float32 numpy array [D, d] whose orthonormal columns span the
+    estimated tangent space -- the right singular vectors of the d smallest singular values, d that point's ID -- or None where
+    d < 1 or d > 128 (one warning names the cap).  In this mode every point is handled to completion on one stream (score
+    matrix, spectrum, ID on the host, ``_lib.tangent_basis``): there is NO side-stream overlap of spectrum and score
+    evaluations, and it needs a single rank with ``dim_estimation.shard = 'points'`` (NotImplementedError otherwise).  The
+    singular values and dims are those of a call without the flag, bit for bit.  Without ``return_svd`` the config key
+    ``dim_estimation.save_tangent`` (default False) selects the mode and writes ``<name>_tangent.pkl`` =
+    ``{'tangent': [...], 'dims': [...]}`` beside the unchanged ``<name>.pkl``."""
     log_path, log_name = config.logging.log_path, config.logging.log_name
     save_path = os.path.join(log_path, log_name, 'svd')
     rank, world = parallel.rank_world()
+    if return_tangent and not return_svd:
+        raise ValueError("return_tangent needs return_svd=True (set dim_estimation.save_tangent to have the bases written to disk)")
+    save_tangent = not return_svd and bool(config.get('dim_estimation.save_tangent', False))
+    if return_tangent or save_tangent:
+        _tangent_refused(config, world)
     if rank == 0 and not return_svd:
         Path(save_path).mkdir(parents=True, exist_ok=True)
 
@@ -432,10 +518,13 @@ def get_manifold_dimension(config, name=None, return_svd=False, return_dims=Fals
     if not points:                       # num_datapoints <= 1: the reference's loop body never runs (:159-164)
         info = {'singular_values': []}
         if return_svd:
-            return info
+            return ((info, [], []) if return_dims else (info, [])) if return_tangent else info
         if rank == 0:
             with open(os.path.join(save_path, f'{name}.pkl'), 'wb') as f:
                 pickle.dump(info, f)
+            if save_tangent:
+                with open(os.path.join(save_path, f'{name}_tangent.pkl'), 'wb') as f:
+                    pickle.dump({'tangent': [], 'dims': []}, f)
         return None
     builder = ScoreMatrixBuilder(score_fn, pl_module.sde, pl_module.sampling_eps, device,
                                  config.get('dim_estimation.inflight_rows', None))
@@ -457,6 +546,18 @@ def get_manifold_dimension(config, name=None, return_svd=False, return_dims=Fals
         if rank == 0:
             with open(os.path.join(save_path, f'{name}.pkl'), 'wb') as f:
                 pickle.dump(info, f)
+        return None
+
+    if return_tangent or save_tangent:
+        local, dims, tangent = _points_with_tangent(config, builder, points, point_seed, device)
+        keep = [min(batching(tuple(x.shape), b)[2], x.numel()) for x, b in points]
+        info = {'singular_values': [s[:k].tolist() for s, k in zip(checked_spectra(local), keep)]}
+        if return_svd:
+            return (info, dims, tangent) if return_dims else (info, tangent)
+        with open(os.path.join(save_path, f'{name}.pkl'), 'wb') as f:
+            pickle.dump(info, f)
+        with open(os.path.join(save_path, f'{name}_tangent.pkl'), 'wb') as f:
+            pickle.dump({'tangent': tangent, 'dims': dims}, f)
         return None
 
     mine = parallel.my_points(len(points), rank, world)

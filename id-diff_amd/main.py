@@ -3,6 +3,10 @@
 
 Run it from the repo root as ``python id-diff_amd/main.py ...`` or, for several GPUs of one node,
 ``python -m torch.distributed.run --nproc-per-node N id-diff_amd/main.py ...``.
+
+``--mode manifold_dimension`` with the config key ``dim_estimation.save_tangent = True`` (not in the reference; default False, one
+GPU only) also writes ``<log_path>/<log_name>/svd/<log_name>_tangent.pkl`` = ``{'tangent': [...], 'dims': [...]}``: per point the
+[D, d] float32 basis of its estimated tangent space, or None (``dim_reduction.get_manifold_dimension``).
 """
 import argparse
 import os

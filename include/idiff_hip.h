@@ -454,6 +454,21 @@ int idiff_symtridiag_f64(double *G, int P, int D, double *diag, double *offdiag,
 int idiff_symtridiag_plan(int D);
 int idiff_tridiag_eigvals_f64(const double *diag, const double *offdiag, int P, int D, double *eig, void *stream);
 
+/* The tangent side of the spectrum: T [D, k] row-major with orthonormal columns spanning the invariant subspace of the k SMALLEST
+ * eigenvalues of the symmetric positive semi-definite G [D, D] (both triangles), ritz [k] the Ritz values of G on it (ascending,
+ * column i of T belongs to ritz[i]) and resid [1] = |G T - T diag(ritz)|_F, evaluated from the T that is returned.  At small t
+ * the score vectors span the normal space, so for k = the point's intrinsic dimension T is the estimated tangent space (the
+ * `v` the reference's torch.linalg.svd returns and drops, dim_reduction.py:197) and its orthogonal complement the normal space.
+ * Method: Cholesky of G + eps I, eps = 8 D 2^-53 max_i G_ii (blocked, trailing updates on v_mfma_f64_16x16x4), four steps of
+ * inverse subspace iteration from a fixed Philox block (the same result on every call), each followed by CholeskyQR2, then
+ * Rayleigh-Ritz with a cyclic Jacobi eigensolver of the k x k projection.  The contraction per step is lambda_k / lambda_k+1:
+ * the gap the ID rule detects.  G is only read (the factor lives in the scratch).  A non-positive pivot -- G not positive
+ * semi-definite to rounding, or a start block that lost rank -- and a NaN in G turn T, ritz and resid into NaN; no input can hang
+ * the call.  Needs 1 <= k <= 128 and k < D (IDIFF_EINVAL otherwise, as for null pointers; nothing is launched).  scratch:
+ * idiff_sym_lowvecs_scratch_doubles(D, k) doubles (0 for arguments the call refuses).  No host synchronisation. */
+int64_t idiff_sym_lowvecs_scratch_doubles(int D, int k);
+int idiff_sym_lowvecs_f64(double *G, int D, int k, double *T, double *ritz, double *resid, double *scratch, void *stream);
+
 /* ------------------------------------------------------------------ exact k nearest neighbours */
 
 /* Replaces `NearestNeighbors(n_neighbors=k+1, algorithm='ball_tree').fit(X).kneighbors(X)` of mle.py:19-20 / :47-48 /
