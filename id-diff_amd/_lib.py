@@ -759,21 +759,30 @@ _FALLBACKS = (("IDIFF_CHASE_WAVEFRONT", "bulge chasing one launch per wavefront"
               ("IDIFF_TRIDIAG_ONESTAGE", "one-stage Householder sweep"))
 
 
+def solve_with_fallbacks(solve, any_rank=None, log=None):
+    """``solve()`` under each fallback form in turn, on the current stream, until one comes back without NaN; raises when none
+    does.  Synchronises (the rare path).  ``any_rank``: with a process group, a callable that reduces the failure flag (a bool
+    tensor -> a Python bool, true if it is set on any rank), so that every rank runs the same forms and returns the same result.
+    ``log`` takes the one-line account of the form that served (default ``warnings.warn``)."""
+    import warnings
+    for name, what in _FALLBACKS:
+        with thread_option(name, 1):                       # this thread's launches only
+            out = solve()
+        failed = torch.isnan(out).any()
+        if not (any_rank(failed) if any_rank is not None else bool(failed)):
+            msg = f"id-diff_amd: the two-stage eigensolver reported a failure; spectrum re-solved with {what} ({name})"
+            (log or warnings.warn)(msg)
+            return out
+    raise RuntimeError("the eigensolver reported a failure (NaN) in all of its three forms: two-stage with the systolic chase, with "
+                       "the wavefront chase, and the one-stage sweep")
+
+
 def resolve_failed_spectrum(S, full=False, log=None):
     """``spectrum(S)`` came back with NaN: solve the same matrices again with the fallback forms of the eigensolver, on
     the current stream.  Synchronises (the rare path).  Raises if S itself is non-finite or every form fails."""
-    import warnings
     if not bool(torch.isfinite(S).all()):
         raise RuntimeError("the score matrix holds non-finite values (NaN / inf score vectors): no spectrum exists")
-    for name, what in _FALLBACKS:
-        with thread_option(name, 1):                       # this thread's launches only
-            sv = spectrum(S, full=full)
-        if not bool(torch.isnan(sv).any()):
-            msg = f"id-diff_amd: the two-stage eigensolver reported a failure; spectrum re-solved with {what} ({name})"
-            (log or warnings.warn)(msg)
-            return sv
-    raise RuntimeError("the spectrum kernels reported a failure (NaN singular values) and so did the wavefront chase and the "
-                       "one-stage sweep")
+    return solve_with_fallbacks(lambda: spectrum(S, full=full), log=log)
 
 
 # ---- the stages of the spectrum, for the row-sharded single-point pipeline (dim_reduction.row_sharded_spectrum)

@@ -19,6 +19,8 @@ What is different, by design for MI355X:
   neither on how points are distributed over GPUs nor on the launch-set size; points are sharded round-robin over the ranks of the process group and
   the spectra are combined by one all-gather (parallel.py).
 """
+import contextlib
+import dataclasses
 import math
 import os
 import pickle
@@ -101,35 +103,59 @@ class ScoreMatrixBuilder:
         if row_range is not None and noise is None and seed is None:
             raise RuntimeError("a row range needs position-keyed noise: pass `seed` or explicit `noise`")
         if noise is None and seed is not None and D % 4:
-            # the in-kernel Philox stream writes 16-byte groups (D % 4 == 0).  Other widths draw the point's WHOLE noise
-            # matrix from a generator keyed by the point seed and slice it: still a function of (seed, row, column) only,
-            # whatever the launch-set size, the row range or the number of ranks
-            noise = torch.randn(rows, D, device=self.device, dtype=torch.float32,
-                                generator=torch.Generator(device=self.device).manual_seed(int(seed) & 0x7FFFFFFFFFFFFFFF))
+            noise = self._seeded_noise(rows, D, seed)
         S = torch.empty(r_hi - r_lo, D, device=self.device, dtype=torch.float32)
         step = self.rows_per_launch(rows, D, vector=x.ndim == 1)
         xf = x.reshape(-1).contiguous()
-        nsets = -(-(r_hi - r_lo) // step)
-        if (self.concurrent_sets > 1 and nsets > 1 and torch.device(self.device).type == "cuda" and self._warmed
+        workers, cur = (), None
+        if (self.concurrent_sets > 1 and r_hi - r_lo > step and torch.device(self.device).type == "cuda" and self._warmed
                 and (noise is not None or seed is not None)):      # torch-generator draws stay in sequential order
-            return self._build_concurrent(x, xf, S, r_lo, r_hi, step, D, t, noise, seed)
+            # the launch sets of the point dealt round-robin to ``concurrent_sets`` worker streams; the caller's stream waits
+            # for all of them before S is handed back
+            if self._workers is None or len(self._workers) != self.concurrent_sets:
+                self._workers = [torch.cuda.Stream(device=self.device) for _ in range(self.concurrent_sets)]
+            workers, cur = self._workers, torch.cuda.current_stream()
+            for w in workers:
+                w.wait_stream(cur)
         self._warmed = True     # the first point runs on one stream: filter banks and constants are made lazily, once
-        for lo in range(r_lo, r_hi, step):
+        for i, lo in enumerate(range(r_lo, r_hi, step)):
             n = min(step, r_hi - lo)
-            vec_t = torch.full((n,), float(t), device=self.device, dtype=torch.float32)
-            mean_unit, std = self.sde.marginal_prob(torch.ones((), device=self.device), vec_t)
-            coeff = None if mean_unit.ndim == 0 else mean_unit.reshape(-1).contiguous()
-            batch = torch.empty(n, D, device=self.device, dtype=torch.float32)
-            if noise is None and seed is not None:
-                _lib.perturb_randn(xf, std.contiguous(), coeff, batch, n, D, lo, seed)
+            with torch.cuda.stream(workers[i % len(workers)]) if workers else contextlib.nullcontext():
+                batch, vec_t = self._perturbed([xf], t, lo, n, noise=None if noise is None else [noise],
+                                               seeds=None if seed is None else [seed], generator=generator)
+                self._score_into(S[lo - r_lo:lo - r_lo + n], batch.view(n, *x.shape), vec_t)
+        for w in workers:
+            cur.wait_stream(w)
+        return S
+
+    def _seeded_noise(self, rows, D, seed):
+        """The in-kernel Philox stream writes 16-byte groups (D % 4 == 0).  Other widths draw the point's WHOLE noise matrix
+        [rows, D] from a generator keyed by the point seed and slice it: still a function of (seed, row, column) only, whatever
+        the launch-set size, the row range or the number of ranks."""
+        return torch.randn(rows, D, device=self.device, dtype=torch.float32,
+                           generator=torch.Generator(device=self.device).manual_seed(int(seed) & 0x7FFFFFFFFFFFFFFF))
+
+    def _perturbed(self, xfs, t, lo, n, noise=None, seeds=None, generator=None):
+        """Rows [lo, lo + n) of the noise matrices of the P points ``xfs`` (flat, [D] each), perturbed at time ``t``:
+        (batch [P, n, D], vec_t [n]); the level's std and mean coefficient are computed once for all P.  One noise source, in
+        ``build``'s order of precedence: ``noise`` (per point its whole matrix), ``seeds`` (per point, in-kernel Philox: D % 4 == 0),
+        ``generator``."""
+        P, D = len(xfs), xfs[0].numel()
+        vec_t = torch.full((n,), float(t), device=self.device, dtype=torch.float32)
+        mean_unit, std = self.sde.marginal_prob(torch.ones((), device=self.device), vec_t)
+        coeff = None if mean_unit.ndim == 0 else mean_unit.reshape(-1).contiguous()
+        std = std.contiguous()
+        batch = torch.empty(P, n, D, device=self.device, dtype=torch.float32)
+        for i, xf in enumerate(xfs):
+            if noise is None and seeds is not None:
+                _lib.perturb_randn(xf, std, coeff, batch[i], n, D, lo, seeds[i])
             else:
                 if noise is not None:
-                    z = noise[lo:lo + n].reshape(n, D).contiguous()
+                    z = noise[i][lo:lo + n].reshape(n, D).contiguous()
                 else:
                     z = torch.randn(n, D, device=self.device, dtype=torch.float32, generator=generator)
-                _lib.perturb(xf, z, std.contiguous(), coeff, batch, n, D)
-            self._score_into(S[lo - r_lo:lo - r_lo + n], batch.view(n, *x.shape), vec_t)
-        return S
+                _lib.perturb(xf, z, std, coeff, batch[i], n, D)
+        return batch, vec_t
 
     def _score_into(self, rows, batch, vec_t):
         """Scores of ``batch`` into ``rows`` (a row block of S): written there by the network's last kernel when the model takes an
@@ -139,29 +165,21 @@ class ScoreMatrixBuilder:
         else:
             rows.copy_(self.score_fn(batch, vec_t).reshape(rows.shape))
 
-    def _build_concurrent(self, x, xf, S, r_lo, r_hi, step, D, t, noise, seed):
-        """The launch sets of one point dealt round-robin to ``concurrent_sets`` worker streams; the caller's stream waits
-        for all of them before S is handed back."""
-        cur = torch.cuda.current_stream()
-        if self._workers is None or len(self._workers) != self.concurrent_sets:
-            self._workers = [torch.cuda.Stream(device=self.device) for _ in range(self.concurrent_sets)]
-        for w in self._workers:
-            w.wait_stream(cur)
-        for i, lo in enumerate(range(r_lo, r_hi, step)):
-            n = min(step, r_hi - lo)
-            with torch.cuda.stream(self._workers[i % len(self._workers)]):
-                vec_t = torch.full((n,), float(t), device=self.device, dtype=torch.float32)
-                mean_unit, std = self.sde.marginal_prob(torch.ones((), device=self.device), vec_t)
-                coeff = None if mean_unit.ndim == 0 else mean_unit.reshape(-1).contiguous()
-                batch = torch.empty(n, D, device=self.device, dtype=torch.float32)
-                if noise is None:
-                    _lib.perturb_randn(xf, std.contiguous(), coeff, batch, n, D, lo, seed)
-                else:
-                    _lib.perturb(xf, noise[lo:lo + n].reshape(n, D).contiguous(), std.contiguous(), coeff, batch, n, D)
-                self._score_into(S[lo - r_lo:lo - r_lo + n], batch.view(n, *x.shape), vec_t)
-        for w in self._workers:
-            cur.wait_stream(w)
-        return S
+
+@dataclasses.dataclass(slots=True)
+class _Pending:
+    """A spectrum that has been launched.  ``S`` is held until the failure flag has been read -- a flagged spectrum is solved again
+    from it -- and released then (None marks an entry that ``_reap`` is done with)."""
+    sv: torch.Tensor
+    S: torch.Tensor
+    flag: torch.Tensor        # pinned host bool[1]: NaN in sv
+    done: object              # event behind the flag's copy
+    rebuild: object           # callable -> this point's S again on the safe route, or None
+
+
+def _rank0_log():
+    """``log`` for the eigensolver's fallback walk: the warning on rank 0, silence on the others."""
+    return None if parallel.rank_world()[0] == 0 else (lambda msg: None)
 
 
 class SpectrumPipeline:
@@ -182,8 +200,8 @@ class SpectrumPipeline:
         # evaluations instead of beside them (+35 ms per point under torch.distributed.run, same kernels, same durations).
         prio = int(os.environ.get("IDIFF_SIDE_STREAM_PRIORITY", "-1"))
         self.side = torch.cuda.Stream(device=device, priority=prio) if overlap else None
-        self.pending = []         # [sv, S or None, pinned failure flag, event after the flag copy, rebuild]: S is held until the flag is read
-        self.deferred = None      # (S, ready event) of the last submitted point, not yet enqueued
+        self.pending = []         # _Pending, in submit order
+        self.deferred = None      # (S, ready event, rebuild) of the last submitted point, not yet enqueued
         self.resolved = 0         # spectra that needed a fallback form of the eigensolver (fail-soft, see _reap)
         self.rebuilt = 0          # points whose score matrix was non-finite on the default route and was built again on the safe one
 
@@ -201,7 +219,7 @@ class SpectrumPipeline:
             done.record()
         if self.side is not None:
             S.record_stream(self.side)                   # keep S alive until the side stream is done with it
-        self.pending.append([sv, S, flag, done, rebuild])
+        self.pending.append(_Pending(sv, S, flag, done, rebuild))
 
     def _reap(self, block):
         """Reads the failure flags of the spectra that have completed (all of them with ``block``).  A flagged spectrum is
@@ -209,30 +227,29 @@ class SpectrumPipeline:
         (``_lib.resolve_failed_spectrum``: wavefront chase, then the one-stage sweep) in this process; only a matrix
         that defeats all three, or holds non-finite scores, raises."""
         for entry in self.pending:
-            if entry[1] is None:
+            if entry.S is None:
                 continue
             if block:
-                entry[3].synchronize()
-            elif not entry[3].query():
+                entry.done.synchronize()
+            elif not entry.done.query():
                 break                                    # in stream order: later ones are not done either
-            if bool(entry[2][0]):
+            if bool(entry.flag[0]):
                 stream = self.side if self.side is not None else torch.cuda.current_stream()
-                S = entry[1]
-                if entry[4] is not None and not bool(torch.isfinite(S).all()):
+                S = entry.S
+                if entry.rebuild is not None and not bool(torch.isfinite(S).all()):
                     # not the eigensolver: the score matrix itself is non-finite.  One re-run of the point on the range-unlimited
                     # route (ScoreMatrixBuilder.build(safe=True)), on the caller's stream like every build, before that becomes an error
                     warn_non_finite_point()
-                    S = entry[4]()
+                    S = entry.rebuild()
                     self.rebuilt += 1
                     torch.cuda.current_stream().synchronize()   # the rare path: S (and any filter bank packed for it) is complete
                     with torch.cuda.stream(stream):
-                        entry[0] = _lib.spectrum(S, full=True)
+                        entry.sv = _lib.spectrum(S, full=True)
                 with torch.cuda.stream(stream):
-                    if bool(torch.isnan(entry[0]).any()):
-                        entry[0] = _lib.resolve_failed_spectrum(S, full=True,
-                                                                log=None if parallel.rank_world()[0] == 0 else (lambda msg: None))
+                    if bool(torch.isnan(entry.sv).any()):
+                        entry.sv = _lib.resolve_failed_spectrum(S, full=True, log=_rank0_log())
                         self.resolved += 1
-            entry[1] = entry[4] = None
+            entry.S = entry.rebuild = None
 
     def submit(self, S, rebuild=None):
         """``rebuild``: a callable returning this point's S again on the safe route (see ``_reap``); without it a non-finite S raises."""
@@ -254,7 +271,7 @@ class SpectrumPipeline:
         self._reap(block=True)
         if self.side is not None:
             torch.cuda.current_stream().wait_stream(self.side)
-        out, self.pending = [e[0] for e in self.pending], []
+        out, self.pending = [e.sv for e in self.pending], []
         return out
 
 
@@ -307,44 +324,28 @@ def row_sharded_spectrum(S_local, total_rows, ops=None, block_rows=None, rebuild
             G[r0:r1, c0:].copy_(staging)
         return symmetrize(G)
 
+    def any_rank(flag):
+        """A failure flag (bool tensor), reduced (MAX) over the ranks so that EVERY rank takes the same branch even when only one
+        device's eigensolve failed (a stalled chase is a property of one device, not of G)."""
+        flag = flag.to(torch.int32).reshape(1)
+        if grouped:
+            torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MAX)
+        return bool(flag.item())
+
     eig = eigvals(reduced_gram())                                     # the eigensolver overwrites its input
-    if ops is None:
-        # fail soft.  The failure flag is reduced (MAX) over the ranks so that EVERY rank takes the same branch even when
-        # only one device's eigensolve failed (a stalled chase is a property of one device, not of G); no copy of G is
-        # kept for this rare path -- it is rebuilt (1.2 GB of fp64 at D = 12288 otherwise sat beside G on every call).
-        failed = torch.isnan(eig).any().to(torch.int32).reshape(1)
-        if grouped:
-            torch.distributed.all_reduce(failed, op=torch.distributed.ReduceOp.MAX)
-        if bool(failed.item()):
-            if rebuild is not None:
-                bad = (~torch.isfinite(S_local).all()).to(torch.int32).reshape(1)
-                if grouped:
-                    torch.distributed.all_reduce(bad, op=torch.distributed.ReduceOp.MAX)
-                if bool(bad.item()):                         # the same branch on every rank: the flag is reduced
-                    warn_non_finite_point()
-                    return row_sharded_spectrum(rebuild(), total_rows, ops=ops, block_rows=block_rows, rebuild=None)
-            eig = _resolve_failed_eigvals(reduced_gram, eigvals, grouped)
+    if ops is None and any_rank(torch.isnan(eig).any()):
+        # fail soft: the policy of SpectrumPipeline._reap, every branch taken by all ranks together
+        if rebuild is not None and any_rank(~torch.isfinite(S_local).all()):
+            warn_non_finite_point()
+            return row_sharded_spectrum(rebuild(), total_rows, ops=ops, block_rows=block_rows, rebuild=None)
+        # no copy of G was kept for this rare path (1.2 GB of fp64 at D = 12288 otherwise sat beside G on every call): it is built
+        # again, and once more for every further form, since the solver overwrites it
+        G = reduced_gram()
+        if not bool(torch.isfinite(G).all()):
+            raise RuntimeError("the Gram matrix holds non-finite values (NaN / inf score vectors): no spectrum exists")
+        fresh = [G]
+        eig = _lib.solve_with_fallbacks(lambda: eigvals(fresh.pop() if fresh else reduced_gram()), any_rank=any_rank, log=_rank0_log())
     return eig.clamp_min(0.0).sqrt().flip(0).to(torch.float32)
-
-
-def _resolve_failed_eigvals(make_gram, eigvals, grouped=False):
-    """The slower eigensolver forms in turn, on a freshly built Gram matrix each (the solver overwrites it); with a process
-    group every rank runs the same form and the per-form failure flag is reduced, so all ranks return the same spectrum."""
-    import warnings
-    G = make_gram()
-    if not bool(torch.isfinite(G).all()):
-        raise RuntimeError("the Gram matrix holds non-finite values (NaN / inf score vectors): no spectrum exists")
-    for i, (name, what) in enumerate(_lib._FALLBACKS):
-        with _lib.thread_option(name, 1):                  # this thread's launches only
-            eig = eigvals(G if i == 0 else make_gram())
-        failed = torch.isnan(eig).any().to(torch.int32).reshape(1)
-        if grouped:
-            torch.distributed.all_reduce(failed, op=torch.distributed.ReduceOp.MAX)
-        if not bool(failed.item()):
-            if parallel.rank_world()[0] == 0:
-                warnings.warn(f"id-diff_amd: the two-stage eigensolver reported a failure; re-solved with {what} ({name})")
-            return eig
-    raise RuntimeError("the eigensolver reported a failure (NaN eigenvalues) in all of its three forms")
 
 
 def checked_spectra(spectra):
@@ -374,55 +375,70 @@ def _tangent_refused(config, world):
                                   "the exchange of variable-width bases between ranks is not implemented")
 
 
-def _points_with_tangent(config, builder, points, point_seed, device):
-    """The loop of ``get_manifold_dimension(return_tangent=True)``: every point (every launch group of vector points) is taken
-    to completion -- score matrix, spectrum, ID on the host, ``_lib.tangent_basis(S, d)``, S released -- on ONE stream: the width
-    of the basis is known only once the spectrum has reached the host, so nothing of the next point is queued under it.  Score
-    matrices and spectra come from the same launches as without the flag.  -> (spectra [P, D] on the device, dims, tangent)."""
-    import warnings
-    pipe = SpectrumPipeline(device, overlap=False)
-    spectra, dims, tangent, capped = [], [], [], 0
+def _sv_count(sample_shape, batchsize):
+    """torch.linalg.svd returns min(M, D) values per point (dim_reduction.py:197): a short loader batch gives a shorter list."""
+    return min(batching(tuple(sample_shape), batchsize)[2], math.prod(sample_shape))
 
-    def finish(S_points, svs, ids):
-        nonlocal capped
-        host = checked_spectra(svs)
-        for S, sv, p in zip(S_points, host, ids):
+
+def _safe_rebuild(builder, x, batchsize, **kw):
+    """The ``rebuild`` of SpectrumPipeline.submit / row_sharded_spectrum for the point ``builder.build(x, batchsize, **kw)``: the
+    same build on the safe route."""
+    return lambda: builder.build(x.to(builder.device), batchsize, safe=True, **kw)
+
+
+def _launch_groups(config, points, ids):
+    """How the points ``ids`` share launches -> (batched, groups of ids).  Vector data (at most 4096 elements a point, one loader
+    batch size): many points per launch set and the batched spectrum kernel (one workgroup per matrix for D <= 128), in groups
+    of ``dim_estimation.points_per_launch`` (default: 131072 rows a launch).  Anything else: one point per group."""
+    if not ids or points[ids[0]][0].numel() > 4096 or len({points[p][1] for p in ids}) != 1:
+        return False, [[p] for p in ids]
+    rows = batching(tuple(points[ids[0]][0].shape), points[ids[0]][1])[2]
+    group = max(1, min(len(ids), int(config.get('dim_estimation.points_per_launch', max(1, 131072 // rows)))))
+    return True, [ids[lo:lo + group] for lo in range(0, len(ids), group)]
+
+
+def _group_scores(builder, points, ids, batched, point_seed):
+    """(S, rebuild) of one launch group: S [P, M, D] of a batched group (``build_many``; no rebuild), or S [M, D] of the group's
+    one point and its safe rebuild."""
+    if batched:
+        return build_many(builder, [points[p][0].to(builder.device) for p in ids], points[ids[0]][1],
+                          [point_seed(p) for p in ids]), None
+    x, batchsize = points[ids[0]]
+    return (builder.build(x.to(builder.device), batchsize, seed=point_seed(ids[0])),
+            _safe_rebuild(builder, x, batchsize, seed=point_seed(ids[0])))
+
+
+def _points_with_tangent(builder, points, batched, groups, point_seed):
+    """The loop of ``get_manifold_dimension(return_tangent=True)``: every launch group is taken to completion -- score matrix,
+    spectrum, ID on the host, ``_lib.tangent_basis(S, d)``, S released -- on ONE stream: the width of the basis is known only
+    once the spectrum has reached the host, so nothing of the next point is queued under it.  Score matrices and spectra come
+    from the same launches as without the flag.  -> (spectra [P, D] on the device, dims, tangent)."""
+    import warnings
+    pipe = SpectrumPipeline(builder.device, overlap=False)
+    spectra, dims, tangent, capped = [], [], [], 0
+    for ids in groups:
+        S, rebuild = _group_scores(builder, points, ids, batched, point_seed)
+        # the possibly rebuilt S is needed for the basis afterwards, so the finite check is made here, not by the pipeline
+        if rebuild is not None and not bool(torch.isfinite(S).all()):
+            warn_non_finite_point()
+            S = rebuild()
+        pipe.submit(S)
+        svs = pipe.results()[0] if batched else torch.stack(pipe.results())
+        for S_p, sv, p in zip(S if batched else [S], checked_spectra(svs), ids):
             x, b = points[p]
-            d, k = tangent_width(sv[:min(batching(tuple(x.shape), b)[2], x.numel())].tolist(), x.numel())
+            d, k = tangent_width(sv[:_sv_count(x.shape, b)].tolist(), x.numel())
             dims.append(d)
             capped += d > _lib.TANGENT_MAX
             if k is None:
                 tangent.append(None)
                 continue
-            T, _, resid = _lib.tangent_basis(S, k)
+            T, _, resid = _lib.tangent_basis(S_p, k)
             if not math.isfinite(float(resid)):
                 raise RuntimeError(f"point {p}: the tangent basis of width {k} came back non-finite (the Gram matrix of the scores is "
                                    "not positive semi-definite to rounding, or holds non-finite values)")
             tangent.append(T.to(torch.float32).cpu().numpy())
         spectra.extend(svs)
-
-    with torch.no_grad():
-        ids_all = list(range(len(points)))
-        small = points[0][0].numel() <= 4096 and len({b for _, b in points}) == 1
-        if small:
-            rows = batching(tuple(points[0][0].shape), points[0][1])[2]
-            group = max(1, min(len(ids_all), int(config.get('dim_estimation.points_per_launch', max(1, 131072 // rows)))))
-            for lo in range(0, len(ids_all), group):
-                ids = ids_all[lo:lo + group]
-                S = build_many(builder, [points[p][0].to(device) for p in ids], points[ids[0]][1], [point_seed(p) for p in ids])
-                pipe.submit(S)
-                finish(S, pipe.results()[0], ids)
-                del S
-        else:
-            for p in ids_all:
-                x, batchsize = points[p]
-                S = builder.build(x.to(device), batchsize, seed=point_seed(p))
-                if not bool(torch.isfinite(S).all()):
-                    warn_non_finite_point()
-                    S = builder.build(x.to(device), batchsize, seed=point_seed(p), safe=True)
-                pipe.submit(S)
-                finish([S], torch.stack(pipe.results()), [p])
-                del S
+        del S
     if capped:
         warnings.warn(f"id-diff_amd: {capped} point(s) have an intrinsic dimension above {_lib.TANGENT_MAX}, the widest tangent "
                       "basis that is computed: their entry of `tangent` is None")
@@ -434,19 +450,10 @@ def build_many(builder, xs, batchsize, seeds):
     launch-bound one point at a time (M = 1501 rows of a 7-layer MLP), so points are batched (BASELINE config 2)."""
     x0 = xs[0]
     _, _, rows = batching(tuple(x0.shape), batchsize)
-    D, P, dev = x0.numel(), len(xs), builder.device
-    vec_t = torch.full((rows,), float(builder.eps), device=dev, dtype=torch.float32)
-    mean_unit, std = builder.sde.marginal_prob(torch.ones((), device=dev), vec_t)
-    coeff = None if mean_unit.ndim == 0 else mean_unit.reshape(-1).contiguous()
-    std = std.contiguous()
-    batch = torch.empty(P, rows, D, device=dev, dtype=torch.float32)
-    for i, (x, seed) in enumerate(zip(xs, seeds)):
-        if D % 4 == 0:
-            _lib.perturb_randn(x.reshape(-1).contiguous(), std, coeff, batch[i], rows, D, 0, seed)
-        else:
-            z = torch.randn(rows, D, device=dev, dtype=torch.float32, generator=torch.Generator(device=dev).manual_seed(seed))
-            _lib.perturb(x.reshape(-1).contiguous(), z, std, coeff, batch[i], rows, D)
-    t_all = torch.full((P * rows,), float(builder.eps), device=dev, dtype=torch.float32)
+    D, P = x0.numel(), len(xs)
+    noise = [builder._seeded_noise(rows, D, seed) for seed in seeds] if D % 4 else None
+    batch, _ = builder._perturbed([x.reshape(-1).contiguous() for x in xs], builder.eps, 0, rows, noise=noise, seeds=seeds)
+    t_all = torch.full((P * rows,), float(builder.eps), device=builder.device, dtype=torch.float32)
     score = builder.score_fn(batch.view(P * rows, *x0.shape), t_all)
     return score.reshape(P, rows, D)
 
@@ -498,7 +505,10 @@ def get_manifold_dimension(config, name=None, return_svd=False, return_dims=Fals
     evaluations, and it needs a single rank with ``dim_estimation.shard = 'points'`` (NotImplementedError otherwise).  The
     singular values and dims are those of a call without the flag, bit for bit.  Without ``return_svd`` the config key
     ``dim_estimation.save_tangent`` (default False) selects the mode and writes ``<name>_tangent.pkl`` =
-    ``{'tangent': [...], 'dims': [...]}`` beside the unchanged ``<name>.pkl``."""
+    ``{'tangent': [...], 'dims': [...]}`` beside the unchanged ``<name>.pkl``.
+
+    The row-sharded mode (``dim_estimation.shard = 'rows'`` on more than one rank) does not serve ``return_dims``: it returns
+    ``info`` alone."""
     log_path, log_name = config.logging.log_path, config.logging.log_name
     save_path = os.path.join(log_path, log_name, 'svd')
     rank, world = parallel.rank_world()
@@ -510,22 +520,25 @@ def get_manifold_dimension(config, name=None, return_svd=False, return_dims=Fals
     if rank == 0 and not return_svd:
         Path(save_path).mkdir(parents=True, exist_ok=True)
 
+    def deliver(info, dims=None, tangent=None):
+        """The one exit of every mode: what the flags ask for (``dims=None``: a mode that serves no IDs), or the pickles on rank 0."""
+        if return_svd:
+            out = (info,) + ((dims,) if return_dims and dims is not None else ()) + ((tangent,) if return_tangent else ())
+            return out if len(out) > 1 else info
+        if rank == 0:
+            with open(os.path.join(save_path, f'{name}.pkl'), 'wb') as f:
+                pickle.dump(info, f)
+            if save_tangent:
+                with open(os.path.join(save_path, f'{name}_tangent.pkl'), 'wb') as f:
+                    pickle.dump({'tangent': tangent, 'dims': dims}, f)
+
     seed = int(config.get('seed', 42))
     torch.manual_seed(seed)  # same data split / loader order on every rank
     DataModule, pl_module, score_fn, device = setup_model(config)
     num_datapoints = _num_datapoints(config)
     points = collect_points(DataModule.train_dataloader(), num_datapoints)
     if not points:                       # num_datapoints <= 1: the reference's loop body never runs (:159-164)
-        info = {'singular_values': []}
-        if return_svd:
-            return ((info, [], []) if return_dims else (info, [])) if return_tangent else info
-        if rank == 0:
-            with open(os.path.join(save_path, f'{name}.pkl'), 'wb') as f:
-                pickle.dump(info, f)
-            if save_tangent:
-                with open(os.path.join(save_path, f'{name}_tangent.pkl'), 'wb') as f:
-                    pickle.dump({'tangent': [], 'dims': []}, f)
-        return None
+        return deliver({'singular_values': []}, [], [])
     builder = ScoreMatrixBuilder(score_fn, pl_module.sde, pl_module.sampling_eps, device,
                                  config.get('dim_estimation.inflight_rows', None))
     def point_seed(p):
@@ -539,62 +552,27 @@ def get_manifold_dimension(config, name=None, return_svd=False, return_dims=Fals
                 rows = batching(tuple(x.shape), batchsize)[2]
                 kw = dict(seed=point_seed(p), row_range=parallel.my_rows(rows, rank, world))
                 S_local = builder.build(x.to(device), batchsize, **kw)
-                spectra.append(row_sharded_spectrum(S_local, rows, rebuild=lambda x=x, b=batchsize, kw=kw: builder.build(x.to(device), b, safe=True, **kw)))
-        info = {'singular_values': [s.tolist() for s in checked_spectra(torch.stack(spectra))]}
-        if return_svd:
-            return info
-        if rank == 0:
-            with open(os.path.join(save_path, f'{name}.pkl'), 'wb') as f:
-                pickle.dump(info, f)
-        return None
-
-    if return_tangent or save_tangent:
-        local, dims, tangent = _points_with_tangent(config, builder, points, point_seed, device)
-        keep = [min(batching(tuple(x.shape), b)[2], x.numel()) for x, b in points]
-        info = {'singular_values': [s[:k].tolist() for s, k in zip(checked_spectra(local), keep)]}
-        if return_svd:
-            return (info, dims, tangent) if return_dims else (info, tangent)
-        with open(os.path.join(save_path, f'{name}.pkl'), 'wb') as f:
-            pickle.dump(info, f)
-        with open(os.path.join(save_path, f'{name}_tangent.pkl'), 'wb') as f:
-            pickle.dump({'tangent': tangent, 'dims': dims}, f)
-        return None
+                spectra.append(row_sharded_spectrum(S_local, rows, rebuild=_safe_rebuild(builder, x, batchsize, **kw)))
+        return deliver({'singular_values': [s.tolist() for s in checked_spectra(torch.stack(spectra))]})
 
     mine = parallel.my_points(len(points), rank, world)
-    n_sv = None
-    pipe = SpectrumPipeline(device, overlap=bool(config.get('dim_estimation.overlap_spectrum', True)))
-
+    batched, groups = _launch_groups(config, points, mine)
+    keep = [_sv_count(x.shape, b) for x, b in points]
     with torch.no_grad():
-        small = bool(mine) and points[mine[0]][0].numel() <= 4096 and len({points[p][1] for p in mine}) == 1
-        if small:
-            # vector data: many points per launch set, batched spectrum kernel (one workgroup per matrix for D <= 128)
-            rows = batching(tuple(points[mine[0]][0].shape), points[mine[0]][1])[2]
-            group = max(1, min(len(mine), int(config.get('dim_estimation.points_per_launch', max(1, 131072 // rows)))))
-            for lo in range(0, len(mine), group):
-                ids = mine[lo:lo + group]
-                S = build_many(builder, [points[p][0].to(device) for p in ids], points[ids[0]][1],
-                               [point_seed(p) for p in ids])
-                pipe.submit(S)
-            local = [sv for block in pipe.results() for sv in block]
+        if return_tangent or save_tangent:           # one rank: ``mine`` is every point, nothing to exchange
+            spectra, dims, tangent = _points_with_tangent(builder, points, batched, groups, point_seed)
         else:
-            for p in mine:
-                x, batchsize = points[p]
-                pipe.submit(builder.build(x.to(device), batchsize, seed=point_seed(p)),
-                            rebuild=lambda x=x, b=batchsize, sd=point_seed(p): builder.build(x.to(device), b, seed=sd, safe=True))
-            local = pipe.results()
-    n_sv = points[0][0].numel()              # fixed-width rows for the exchange (a rank without points takes part too)
-    local = torch.stack(local) if local else torch.empty(0, n_sv, device=device)
-    # torch.linalg.svd returns min(M, D) values per point (dim_reduction.py:197): a short loader batch gives a shorter list
-    keep = [min(batching(tuple(x.shape), b)[2], x.numel()) for x, b in points]
-    # (the rule needs three singular values; -1 marks a point that has fewer)
-    my_dims = [estimate_dim(sv[:keep[p]].tolist()) if keep[p] >= 3 else -1 for sv, p in zip(checked_spectra(local), mine)]
-    spectra, dims = parallel.gather_spectra(local, len(points), n_sv, device, dims=my_dims)
-    info = {'singular_values': [s[:k].tolist() for s, k in zip(checked_spectra(spectra), keep)]}
-    if return_svd:
-        return (info, dims.tolist()) if return_dims else info
-    if rank == 0:
-        with open(os.path.join(save_path, f'{name}.pkl'), 'wb') as f:
-            pickle.dump(info, f)
+            pipe = SpectrumPipeline(device, overlap=bool(config.get('dim_estimation.overlap_spectrum', True)))
+            for ids in groups:
+                pipe.submit(*_group_scores(builder, points, ids, batched, point_seed))
+            local = [sv for block in pipe.results() for sv in block] if batched else pipe.results()
+            n_sv = points[0][0].numel()              # fixed-width rows for the exchange (a rank without points takes part too)
+            local = torch.stack(local) if local else torch.empty(0, n_sv, device=device)
+            # (the rule needs three singular values; -1 marks a point that has fewer)
+            my_dims = [estimate_dim(sv[:keep[p]].tolist()) if keep[p] >= 3 else -1 for sv, p in zip(checked_spectra(local), mine)]
+            spectra, dims = parallel.gather_spectra(local, len(points), n_sv, device, dims=my_dims)
+            dims, tangent = dims.tolist(), None
+    return deliver({'singular_values': [s[:k].tolist() for s, k in zip(checked_spectra(spectra), keep)]}, dims, tangent)
 
 
 def collect_labelled_points(loader, num_datapoints, label=1):
@@ -640,14 +618,13 @@ def conditional_spectra(builder, loader, num_datapoints, seed=42, levels=None, n
                 x, _, batchsize = points[p]
                 z = None if noise is None else noise(level, p).to(device)
                 kw = dict(t=float(t_slice), noise=z, seed=seed + 1000003 * (p + 1) + 7919 * level)
-                pipe.submit(builder.build(x.to(device), batchsize, **kw),
-                            rebuild=lambda x=x, b=batchsize, kw=kw: builder.build(x.to(device), b, safe=True, **kw))
+                pipe.submit(builder.build(x.to(device), batchsize, **kw), rebuild=_safe_rebuild(builder, x, batchsize, **kw))
             local = pipe.results()
         if points:
             n_sv = points[0][0].numel()
             local = torch.stack(local) if local else torch.empty(0, n_sv, device=device)
             spectra = checked_spectra(parallel.gather_spectra(local, len(points), n_sv, device))
-            spectra = [s[:min(batching(tuple(x.shape), b)[2], x.numel())] for s, (x, _, b) in zip(spectra, points)]
+            spectra = [s[:_sv_count(x.shape, b)] for s, (x, _, b) in zip(spectra, points)]
         else:
             spectra = torch.empty(0, 0)
         out.append({'level': level, 't': float(t_slice),
