@@ -117,6 +117,11 @@ _SIGNATURES = {
     "idiff_sym_lowvecs_f64": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "idiff_knn_workspace_bytes": (c_i64, [c_i, c_i, c_i]),
     "idiff_knn_f32": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p]),
+    "idiff_apsp_tile": (c_i, []),
+    "idiff_knn_graph_f64": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p]),
+    "idiff_apsp_f64": (c_i, [c_p, c_i, c_p]),
+    "idiff_double_center_scratch_doubles": (c_i64, [c_i]),
+    "idiff_double_center_f64": (c_i, [c_p, c_i, c_p, c_p, c_p, c_p]),
     "idiff_render_squares_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
     "idiff_render_gaussians_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
 }
@@ -919,6 +924,55 @@ def knn(X, k, workspace=None):
     _check(lib().idiff_knn_f32(X.data_ptr(), N, D, k, _ptr(workspace), 0 if workspace is None else workspace.numel() * 8,
                                dist.data_ptr(), idx.data_ptr(), n_exact.data_ptr(), _stream()), "idiff_knn_f32")
     return dist, idx, n_exact
+
+
+# ------------------------------------------------------------------------------------------- geodesic distances (Isomap)
+def __getattr__(name):
+    """``_lib.APSP_TILE``: the tile of the blocked Floyd-Warshall, asked of the library (idiff_apsp_tile; the edge cases of the
+    tests sit around it)."""
+    if name == "APSP_TILE":
+        return lib().idiff_apsp_tile()
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def _square_f64(M, name):
+    _dev(M, name, dtype=torch.float64)
+    if M.ndim != 2 or M.shape[0] != M.shape[1] or M.shape[0] < 1:
+        raise RuntimeError(f"{name} must be [N, N] with N >= 1, got {tuple(M.shape)}")
+    return M.shape[0]
+
+
+def knn_graph(dist, idx):
+    """Dense neighbourhood graph G [N, N] fp64 of a ``knn`` result (dist [N, k] fp64, idx [N, k] int64): 0 on the diagonal,
+    the distance where either point is among the other's neighbours (the smaller where both are), +inf elsewhere -- the graph
+    ``scipy.sparse.csgraph.shortest_path(directed=False)`` reads from sklearn's ``kneighbors_graph``.  No host sync."""
+    _dev(dist, "dist", dtype=torch.float64); _dev(idx, "idx", dtype=torch.int64)
+    if dist.ndim != 2 or dist.shape != idx.shape:
+        raise RuntimeError(f"knn_graph: dist and idx must both be [N, k], got {tuple(dist.shape)} and {tuple(idx.shape)}")
+    N, k = dist.shape
+    G = torch.empty(max(N, 1), max(N, 1), dtype=torch.float64, device=dist.device)
+    _check(lib().idiff_knn_graph_f64(_ptr(dist), _ptr(idx), N, k, G.data_ptr(), _stream()), "idiff_knn_graph_f64")
+    return G
+
+
+def geodesic_distances(G):
+    """All-pairs shortest paths of the dense graph G [N, N] fp64 (non-negative weights, 0 diagonal, +inf = no edge), IN PLACE
+    (blocked Floyd-Warshall, idiff_apsp_f64); returns G.  Unreachable pairs stay +inf.  No host sync."""
+    N = _square_f64(G, "G")
+    _check(lib().idiff_apsp_f64(G.data_ptr(), N, _stream()), "idiff_apsp_f64")
+    return G
+
+
+def double_center(D):
+    """``(K, fro2)`` of a symmetric distance matrix D [N, N] fp64 (only read): K = -1/2 J (D o D) J fp64 [N, N] and the 0-d
+    fp64 device tensor ||K||_F^2.  No host sync."""
+    N = _square_f64(D, "D")
+    K = torch.empty_like(D)
+    fro2 = torch.empty((), dtype=torch.float64, device=D.device)
+    scratch = torch.empty(max(1, lib().idiff_double_center_scratch_doubles(N)), dtype=torch.float64, device=D.device)
+    _check(lib().idiff_double_center_f64(D.data_ptr(), N, K.data_ptr(), fro2.data_ptr(), scratch.data_ptr(), _stream()),
+           "idiff_double_center_f64")
+    return K, fro2
 
 
 # ------------------------------------------------------------------------------------------- image manifolds

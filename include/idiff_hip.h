@@ -484,6 +484,30 @@ int64_t idiff_knn_workspace_bytes(int N, int D, int k);
 int idiff_knn_f32(const float *X, int N, int D, int k, void *workspace, int64_t workspace_bytes, double *dist, int64_t *idx,
                   int *n_exact_rows, void *stream);
 
+/* ------------------------------------------------------------------ geodesic distances (Isomap) */
+
+/* The three device stages of `Isomap(n_neighbors, n_components).fit(X).reconstruction_error()` of isomap.py:56-58 between
+ * the neighbour search and the eigenvalues, all fp64, row-major, contiguous.  Each launches on `stream`, does not
+ * synchronise and does not allocate.  Needs 1 <= N <= 2^20 and non-null pointers (IDIFF_EINVAL otherwise, nothing launched).
+ *
+ * knn_graph: dist, idx [N, k] as idiff_knn_f32 writes them (0 <= k <= N - 1; both may be null only for k = 0) -> G [N, N]
+ * with G[i, i] = 0, G[i, j] = the distance where j is among i's neighbours or i among j's (the smaller where both),
+ * +inf elsewhere: the graph scipy.sparse.csgraph.shortest_path(directed=False) reads from sklearn's kneighbors_graph.
+ * Deterministic (no atomics); an index outside [0, N) is dropped.
+ *
+ * apsp: all-pairs shortest paths in place, blocked Floyd-Warshall on tiles of idiff_apsp_tile() = 64 (3 launches per
+ * diagonal tile; any N, no padding asked of the caller).  G holds non-negative weights, 0 on the diagonal and +inf for
+ * "no edge", no NaN; an unreachable pair stays +inf and the diagonal stays 0 exactly.  2 N^3 fp64 operations.
+ *
+ * double_center: D [N, N] (symmetric, only read) -> K = -1/2 J (D o D) J, J = I - 1 1^T / N, and *fro2 = ||K||_F^2 (device
+ * scalar).  scratch: idiff_double_center_scratch_doubles(N) doubles (0 for an N the call refuses).  Fixed summation
+ * trees: the same bits on every launch. */
+int idiff_apsp_tile(void);
+int idiff_knn_graph_f64(const double *dist, const int64_t *idx, int N, int k, double *G, void *stream);
+int idiff_apsp_f64(double *G, int N, void *stream);
+int64_t idiff_double_center_scratch_doubles(int N);
+int idiff_double_center_f64(const double *D, int N, double *K, double *fro2, double *scratch, void *stream);
+
 /* ------------------------------------------------------------------ image manifolds of known dimension */
 
 /* The two fixed image manifolds of lightning_data_modules/SyntheticDataset.py:81-183, one workgroup per image, out
