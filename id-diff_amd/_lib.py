@@ -21,7 +21,7 @@ _lib = None
 
 ACT = {None: 0, "none": 0, "linear": 0, "silu": 1, "swish": 1, "elu": 2, "relu": 3, "lrelu": 4}
 
-c_i, c_i64, c_f, c_p = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
+c_i, c_i64, c_f, c_d, c_p = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_void_p
 
 
 class Epilogue(ctypes.Structure):
@@ -115,6 +115,8 @@ _SIGNATURES = {
     "idiff_tridiag_eigvals_f64": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p]),
     "idiff_sym_lowvecs_scratch_doubles": (c_i64, [c_i, c_i]),
     "idiff_sym_lowvecs_f64": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "idiff_sym_topvecs_scratch_doubles": (c_i64, [c_i, c_i, c_i]),
+    "idiff_sym_topvecs_f64": (c_i, [c_p, c_i, c_i, c_i, c_d, c_d, c_d, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "idiff_knn_workspace_bytes": (c_i64, [c_i, c_i, c_i]),
     "idiff_knn_f32": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p]),
     "idiff_apsp_tile": (c_i, []),
@@ -122,6 +124,10 @@ _SIGNATURES = {
     "idiff_apsp_f64": (c_i, [c_p, c_i, c_p]),
     "idiff_double_center_scratch_doubles": (c_i64, [c_i]),
     "idiff_double_center_f64": (c_i, [c_p, c_i, c_p, c_p, c_p, c_p]),
+    "idiff_knn_cross_workspace_bytes": (c_i64, [c_i, c_i]),
+    "idiff_knn_cross_f64": (c_i, [c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p]),
+    "idiff_isomap_project_scratch_doubles": (c_i64, [c_i]),
+    "idiff_isomap_project_f64": (c_i, [c_p, c_p, c_i, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p]),
     "idiff_render_squares_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
     "idiff_render_gaussians_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
 }
@@ -890,6 +896,97 @@ def sym_lowvecs(G, k):
     return T, ritz, resid
 
 
+
+# ------------------------------------------------------------------------------------------- largest eigenpairs
+TOPVECS_MAX = 64                  # most eigenpairs idiff_sym_topvecs_f64 returns
+TOPVECS_BLOCK_MAX = 128           # widest block it iterates on
+TOPVECS_OVERSAMPLING = 16         # fewest columns beyond k (max(16, k) are taken): the filter's upper end is lambda_(p + 1), not lambda_(k + 1)
+TOPVECS_AMPLIFICATION = 1e6       # bound of C_m(lambda_1) / C_m(lambda_k) per sweep: column k keeps 10 of its 16 digits
+TOPVECS_BLOCK_AMPLIFICATION = 1e10   # the same for the last column of the block (it need only stay a direction)
+TOPVECS_DEGREE_MAX = 32
+TOPVECS_TARGET = 1e13             # total damping of lambda_(p+1) against lambda_k the sweeps must reach
+TOPVECS_PRODUCTS_MAX = 1000       # matrix products (degree * sweeps) a plan may ask for
+
+
+def _log_cheb(m, x):
+    """log T_m(x) for x >= 1, without forming T_m (which overflows a double beyond m acosh(x) = 710)."""
+    import math
+    a = m * math.acosh(x) if x > 1.0 else 0.0
+    return a + math.log1p(math.exp(-2.0 * a)) - math.log(2.0)
+
+
+def topvecs_plan(eigvals, k):
+    """The fixed schedule of ``sym_topvecs`` from ALL eigenvalues of the matrix (any order; host numpy): a dict with the block
+    width ``p`` = min(k + max(16, k), 128, N - 1) (a wide block keeps lambda_(p+1) well below lambda_k where the spectrum decays
+    slowly), the filter interval ``lo`` = lambda_min, ``hi`` = lambda_(p+1), ``top`` = lambda_1 (for
+    p = N - 1, where the two ends coincide, lo = hi - (top - hi)), the
+    Chebyshev ``degree`` per sweep, the number of ``sweeps``, ``products`` = degree * sweeps and ``amplification`` =
+    C_m(lambda_1) / C_m(lambda_k), the factor by which one sweep lifts column 1 over column k.  The degree is, among those (up to 32)
+    that keep that factor below 1e6 (and the same factor for the block's last column below 1e10), the one with the fewest products: a filter that lifts lambda_1
+    by 1e40 over lambda_3 leaves nothing of column 3 in fp64.  The sweeps are as many as damp lambda_(p+1) by 1e13 against
+    lambda_k, plus one.  Pure host arithmetic.  Raises ``ValueError`` when lambda_k is not positive (above 1e-12 of lambda_1, the
+    rule of ``isomap.n_positive``) or when the schedule would need more than 1000 matrix products (a flat spectrum from lambda_k
+    to lambda_(p+1))."""
+    import math
+    import numpy as np
+    lam = np.sort(np.asarray(eigvals, dtype=np.float64).reshape(-1))[::-1]
+    N, k = lam.size, int(k)
+    if not 1 <= k <= TOPVECS_MAX or k >= N:
+        raise ValueError(f"topvecs_plan: k = {k} outside 1..min({TOPVECS_MAX}, N - 1 = {N - 1})")
+    if not np.isfinite(lam).all():
+        raise ValueError("topvecs_plan: the eigenvalues hold NaN or inf")
+    if not (lam[0] > 0 and lam[k - 1] > 1e-12 * lam[0]):
+        raise ValueError(f"topvecs_plan: lambda_{k} = {float(lam[k - 1])!r} is not positive (lambda_1 = {float(lam[0])!r}): the matrix has "
+                         f"{int(np.count_nonzero(lam > 1e-12 * lam[0])) if lam[0] > 0 else 0} positive eigenvalues")
+    p = min(k + max(TOPVECS_OVERSAMPLING, k), TOPVECS_BLOCK_MAX, N - 1)
+    lo, hi, top = float(lam[-1]), float(lam[p]), float(lam[0])
+    if p == N - 1:                                   # lambda_(p+1) is lambda_min itself: an interval as wide below it as lambda_1 is above
+        lo = hi - (top - hi)
+    flat = (f"topvecs_plan: lambda_{k} = {float(lam[k - 1])!r} and lambda_{p + 1} = {hi!r} (lambda_1 = {top!r}, lambda_min = {lo!r}) are too "
+            f"close: separating them needs more than {TOPVECS_PRODUCTS_MAX} matrix products")
+    c, e = 0.5 * (hi + lo), 0.5 * (hi - lo)
+    if not e > 0:
+        raise ValueError(flat)
+    x1, xk, xp = (top - c) / e, (float(lam[k - 1]) - c) / e, (float(lam[p - 1]) - c) / e
+    log_amp, log_block = math.log(TOPVECS_AMPLIFICATION), math.log(TOPVECS_BLOCK_AMPLIFICATION)
+    allowed = 1                                      # degrees 1 .. allowed keep both amplifications within their bounds
+    while (allowed < TOPVECS_DEGREE_MAX and _log_cheb(allowed + 1, x1) - _log_cheb(allowed + 1, xk) <= log_amp
+           and _log_cheb(allowed + 1, x1) - _log_cheb(allowed + 1, xp) <= log_block):
+        allowed += 1
+    if not _log_cheb(allowed, xk) > 1e-12:
+        raise ValueError(flat)
+    sweeps_of = lambda m: max(2, int(math.ceil(math.log(TOPVECS_TARGET) / _log_cheb(m, xk))) + 1)
+    degree = min(range(1, allowed + 1), key=lambda m: (m * sweeps_of(m), m))        # the fewest products, the lower degree among equals
+    sweeps, log_gain = sweeps_of(degree), _log_cheb(degree, xk)
+    if degree * sweeps > TOPVECS_PRODUCTS_MAX:
+        raise ValueError(flat)
+    return {"p": p, "lo": lo, "hi": hi, "top": top, "degree": degree, "sweeps": sweeps, "products": degree * sweeps,
+            "amplification": math.exp(min(_log_cheb(degree, x1) - log_gain, 700.0))}
+
+
+def sym_topvecs(K, k, eigvals, plan=None):
+    """``(V, ritz, resid)`` of a symmetric fp64 matrix K [N, N] that may be indefinite: V [N, k] fp64 with orthonormal columns, the
+    eigenvectors of the k LARGEST eigenvalues, ritz [k] fp64 descending, resid a 0-d fp64 tensor |K V - V diag(ritz)|_F.
+    ``eigvals``: all N eigenvalues as a host array (``sym_eigvals(K.clone()).cpu()``), from which ``topvecs_plan`` fixes the
+    schedule (``plan``: that plan, when the caller has made it already); 1 <= k <= 64, k < N.  K is only read; a NaN in K or a failed factorisation comes back as NaN in all three.
+    No host sync."""
+    N = _square_f64(K, "K")
+    k = int(k)
+    if len(eigvals) != N:
+        raise ValueError(f"sym_topvecs: {len(eigvals)} eigenvalues for a {N} x {N} matrix")
+    if plan is None:
+        plan = topvecs_plan(eigvals, k)
+    p = plan["p"]
+    scratch = torch.empty(max(1, lib().idiff_sym_topvecs_scratch_doubles(N, k, p)), dtype=torch.float64, device=K.device)
+    V = torch.empty(N, k, dtype=torch.float64, device=K.device)
+    ritz = torch.empty(k, dtype=torch.float64, device=K.device)
+    resid = torch.empty((), dtype=torch.float64, device=K.device)
+    _check(lib().idiff_sym_topvecs_f64(K.data_ptr(), N, k, p, plan["lo"], plan["hi"], plan["top"], plan["degree"], plan["sweeps"],
+                                       V.data_ptr(), ritz.data_ptr(), resid.data_ptr(), scratch.data_ptr(), _stream()),
+           "idiff_sym_topvecs_f64")
+    return V, ritz, resid
+
+
 def tangent_basis(S, k):
     """The estimated tangent space at a point from its score matrix S [M, D] (CUDA fp32): the k right singular vectors of the
     column-centred S with the SMALLEST singular values, through the fp64 Gram matrix the spectrum is computed from
@@ -963,16 +1060,63 @@ def geodesic_distances(G):
     return G
 
 
-def double_center(D):
+def double_center(D, return_means=False):
     """``(K, fro2)`` of a symmetric distance matrix D [N, N] fp64 (only read): K = -1/2 J (D o D) J fp64 [N, N] and the 0-d
-    fp64 device tensor ||K||_F^2.  No host sync."""
+    fp64 device tensor ||K||_F^2.  ``return_means=True`` adds ``(colmean [N], grand 0-d)``, the column means and the grand mean
+    of -1/2 D o D (what ``isomap_project`` centres a new point's row with).  No host sync."""
     N = _square_f64(D, "D")
     K = torch.empty_like(D)
     fro2 = torch.empty((), dtype=torch.float64, device=D.device)
     scratch = torch.empty(max(1, lib().idiff_double_center_scratch_doubles(N)), dtype=torch.float64, device=D.device)
     _check(lib().idiff_double_center_f64(D.data_ptr(), N, K.data_ptr(), fro2.data_ptr(), scratch.data_ptr(), _stream()),
            "idiff_double_center_f64")
+    if return_means:
+        return K, fro2, (-0.5 * scratch[:N], -0.5 * scratch[2 * N])
     return K, fro2
+
+
+def knn_cross(Xq, X, k, workspace=None):
+    """Exact k nearest rows of X [N, D] for every row of Xq [M, D] (both CUDA fp32, contiguous): ``(dist, idx)`` with dist [M, k]
+    fp64 (Euclidean, from fp64 sums of squared differences of the fp32 coordinates; ascending, equal distances by lower index)
+    and idx [M, k] int64.  No row is excluded: a query that is a row of X finds it at distance 0.  k <= 64, k <= N.  No host sync."""
+    _dev(Xq, "Xq"); _dev(X, "X")
+    if Xq.ndim != 2 or X.ndim != 2 or Xq.shape[1] != X.shape[1]:
+        raise RuntimeError(f"knn_cross: Xq and X must be [M, D] and [N, D], got {tuple(Xq.shape)} and {tuple(X.shape)}")
+    if Xq.device != X.device:
+        raise RuntimeError(f"knn_cross: Xq on {Xq.device}, X on {X.device}")
+    (M, D), N, k = Xq.shape, X.shape[0], int(k)
+    need = lib().idiff_knn_cross_workspace_bytes(M, N)
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty(max(1, need // 8), dtype=torch.float64, device=X.device)
+    ok = M > 0 and k > 0
+    dist = torch.empty((M, k) if ok else (1,), dtype=torch.float64, device=X.device)
+    idx = torch.empty((M, k) if ok else (1,), dtype=torch.int64, device=X.device)
+    _check(lib().idiff_knn_cross_f64(Xq.data_ptr(), M, X.data_ptr(), N, D, k, workspace.data_ptr(), workspace.numel() * 8,
+                                     dist.data_ptr(), idx.data_ptr(), _stream()), "idiff_knn_cross_f64")
+    return dist, idx
+
+
+def isomap_project(dist, idx, D, A, colmean, grand):
+    """Isomap coordinates Z [M, c] fp64 of M new points from their neighbours among the fitted points (dist [M, k] fp64, idx [M, k]
+    int64, as ``knn_cross`` returns them), the fitted geodesic matrix D [N, N], A [N, c] = eigenvectors / sqrt(eigenvalue), and
+    ``colmean`` [N], ``grand`` (0-d device tensor), the means of -1/2 D o D (``double_center(D, return_means=True)``): what
+    scikit-learn's ``Isomap.transform`` computes, in one pass that never writes the [M, N] geodesic matrix.  An index outside
+    0..N-1 is ignored.  k <= 64, c <= 64.  No host sync."""
+    N = _square_f64(D, "D")
+    for t, name in ((dist, "dist"), (A, "A"), (colmean, "colmean"), (grand, "grand")):
+        _dev(t, name, dtype=torch.float64)
+    _dev(idx, "idx", dtype=torch.int64)
+    if dist.ndim != 2 or dist.shape != idx.shape:
+        raise RuntimeError(f"isomap_project: dist and idx must both be [M, k], got {tuple(dist.shape)} and {tuple(idx.shape)}")
+    if A.ndim != 2 or A.shape[0] != N or colmean.shape != (N,) or grand.numel() != 1:
+        raise RuntimeError(f"isomap_project: A must be [{N}, c], colmean [{N}] and grand a scalar, got {tuple(A.shape)}, "
+                           f"{tuple(colmean.shape)}, {tuple(grand.shape)}")
+    (M, k), c = dist.shape, A.shape[1]
+    Z = torch.empty(max(M, 1), max(c, 1), dtype=torch.float64, device=D.device)
+    scratch = torch.empty(max(1, lib().idiff_isomap_project_scratch_doubles(c)), dtype=torch.float64, device=D.device)
+    _check(lib().idiff_isomap_project_f64(dist.data_ptr(), idx.data_ptr(), M, k, D.data_ptr(), N, A.data_ptr(), c, colmean.data_ptr(),
+                                          grand.data_ptr(), Z.data_ptr(), scratch.data_ptr(), _stream()), "idiff_isomap_project_f64")
+    return Z
 
 
 # ------------------------------------------------------------------------------------------- image manifolds

@@ -1,4 +1,5 @@
-"""Isomap reconstruction error against the embedding dimension (the curve of the reference's isomap.py, figures/isomap.png).
+"""Isomap: the reconstruction error against the embedding dimension (the curve of the reference's isomap.py, figures/isomap.png),
+the embedding itself, and the coordinates of points that were not in the fit.
 
 The reference fits ``sklearn.manifold.Isomap(n_components=k)`` once per k (isomap.py:54-60): 29 neighbour graphs, 29
 all-pairs shortest paths and 29 eigen-decompositions of the same matrix.  Every error follows from ONE geodesic matrix D and
@@ -11,8 +12,13 @@ which is what ``Isomap(n_neighbors, n_components=k).fit(X).reconstruction_error(
 ``_lib.knn`` (exact fp64 neighbour distances) -> ``_lib.knn_graph`` -> ``_lib.geodesic_distances`` (blocked Floyd-Warshall,
 csrc/geodesic.hip) -> ``_lib.double_center`` -> ``_lib.sym_eigvals``; the O(len(ks)) arithmetic after it is host fp64.
 
-Not here: the embedding itself (eigenvectors), ``transform`` of new points, the random-forest score the reference computes
-on the embedding (isomap.py:62-67), more than one GPU.
+The embedding (class ``Isomap``) adds the k largest eigenpairs of K: ``_lib.double_center`` once more (the eigenvalue solver
+overwrites K) -> ``_lib.sym_topvecs`` (Chebyshev-filtered subspace iteration, csrc/topvecs.hip, scheduled from the eigenvalues
+already at hand), embedding = V sqrt(lambda) with scikit-learn's column signs.  ``transform`` places new points with
+``_lib.knn_cross`` -> ``_lib.isomap_project`` (csrc/isomap_project.hip).  ``run(embed=True)`` writes the embeddings and, given
+labels and scikit-learn, the random-forest scores the reference computes on them (isomap.py:56-67), fitted on the host.
+
+Not here: more than one GPU, n_components > 64, radius neighbourhoods, scikit-learn's repair of a disconnected graph.
 """
 import os
 import pickle
@@ -65,17 +71,52 @@ def _center(D):
     return K
 
 
-def errors_from_geodesics(D, ks, return_eigenvalues=False):
-    """The same arithmetic from a given geodesic matrix D [N, N], in numpy fp64 on the host (LAPACK eigenvalues)."""
+def svd_flip_columns(V):
+    """V with each column's sign chosen so that its entry of largest magnitude is positive (scikit-learn's ``svd_flip`` on the
+    eigenvectors, as KernelPCA applies it); numpy array or torch tensor."""
+    if isinstance(V, torch.Tensor):
+        top = V.gather(0, V.abs().argmax(dim=0, keepdim=True))
+        return V * torch.where(top < 0, -torch.ones_like(top), torch.ones_like(top))
+    V = np.asarray(V)
+    top = V[np.abs(V).argmax(axis=0), np.arange(V.shape[1])]
+    return V * np.where(top < 0, -1.0, 1.0)
+
+
+def errors_from_geodesics(D, ks, return_eigenvalues=False, return_embedding=False):
+    """The same arithmetic from a given geodesic matrix D [N, N], in numpy fp64 on the host (LAPACK).  ``return_embedding=True``
+    adds ``(V, lam_k)`` for k = max(ks): the eigenvectors [N, k] of the k largest eigenvalues with scikit-learn's signs and those
+    eigenvalues; the embedding is ``V * sqrt(lam_k)``."""
     D = np.asarray(D, dtype=np.float64)
     if D.ndim != 2 or D.shape[0] != D.shape[1]:
         raise ValueError(f"D must be [N, N], got {D.shape}")
     if not np.isfinite(D).all():
         raise ValueError(f"the neighbourhood graph has {count_components(np.isfinite(D))} connected components")
     K = _center(D)
-    lam = np.linalg.eigvalsh(K)[::-1]
+    if return_embedding:
+        w, W = np.linalg.eigh(K)
+        lam = w[::-1]
+    else:
+        lam = np.linalg.eigvalsh(K)[::-1]
     err = errors_from_eigenvalues(float((K * K).sum()), lam, D.shape[0], ks)
-    return (err, lam) if return_eigenvalues else err
+    out = (err, lam) if return_eigenvalues else (err,)
+    if return_embedding:
+        k = max(int(k) for k in ks)
+        out += ((svd_flip_columns(W[:, ::-1][:, :k]), lam[:k].copy()),)
+    return out if len(out) > 1 else err
+
+
+def transform_from_geodesics(D, V, lam, dist, idx):
+    """scikit-learn's ``Isomap.transform`` in numpy fp64 on the host: D [N, N] the fitted geodesic matrix, V [N, k] and lam [k] the
+    eigenvectors and eigenvalues of the embedding, dist / idx [M, n] the distances to and the indices of each new point's nearest
+    fitted points.  -> Z [M, k]"""
+    D, V, lam = np.asarray(D, dtype=np.float64), np.asarray(V, dtype=np.float64), np.asarray(lam, dtype=np.float64)
+    dist, idx = np.asarray(dist, dtype=np.float64), np.asarray(idx)
+    G = (dist[:, :, None] + D[idx]).min(axis=1)                    # [M, N]
+    G = -0.5 * G ** 2
+    S = -0.5 * D ** 2
+    colmean = S.mean(axis=0)
+    G = G - colmean[None, :] - G.mean(axis=1, keepdims=True) + colmean.mean()
+    return G @ (V / np.sqrt(lam))
 
 
 # ------------------------------------------------------------------------------------------- device path
@@ -100,7 +141,7 @@ def geodesics(X, n_neighbors=5):
     return D
 
 
-def _kernel_spectrum(X, n_neighbors):
+def _kernel_spectrum(X, n_neighbors, return_geodesics=False):
     """(||K||_F^2, eigenvalues of K descending [numpy fp64], N): one geodesic matrix, one centring, one eigensolve."""
     N = _n_rows(X)
     if N > N_MAX:
@@ -110,7 +151,8 @@ def _kernel_spectrum(X, n_neighbors):
     eig = _lib.sym_eigvals(K)                               # K is overwritten
     if bool(torch.isnan(eig).any()):
         eig = _lib.solve_with_fallbacks(lambda: _lib.sym_eigvals(_lib.double_center(D)[0]))
-    return float(fro2), eig.cpu().numpy()[::-1].copy(), N
+    out = float(fro2), eig.cpu().numpy()[::-1].copy(), N
+    return out + (D,) if return_geodesics else out
 
 
 def reconstruction_errors(X, ks, n_neighbors=5, return_eigenvalues=False):
@@ -124,23 +166,134 @@ def reconstruction_errors(X, ks, n_neighbors=5, return_eigenvalues=False):
     return (err, lam) if return_eigenvalues else err
 
 
+RESID_TOL = 1e-9                # fit() accepts |K V - V diag(lambda)|_F up to this times lambda_1 sqrt(k)
+
+
+class Isomap:
+    """``sklearn.manifold.Isomap(n_neighbors, n_components)`` on the device path of this module: ``fit`` / ``fit_transform`` /
+    ``transform`` / ``reconstruction_error``.  After ``fit``: ``embedding_`` [N, k] fp64 device tensor (= V sqrt(lambda), each
+    column's entry of largest magnitude positive, as scikit-learn's ``svd_flip`` leaves it), ``dist_matrix_`` [N, N] fp64 device
+    tensor (the geodesic distances), ``eigenvalues_`` [k] fp64 numpy, descending.  A disconnected neighbourhood graph, N > 12288 and
+    an n_components above the number of positive eigenvalues raise ``ValueError`` as ``reconstruction_errors`` does; a basis whose
+    residual exceeds 1e-9 lambda_1 sqrt(k) raises ``RuntimeError``.  n_components <= 64."""
+
+    def __init__(self, n_neighbors=5, n_components=2):
+        self.n_neighbors, self.n_components = int(n_neighbors), int(n_components)
+        if not 1 <= self.n_components <= _lib.TOPVECS_MAX:
+            raise ValueError(f"n_components = {n_components} outside 1..{_lib.TOPVECS_MAX}")
+
+    def fit(self, X):
+        k = self.n_components
+        fro2, lam, N, D = _kernel_spectrum(X, self.n_neighbors, return_geodesics=True)     # refuses N > 12288 before any device call
+        self._error = errors_from_eigenvalues(fro2, lam, N, [k])[0]           # raises for k beyond the positive eigenvalues
+        self.plan_ = _lib.topvecs_plan(lam, k)
+        K, _, (colmean, grand) = _lib.double_center(D, return_means=True)     # again: the eigenvalue solver has overwritten K
+        V, ritz, resid = _lib.sym_topvecs(K, k, lam, plan=self.plan_)
+        Xd = _points(X).to(D.device)
+        resid, top = float(resid), float(lam[0])
+        if not resid <= RESID_TOL * top * np.sqrt(k):
+            raise RuntimeError(f"isomap: the eigenvector residual |K V - V diag(lambda)|_F = {resid!r} exceeds "
+                               f"{RESID_TOL} * lambda_1 * sqrt(k) = {RESID_TOL * top * np.sqrt(k)!r} (n_components = {k})")
+        V = svd_flip_columns(V)
+        root = torch.sqrt(ritz)
+        self.embedding_ = V * root
+        self.eigenvalues_ = ritz.cpu().numpy()
+        self.dist_matrix_, self.residual_ = D, resid
+        self._fit_X, self._A, self._colmean, self._grand = Xd, (V / root).contiguous(), colmean.contiguous(), grand.reshape(1).contiguous()
+        return self
+
+    def fit_transform(self, X):
+        return self.fit(X).embedding_
+
+    def transform(self, X):
+        """Coordinates [M, k] (fp64 device tensor) of new points: their ``n_neighbors`` nearest fitted points, the shortest way into
+        the fitted graph through one of them, and the projection onto the fitted eigenvectors."""
+        Xq = _points(X).to(self._fit_X.device)
+        if Xq.shape[1] != self._fit_X.shape[1]:
+            raise ValueError(f"transform: points of dimension {Xq.shape[1]}, fitted on dimension {self._fit_X.shape[1]}")
+        dist, idx = _lib.knn_cross(Xq, self._fit_X, self.n_neighbors)
+        return _lib.isomap_project(dist, idx, self.dist_matrix_, self._A, self._colmean, self._grand)
+
+    def reconstruction_error(self):
+        return self._error
+
+
 # ------------------------------------------------------------------------------------------- the reference script's job
-def run(config, N=1000, ks=None, out_dir='isomap', n_neighbors=5):
+def classifier_scores(train, y_train, test, y_test):
+    """Accuracy of ``RandomForestClassifier(random_state=0)`` fitted to ``train`` / ``y_train`` and scored on ``test`` / ``y_test``
+    (isomap.py:62-67 of the reference), on the host.  Needs scikit-learn."""
+    from sklearn.ensemble import RandomForestClassifier
+    clf = RandomForestClassifier(random_state=0).fit(np.asarray(train), np.asarray(y_train))
+    return float(clf.score(np.asarray(test), np.asarray(y_test)))
+
+
+def _first_rows(loader, N):
+    """(X [<= N, D], labels [<= N] or None) from the first batches of a loader."""
+    rows, labels, have = [], [], 0
+    for item in loader:
+        pair = isinstance(item, (list, tuple))
+        x = item[0] if pair else item
+        rows.append(x.reshape(x.shape[0], -1))
+        if pair and len(item) > 1 and labels is not None and torch.is_tensor(item[1]) and item[1].shape[:1] == x.shape[:1]:
+            labels.append(item[1].reshape(x.shape[0], -1)[:, 0])
+        else:
+            labels = None
+        have += x.shape[0]
+        if have >= N:
+            break
+    return torch.cat(rows, dim=0)[:N], (torch.cat(labels)[:N].cpu().numpy() if labels else None)
+
+
+def _embed(DataModule, X, y, N, ks, out_dir, n_neighbors, pos):
+    """The ``embed=True`` part of ``run``: embedding.pkl ({k: [N, k] array} for k in (2, 3)) and, with labels and scikit-learn,
+    clf_scores.pkl ({k: accuracy} for every k <= 64 of ``ks``).  ONE fit, at the largest k asked for: column i of the embedding
+    and of ``transform`` belongs to eigenvalue i whatever n_components is, so the embedding of k components is the first k
+    columns.  A largest k whose eigenvectors ``_lib.topvecs_plan`` refuses (eigenvalues too close to separate) is given up for
+    the next smaller one, with one warning that names the values of k left out."""
+    wanted = sorted({k for k in list(ks) + [2, 3] if 1 <= k <= min(pos, _lib.TOPVECS_MAX, X.shape[0] - 1)})
+    iso, refused = None, []
+    while wanted and iso is None:
+        try:
+            iso = Isomap(n_neighbors, wanted[-1]).fit(X)
+        except ValueError as e:
+            if "topvecs_plan" not in str(e):
+                raise
+            refused.insert(0, wanted.pop())
+            why = str(e)
+    if refused:
+        warnings.warn(f"isomap: no embedding for n_components {refused}: {why}")
+    Z = iso.embedding_.cpu().numpy() if iso is not None else None
+    emb = {k: Z[:, :k].copy() for k in (2, 3) if k in wanted}
+    with open(os.path.join(out_dir, 'embedding.pkl'), 'wb') as f:
+        pickle.dump(emb, f)
+    try:
+        import sklearn  # noqa: F401
+        have_sklearn = True
+    except ImportError:
+        have_sklearn = False
+    Xt, yt = _first_rows(DataModule.test_dataloader(), N) if y is not None and have_sklearn and iso is not None else (None, None)
+    if yt is None:
+        warnings.warn("isomap: no classifier scores (" + ("scikit-learn is not installed" if not have_sklearn else
+                                                           "the loaders yield no labels") + ")")
+        return emb, None
+    T = iso.transform(Xt).cpu().numpy()
+    scores = {k: classifier_scores(Z[:, :k], y, T[:, :k], yt) for k in wanted if k in ks}
+    with open(os.path.join(out_dir, 'clf_scores.pkl'), 'wb') as f:
+        pickle.dump(scores, f)
+    return emb, scores
+
+
+def run(config, N=1000, ks=None, out_dir='isomap', n_neighbors=5, embed=False):
     """isomap.py:37-75 of the reference: the first N points of the train loader, the error for every k of ``ks`` (default the
     reference's list) into ``out_dir/reconstruction_error.pkl`` (a plain list of floats) and, when matplotlib imports,
-    ``reconstruction_error.png``.  Values of k beyond the positive eigenvalues are cut off with one warning.  -> (ks, errors)"""
+    ``reconstruction_error.png``.  Values of k beyond the positive eigenvalues are cut off with one warning.  -> (ks, errors)
+    ``embed=True`` also writes ``embedding.pkl`` (n_components 2 and 3) and, when the loaders yield labels and scikit-learn
+    imports, ``clf_scores.pkl``: the random-forest accuracy on the transformed test points for every k <= 64 of ``ks``."""
     from .lightning_data_modules.utils import create_lightning_datamodule
     ks = list(DEFAULT_KS if ks is None else ks)
     DataModule = create_lightning_datamodule(config)
     DataModule.setup()
-    rows, have = [], 0
-    for item in DataModule.train_dataloader():
-        x = item[0] if isinstance(item, (list, tuple)) else item
-        rows.append(x.reshape(x.shape[0], -1))
-        have += x.shape[0]
-        if have >= N:
-            break
-    X = torch.cat(rows, dim=0)[:N]
+    X, y = _first_rows(DataModule.train_dataloader(), N)
     fro2, lam, n = _kernel_spectrum(X, n_neighbors)
     pos = n_positive(lam)
     kept = [k for k in ks if k <= pos]
@@ -159,6 +312,8 @@ def run(config, N=1000, ks=None, out_dir='isomap', n_neighbors=5):
         fig = Figure(figsize=(10, 10))
         fig.subplots().plot(kept, values)
         fig.savefig(os.path.join(out_dir, 'reconstruction_error.png'), dpi=300, facecolor='white')
+    if embed:
+        _embed(DataModule, X, y, N, kept, out_dir, n_neighbors, pos)
     return kept, values
 
 
@@ -170,8 +325,9 @@ def main(argv=None):
     ap.add_argument('--N', type=int, default=1000)
     ap.add_argument('--n_neighbors', type=int, default=5)
     ap.add_argument('--out_dir', default='isomap')
+    ap.add_argument('--embed', action='store_true', help='also write embedding.pkl and, with labels and scikit-learn, clf_scores.pkl')
     args = ap.parse_args(argv)
-    ks, values = run(read_config(args.config), N=args.N, out_dir=args.out_dir, n_neighbors=args.n_neighbors)
+    ks, values = run(read_config(args.config), N=args.N, out_dir=args.out_dir, n_neighbors=args.n_neighbors, embed=args.embed)
     for k, v in zip(ks, values):
         print(f'k = {k}  reconstruction error: {v}')
 

@@ -469,6 +469,21 @@ int idiff_tridiag_eigvals_f64(const double *diag, const double *offdiag, int P, 
 int64_t idiff_sym_lowvecs_scratch_doubles(int D, int k);
 int idiff_sym_lowvecs_f64(double *G, int D, int k, double *T, double *ritz, double *resid, double *scratch, void *stream);
 
+/* The other end of the spectrum: the k LARGEST eigenpairs of a symmetric fp64 matrix K [N, N] (both triangles) that may be
+ * indefinite -- the centred geodesic kernel of Isomap.  V [N, k] row-major with orthonormal columns, ritz [k] descending (column i
+ * of V belongs to ritz[i]), resid [1] = |K V - V diag(ritz)|_F evaluated from the V that is returned.  Method: block subspace
+ * iteration on p columns (k <= p <= 128, p < N) with a Chebyshev filter: `sweeps` times a polynomial of degree `degree` in K that
+ * stays within [-1, 1] on [lo, hi] and equals 1 at `top`, every step Y <- alpha K X + beta X + gamma Z on v_mfma_f64_16x16x4 with K
+ * read once, each sweep followed by a shifted CholeskyQR3; then Rayleigh-Ritz (cyclic Jacobi) on the p columns, of which the k
+ * largest pairs are returned.  The caller, who has the eigenvalues, sets lo = lambda_min, hi = lambda_(p+1), top = lambda_1 and
+ * bounds the degree (python: _lib.topvecs_plan): all loops are fixed, nothing waits.  K is only read.  A NaN in K and a failed
+ * p x p factorisation turn V, ritz and resid into NaN.  Needs 1 <= k <= 64, k < N <= 2^20, lo < hi <= top finite, 1 <= degree <= 64,
+ * degree * sweeps <= 4096 (IDIFF_EINVAL otherwise, as for null pointers; nothing is launched).  scratch:
+ * idiff_sym_topvecs_scratch_doubles(N, k, p) doubles (0 for arguments the call refuses).  No host synchronisation. */
+int64_t idiff_sym_topvecs_scratch_doubles(int N, int k, int p);
+int idiff_sym_topvecs_f64(const double *K, int N, int k, int p, double lo, double hi, double top, int degree, int sweeps, double *V,
+                          double *ritz, double *resid, double *scratch, void *stream);
+
 /* ------------------------------------------------------------------ exact k nearest neighbours */
 
 /* Replaces `NearestNeighbors(n_neighbors=k+1, algorithm='ball_tree').fit(X).kneighbors(X)` of mle.py:19-20 / :47-48 /
@@ -500,13 +515,35 @@ int idiff_knn_f32(const float *X, int N, int D, int k, void *workspace, int64_t 
  * "no edge", no NaN; an unreachable pair stays +inf and the diagonal stays 0 exactly.  2 N^3 fp64 operations.
  *
  * double_center: D [N, N] (symmetric, only read) -> K = -1/2 J (D o D) J, J = I - 1 1^T / N, and *fro2 = ||K||_F^2 (device
- * scalar).  scratch: idiff_double_center_scratch_doubles(N) doubles (0 for an N the call refuses).  Fixed summation
- * trees: the same bits on every launch. */
+ * scalar).  scratch: idiff_double_center_scratch_doubles(N) doubles (0 for an N the call refuses); on return its first N hold
+ * the row (= column) means of D o D and scratch[2 N] their grand mean.  Fixed summation trees: the same bits on every launch. */
 int idiff_apsp_tile(void);
 int idiff_knn_graph_f64(const double *dist, const int64_t *idx, int N, int k, double *G, void *stream);
 int idiff_apsp_f64(double *G, int N, void *stream);
 int64_t idiff_double_center_scratch_doubles(int N);
 int idiff_double_center_f64(const double *D, int N, double *K, double *fro2, double *scratch, void *stream);
+
+/* Points that were not in the fit (sklearn.manifold.Isomap.transform), fp64 results, row-major, contiguous, no host
+ * synchronisation, no allocation.
+ *
+ * knn_cross: for every row of Xq [M, D] the k nearest rows of X [N, D] (both fp32) by fp64 brute force: dist [M, k] =
+ * sqrt(sum_d (q_d - x_d)^2) evaluated in fp64 from the fp32 inputs, ascending, equal distances by lower index; idx [M, k] the
+ * rows of X.  No row is excluded.  Needs 1 <= M, 1 <= N <= 2^20, 1 <= D, 1 <= k <= 64, k <= N.  workspace:
+ * idiff_knn_cross_workspace_bytes(M, N) bytes, 8-byte aligned (0 for arguments the call refuses).
+ *
+ * isomap_project: dist, idx [M, k] as knn_cross writes them, D [N, N] the fitted geodesic matrix, A [N, c] the eigenvectors
+ * divided by sqrt(eigenvalue), colmean [N] and grand [1] (device) the column means and the grand mean of -1/2 D o D over the fit
+ * -> Z [M, c] with g_ij = min_n (dist[i, n] + D[idx[i, n], j]), g'_ij = -1/2 g_ij^2 and
+ * Z[i, :] = sum_j (g'_ij - colmean_j - mean_j g'_ij + grand) A[j, :], in one launch: the [M, N] geodesic matrix is never
+ * written (the columns j are walked once per 8 components: one pass for c <= 8).
+ * Fixed summation trees: the same bits on every launch.  An index outside [0, N) is dropped.  Needs 1 <= M, 1 <= N <= 2^20,
+ * 1 <= k <= 64, 1 <= c <= 64.  scratch: idiff_isomap_project_scratch_doubles(c) doubles (0 for a c the call refuses). */
+int64_t idiff_knn_cross_workspace_bytes(int M, int N);
+int idiff_knn_cross_f64(const float *Xq, int M, const float *X, int N, int D, int k, void *workspace, int64_t workspace_bytes,
+                        double *dist, int64_t *idx, void *stream);
+int64_t idiff_isomap_project_scratch_doubles(int c);
+int idiff_isomap_project_f64(const double *dist, const int64_t *idx, int M, int k, const double *D, int N, const double *A, int c,
+                             const double *colmean, const double *grand, double *Z, double *scratch, void *stream);
 
 /* ------------------------------------------------------------------ image manifolds of known dimension */
 
