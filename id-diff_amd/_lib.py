@@ -124,6 +124,11 @@ _SIGNATURES = {
     "idiff_apsp_f64": (c_i, [c_p, c_i, c_p]),
     "idiff_double_center_scratch_doubles": (c_i64, [c_i]),
     "idiff_double_center_f64": (c_i, [c_p, c_i, c_p, c_p, c_p, c_p]),
+    "idiff_component_labels_f64": (c_i, [c_p, c_i, c_p, c_p, c_p, c_p]),
+    "idiff_component_bridges_workspace_bytes": (c_i64, [c_i]),
+    "idiff_component_bridges_f64": (c_i, [c_p, c_i, c_i, c_p, c_i, c_p, c_i64, c_p, c_p, c_p, c_p]),
+    "idiff_minplus_f64": (c_i, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i, c_i, c_i, c_p]),
+    "idiff_symmetrize_min_f64": (c_i, [c_p, c_i, c_p]),
     "idiff_knn_cross_workspace_bytes": (c_i64, [c_i, c_i]),
     "idiff_knn_cross_f64": (c_i, [c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p]),
     "idiff_isomap_project_scratch_doubles": (c_i64, [c_i]),
@@ -1073,6 +1078,112 @@ def double_center(D, return_means=False):
     if return_means:
         return K, fro2, (-0.5 * scratch[:N], -0.5 * scratch[2 * N])
     return K, fro2
+
+
+# ------------------------------------------------------------------------------------------- a disconnected graph, joined
+# bridge endpoints / N up to which repair_geodesics updates the matrix (above: a second full solve).  NOT MEASURED yet: by operation
+# count the update is 10 % cheaper up to 0.54 (scripts/isomap_connect_bench.py measures it, profiles/isomap_connect_bench.txt)
+UPDATE_MAX_ENDPOINT_FRACTION = 0.5
+
+
+def component_labels(D):
+    """``(labels, count)`` of a shortest-path matrix D [N, N] fp64 (only read): labels [N] int32, 0 .. C - 1 in the order of each
+    component's smallest vertex, and the 0-d int32 device tensor C.  Two vertices share a component exactly when their distance is
+    finite.  No host sync."""
+    N = _square_f64(D, "D")
+    labels = torch.empty(N, dtype=torch.int32, device=D.device)
+    count = torch.empty((), dtype=torch.int32, device=D.device)
+    scratch = torch.empty(N, dtype=torch.int32, device=D.device)
+    _check(lib().idiff_component_labels_f64(D.data_ptr(), N, labels.data_ptr(), count.data_ptr(), scratch.data_ptr(), _stream()),
+           "idiff_component_labels_f64")
+    return labels, count
+
+
+def component_bridges(X, labels, C):
+    """The edges scikit-learn joins C components with: ``(i, j, w)``, int64 [B], int64 [B], fp64 [B] device tensors, B = C (C - 1) / 2.
+    For every component i and every j < i (position i (i - 1) / 2 + j) the point i[.] of component i and the point j[.] of
+    component j at the smallest Euclidean distance w[.] (fp64 from the fp32 rows of X [N, D]); exact ties by the smallest i[.], then
+    the smallest j[.].  labels [N] int32 as ``component_labels`` writes them.  2 <= C <= 1024.  No host sync."""
+    _dev(X, "X"); _dev(labels, "labels", dtype=torch.int32)
+    if X.ndim != 2 or labels.shape != (X.shape[0],):
+        raise RuntimeError(f"component_bridges: X must be [N, D] and labels [N], got {tuple(X.shape)} and {tuple(labels.shape)}")
+    (N, D), C = X.shape, int(C)
+    B = max(C * (C - 1) // 2, 1)
+    ws = torch.empty(max(1, lib().idiff_component_bridges_workspace_bytes(C) // 8), dtype=torch.int64, device=X.device)
+    bi = torch.empty(B, dtype=torch.int64, device=X.device)
+    bj = torch.empty(B, dtype=torch.int64, device=X.device)
+    bw = torch.empty(B, dtype=torch.float64, device=X.device)
+    _check(lib().idiff_component_bridges_f64(X.data_ptr(), N, D, labels.data_ptr(), C, ws.data_ptr(), ws.numel() * 8, bi.data_ptr(),
+                                             bj.data_ptr(), bw.data_ptr(), _stream()), "idiff_component_bridges_f64")
+    return bi, bj, bw
+
+
+def minplus(A, B, C):
+    """C = min(C, A (x) B) in place, the (min, +) product of A [m, p] and B [p, n] into C [m, n] (fp64; each may be a view with
+    unit column stride; C may not overlap A or B); returns C.  No host sync."""
+    for t, name in ((A, "A"), (B, "B"), (C, "C")):
+        _dev(t, name, dtype=torch.float64, contiguous=False)
+        if t.ndim != 2 or t.shape[0] < 1 or t.shape[1] < 1 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+            raise RuntimeError(f"minplus: {name} must be a non-empty matrix with unit column stride, got shape {tuple(t.shape)}, strides {t.stride()}")
+    (m, p), n = A.shape, B.shape[1]
+    if B.shape[0] != p or C.shape != (m, n):
+        raise RuntimeError(f"minplus: shapes {tuple(A.shape)} (x) {tuple(B.shape)} -> {tuple(C.shape)}")
+    ld = lambda t: max(t.stride(0), t.shape[1]) if t.shape[0] > 1 else t.shape[1]
+    _check(lib().idiff_minplus_f64(A.data_ptr(), ld(A), B.data_ptr(), ld(B), C.data_ptr(), ld(C), m, n, p, _stream()), "idiff_minplus_f64")
+    return C
+
+
+def symmetrize_min(G):
+    """G = min(G, G^T) in place (G [N, N] fp64); returns G.  No host sync."""
+    N = _square_f64(G, "G")
+    _check(lib().idiff_symmetrize_min_f64(G.data_ptr(), N, _stream()), "idiff_symmetrize_min_f64")
+    return G
+
+
+def _min_edges(G, bi, bj, bw):
+    """The undirected edges (bi, bj, bw) min-ed into the square matrix G (B <= C (C - 1) / 2 single entries; the pairs are distinct)."""
+    G[bi, bj] = torch.minimum(G[bi, bj], bw)
+    G[bj, bi] = torch.minimum(G[bj, bi], bw)
+    return G
+
+
+def repair_geodesics(D0, bi, bj, bw, route=None, knn=None):
+    """All-pairs shortest paths of the graph behind D0 plus the undirected edges (bi, bj, bw) (device tensors as
+    ``component_bridges`` returns them): D0 [N, N] fp64 holds the shortest paths of that graph, +inf between its components.
+    Returns the repaired matrix (D0 itself, updated in place, on the update route), bit-symmetric with a zero diagonal.
+
+    route="update": with P the p distinct endpoints of the edges, M = D0[P, P] with the edges min-ed in is closed by
+    ``geodesic_distances``; then T = D0[:, P] (x) M and D = min(D0, T (x) D0[P, :]) by ``minplus`` (a shortest path that uses a new
+    edge is a leg inside a component to its first endpoint, a path among endpoints, and a leg from its last endpoint), and
+    ``symmetrize_min``, because the two triangles of the product associate their sums differently.  2 N^2 p + 2 N p^2 + 2 p^3
+    operations.  route="full": the edges go into the neighbourhood graph of ``knn`` = (dist, idx) and ``geodesic_distances`` runs
+    again, 2 N^3 operations.  route=None: "update" while p <= UPDATE_MAX_ENDPOINT_FRACTION * N or without ``knn``.  One host sync
+    (the endpoints are sorted on the host)."""
+    if route not in (None, "update", "full"):
+        raise ValueError(f"repair_geodesics: route = {route!r}, expected 'update', 'full' or None")
+    N = _square_f64(D0, "D0")
+    _dev(bi, "bi", dtype=torch.int64); _dev(bj, "bj", dtype=torch.int64); _dev(bw, "bw", dtype=torch.float64)
+    if bi.ndim != 1 or bi.shape != bj.shape or bi.shape != bw.shape:
+        raise RuntimeError(f"repair_geodesics: bi, bj, bw must be [B], got {tuple(bi.shape)}, {tuple(bj.shape)}, {tuple(bw.shape)}")
+    if bi.numel() == 0:
+        return D0
+    ends = torch.cat([bi, bj])
+    if int(ends.min()) < 0 or int(ends.max()) >= N:
+        raise RuntimeError(f"repair_geodesics: an edge endpoint outside 0..{N - 1}")
+    P = torch.unique(ends)                                       # sorted
+    p = P.numel()
+    if route is None:
+        route = "update" if knn is None or p <= UPDATE_MAX_ENDPOINT_FRACTION * N else "full"
+    if route == "full":
+        if knn is None:
+            raise ValueError("repair_geodesics: route='full' needs knn=(dist, idx), the neighbours the graph is built from")
+        return geodesic_distances(_min_edges(knn_graph(*knn), bi, bj, bw))
+    pos = torch.searchsorted(P, ends)
+    M = _min_edges(D0[P][:, P].contiguous(), pos[:bi.numel()], pos[bi.numel():], bw)
+    geodesic_distances(M)
+    cols, rows = D0[:, P].contiguous(), D0[P].contiguous()       # [N, p], [p, N]: copies, D0 is written below
+    T = minplus(cols, M, cols.clone())
+    return symmetrize_min(minplus(T, rows, D0))
 
 
 def knn_cross(Xq, X, k, workspace=None):

@@ -19,6 +19,9 @@
 //                            reads the same address), B row-major with pitch 64 (16 lanes x 16 bytes = one 256-byte line).
 //                            Entries outside the matrix are +inf in LDS, so the edge tiles need no second code path, and
 //                            are neither loaded from nor stored to G.
+//   idiff_minplus_f64        C = min(C, A (x) B) for rectangular A [m, p], B [p, n]: the device function of phases 2 and 3 over every
+//                            pivot tile of p, one workgroup per tile of C (the repair of a disconnected graph, isomap.py).
+//   idiff_symmetrize_min_f64 G = min(G, G^T), the tile pass of knn_graph on its own.
 //   idiff_double_center_f64  K = -1/2 J (D o D) J from the row means and the grand mean of D o D (D is symmetric, so the
 //                            column means are the row means), and ||K||_F^2 from one partial sum per row: every sum is a
 //                            fixed tree, the result does not depend on the launch.
@@ -90,12 +93,12 @@ __global__ void __launch_bounds__(256) graph_symmetrize_kernel(double *__restric
 }
 
 // ------------------------------------------------------------------------------------------------ shortest paths
-// the tile (ti, tj) of G into LDS (row pitch `ld`), +inf outside the matrix
-__device__ __forceinline__ void load_tile(const double *__restrict__ G, int N, int ti, int tj, double *s, int ld) {
+// the tile (ti, tj) of the rows x cols matrix M (row pitch ldm) into LDS (row pitch `ld`), +inf outside the matrix
+__device__ __forceinline__ void load_tile(const double *M, int rows, int cols, int64_t ldm, int ti, int tj, double *s, int ld) {
   for (int e = threadIdx.x; e < T * T; e += 256) {
     const int r = e >> 6, c = e & 63;
     const int i = ti * T + r, j = tj * T + c;
-    s[r * ld + c] = (i < N && j < N) ? G[(int64_t)i * N + j] : INFINITY;
+    s[r * ld + c] = (i < rows && j < cols) ? M[(int64_t)i * ldm + j] : INFINITY;
   }
 }
 
@@ -104,7 +107,7 @@ __device__ __forceinline__ void load_tile(const double *__restrict__ G, int N, i
 __global__ void __launch_bounds__(256) apsp_diag_kernel(double *__restrict__ G, int N, int b) {
   __shared__ double s[T * T];
   const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-  load_tile(G, N, b, b, s, T);
+  load_tile(G, N, N, N, b, b, s, T);
   __syncthreads();
   double acc[4][4];
   for (int r = 0; r < 4; ++r)
@@ -130,65 +133,78 @@ __global__ void __launch_bounds__(256) apsp_diag_kernel(double *__restrict__ G, 
   }
 }
 
-// C (I, J) = min(C, A (I, b) (x) B (b, J)); As: T x LDA doubles, Bs: T x T doubles.  The tile C may be one of the operands
-// (phase 2): both are complete in LDS before the first store.
-__device__ __forceinline__ void minplus_tile(double *__restrict__ G, int N, int I, int J, int b, double *As, double *Bs) {
+// C (I, J) = min(C, A (I, kb) (x) B (kb, J)) over the pivot tiles kb0 <= kb < kb1, with C [m, n], A [m, p] and B [p, n] of row pitches
+// ldc, lda, ldb; As: T x LDA doubles, Bs: T x T doubles.  The tile C may be one of the operands when there is one pivot tile (phase 2 of
+// the Floyd-Warshall: A = B = C = G): both are complete in LDS before the first store.
+__device__ __forceinline__ void minplus_tile(double *C, int64_t ldc, int m, int n, const double *A, int64_t lda, const double *B,
+                                             int64_t ldb, int p, int I, int J, int kb0, int kb1, double *As, double *Bs) {
   const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-  load_tile(G, N, I, b, As, LDA);
-  load_tile(G, N, b, J, Bs, T);
   const int i0 = I * T + 4 * ty, j0 = J * T + 2 * tx;
   double acc[4][4];
   for (int r = 0; r < 4; ++r)
     for (int c = 0; c < 4; ++c) {
       const int i = i0 + r, j = j0 + (c & 1) + 32 * (c >> 1);
-      acc[r][c] = (i < N && j < N) ? G[(int64_t)i * N + j] : INFINITY;
+      acc[r][c] = (i < m && j < n) ? C[(int64_t)i * ldc + j] : INFINITY;
     }
-  __syncthreads();
-  // two pivots per step, every LDS read 16 bytes wide (LDA and T are even, the bases 16-byte aligned); an odd pivot count
-  // runs one pivot into the +inf padding, which changes nothing
-  const int kmax = min(T, N - b * T);
   const double *ap = As + 4 * ty * LDA, *bp = Bs + 2 * tx;
+  for (int kb = kb0; kb < kb1; ++kb) {
+    if (kb > kb0) __syncthreads();                      // every lane is through with the previous pivot tile
+    load_tile(A, m, p, lda, I, kb, As, LDA);
+    load_tile(B, p, n, ldb, kb, J, Bs, T);
+    __syncthreads();
+    // two pivots per step, every LDS read 16 bytes wide (LDA and T are even, the bases 16-byte aligned); an odd pivot count
+    // runs one pivot into the +inf padding, which changes nothing
+    const int kmax = min(T, p - kb * T);
 #pragma unroll 4
-  for (int k = 0; k < kmax; k += 2) {
-    double2 a[4], b0[2], b1[2];
-    for (int r = 0; r < 4; ++r) a[r] = *reinterpret_cast<const double2 *>(ap + r * LDA + k);
-    for (int h = 0; h < 2; ++h) {
-      b0[h] = *reinterpret_cast<const double2 *>(bp + k * T + 32 * h);
-      b1[h] = *reinterpret_cast<const double2 *>(bp + (k + 1) * T + 32 * h);
+    for (int k = 0; k < kmax; k += 2) {
+      double2 a[4], b0[2], b1[2];
+      for (int r = 0; r < 4; ++r) a[r] = *reinterpret_cast<const double2 *>(ap + r * LDA + k);
+      for (int h = 0; h < 2; ++h) {
+        b0[h] = *reinterpret_cast<const double2 *>(bp + k * T + 32 * h);
+        b1[h] = *reinterpret_cast<const double2 *>(bp + (k + 1) * T + 32 * h);
+      }
+      for (int r = 0; r < 4; ++r)
+        for (int h = 0; h < 2; ++h) {
+          acc[r][2 * h] = fmin(acc[r][2 * h], a[r].x + b0[h].x);
+          acc[r][2 * h + 1] = fmin(acc[r][2 * h + 1], a[r].x + b0[h].y);
+        }
+      for (int r = 0; r < 4; ++r)
+        for (int h = 0; h < 2; ++h) {
+          acc[r][2 * h] = fmin(acc[r][2 * h], a[r].y + b1[h].x);
+          acc[r][2 * h + 1] = fmin(acc[r][2 * h + 1], a[r].y + b1[h].y);
+        }
     }
-    for (int r = 0; r < 4; ++r)
-      for (int h = 0; h < 2; ++h) {
-        acc[r][2 * h] = fmin(acc[r][2 * h], a[r].x + b0[h].x);
-        acc[r][2 * h + 1] = fmin(acc[r][2 * h + 1], a[r].x + b0[h].y);
-      }
-    for (int r = 0; r < 4; ++r)
-      for (int h = 0; h < 2; ++h) {
-        acc[r][2 * h] = fmin(acc[r][2 * h], a[r].y + b1[h].x);
-        acc[r][2 * h + 1] = fmin(acc[r][2 * h + 1], a[r].y + b1[h].y);
-      }
   }
   for (int r = 0; r < 4; ++r)
     for (int c = 0; c < 4; ++c) {
       const int i = i0 + r, j = j0 + (c & 1) + 32 * (c >> 1);
-      if (i < N && j < N) G[(int64_t)i * N + j] = acc[r][c];
+      if (i < m && j < n) C[(int64_t)i * ldc + j] = acc[r][c];
     }
 }
 
 // phase 2: blockIdx.y = 0 the tile (b, x) of row b, 1 the tile (x, b) of column b
-__global__ void __launch_bounds__(256) apsp_cross_kernel(double *__restrict__ G, int N, int b) {
+__global__ void __launch_bounds__(256) apsp_cross_kernel(double *G, int N, int b) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int x = blockIdx.x;
   if (x == b) return;
-  if (blockIdx.y == 0) minplus_tile(G, N, b, x, b, smem, smem + T * LDA);
-  else minplus_tile(G, N, x, b, b, smem, smem + T * LDA);
+  if (blockIdx.y == 0) minplus_tile(G, N, N, N, G, N, G, N, N, b, x, b, b + 1, smem, smem + T * LDA);
+  else minplus_tile(G, N, N, N, G, N, G, N, N, x, b, b, b + 1, smem, smem + T * LDA);
 }
 
 // phase 3: the tile (y, x), neither in row b nor in column b
-__global__ void __launch_bounds__(256) apsp_rest_kernel(double *__restrict__ G, int N, int b) {
+__global__ void __launch_bounds__(256) apsp_rest_kernel(double *G, int N, int b) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int I = blockIdx.y, J = blockIdx.x;
   if (I == b || J == b) return;
-  minplus_tile(G, N, I, J, b, smem, smem + T * LDA);
+  minplus_tile(G, N, N, N, G, N, G, N, N, I, J, b, b + 1, smem, smem + T * LDA);
+}
+
+// the rectangular product: the tile (y, x) of C over every pivot tile of p
+__global__ void __launch_bounds__(256)
+minplus_kernel(const double *__restrict__ A, int64_t lda, const double *__restrict__ B, int64_t ldb, double *__restrict__ C, int64_t ldc,
+               int m, int n, int p) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  minplus_tile(C, ldc, m, n, A, lda, B, ldb, p, blockIdx.y, blockIdx.x, 0, (p + T - 1) / T, smem, smem + T * LDA);
 }
 
 // ------------------------------------------------------------------------------------------------ centring
@@ -251,22 +267,55 @@ IDIFF_API int idiff_knn_graph_f64(const double *dist, const int64_t *idx, int N,
   return launch_status("knn_graph");
 }
 
+constexpr int APSP_LDS = (T * LDA + T * T) * (int)sizeof(double);   // 66,560 bytes: two workgroups per CU
+
+// the three kernels that take APSP_LDS bytes of dynamic LDS, allowed it once per device
+static int allow_tile_lds(const char *what) {
+  static AttrGuard guard;
+  const void *fns[3] = {reinterpret_cast<const void *>(apsp_cross_kernel), reinterpret_cast<const void *>(apsp_rest_kernel),
+                        reinterpret_cast<const void *>(minplus_kernel)};
+  return set_dynamic_lds_once(guard, fns, 3, APSP_LDS, what);
+}
+
 IDIFF_API int idiff_apsp_f64(double *G, int N, void *stream) {
   if (N < 1) return fail("apsp: N = %d, need at least 1 vertex", N);
   if (N > N_MAX) return fail("apsp: N = %d above %d", N, N_MAX);
   if (!G) return fail("apsp: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  constexpr int lds = (T * LDA + T * T) * (int)sizeof(double);      // 66,560 bytes: two workgroups per CU
-  static AttrGuard guard;
-  const void *fns[2] = {reinterpret_cast<const void *>(apsp_cross_kernel), reinterpret_cast<const void *>(apsp_rest_kernel)};
-  if (int rc = set_dynamic_lds_once(guard, fns, 2, lds, "apsp")) return rc;
+  if (int rc = allow_tile_lds("apsp")) return rc;
   const int nt = ceil_div(N, T);
   for (int b = 0; b < nt; ++b) {
     hipLaunchKernelGGL(apsp_diag_kernel, dim3(1), dim3(256), 0, st, G, N, b);
-    hipLaunchKernelGGL(apsp_cross_kernel, dim3(nt, 2), dim3(256), lds, st, G, N, b);
-    hipLaunchKernelGGL(apsp_rest_kernel, dim3(nt, nt), dim3(256), lds, st, G, N, b);
+    hipLaunchKernelGGL(apsp_cross_kernel, dim3(nt, 2), dim3(256), APSP_LDS, st, G, N, b);
+    hipLaunchKernelGGL(apsp_rest_kernel, dim3(nt, nt), dim3(256), APSP_LDS, st, G, N, b);
   }
   return launch_status("apsp");
+}
+
+static bool overlap(const double *a, int64_t na, const double *b, int64_t nb) { return a < b + nb && b < a + na; }
+
+IDIFF_API int idiff_minplus_f64(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int m, int n, int p,
+                                void *stream) {
+  if (m < 1 || n < 1 || p < 1) return fail("minplus: m = %d, n = %d, p = %d, need at least 1 each", m, n, p);
+  if (m > N_MAX || n > N_MAX || p > N_MAX) return fail("minplus: m = %d, n = %d, p = %d above %d", m, n, p, N_MAX);
+  if (!A || !B || !C) return fail("minplus: null pointer");
+  if (lda < p || ldb < n || ldc < n || lda > N_MAX || ldb > N_MAX || ldc > N_MAX)
+    return fail("minplus: row pitches %lld, %lld, %lld for rows of %d, %d, %d entries", (long long)lda, (long long)ldb, (long long)ldc, p, n, n);
+  const int64_t na = (int64_t)(m - 1) * lda + p, nb = (int64_t)(p - 1) * ldb + n, nc = (int64_t)(m - 1) * ldc + n;
+  if (overlap(C, nc, A, na) || overlap(C, nc, B, nb)) return fail("minplus: C overlaps an operand");
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = allow_tile_lds("minplus")) return rc;
+  hipLaunchKernelGGL(minplus_kernel, dim3(ceil_div(n, T), ceil_div(m, T)), dim3(256), APSP_LDS, st, A, lda, B, ldb, C, ldc, m, n, p);
+  return launch_status("minplus");
+}
+
+IDIFF_API int idiff_symmetrize_min_f64(double *G, int N, void *stream) {
+  if (N < 1) return fail("symmetrize_min: N = %d, need at least 1 vertex", N);
+  if (N > N_MAX) return fail("symmetrize_min: N = %d above %d", N, N_MAX);
+  if (!G) return fail("symmetrize_min: null pointer");
+  const int nt = ceil_div(N, ST);
+  hipLaunchKernelGGL(graph_symmetrize_kernel, dim3(nt, nt), dim3(256), 0, (hipStream_t)stream, G, N);
+  return launch_status("symmetrize_min");
 }
 
 IDIFF_API int64_t idiff_double_center_scratch_doubles(int N) { return N < 1 || N > N_MAX ? 0 : 2 * (int64_t)N + 1; }

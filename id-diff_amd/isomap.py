@@ -18,7 +18,15 @@ already at hand), embedding = V sqrt(lambda) with scikit-learn's column signs.  
 ``_lib.knn_cross`` -> ``_lib.isomap_project`` (csrc/isomap_project.hip).  ``run(embed=True)`` writes the embeddings and, given
 labels and scikit-learn, the random-forest scores the reference computes on them (isomap.py:56-67), fitted on the host.
 
-Not here: more than one GPU, n_components > 64, radius neighbourhoods, scikit-learn's repair of a disconnected graph.
+A neighbourhood graph that is not connected raises by default (``connect="raise"``).  ``connect="closest"`` does what scikit-learn
+does without being asked (``sklearn.utils.graph._fix_connected_components``, mode "distance"): it joins every two components by
+the closest pair of points between them, warns once, and carries on.  The components are read off the first shortest-path matrix
+(``_lib.component_labels``), the closest pairs are an fp64 brute force over the pairs of points of different components
+(``_lib.component_bridges``, csrc/graph_connect.hip), and the matrix is updated through the few endpoints of the new edges instead
+of being solved again (``_lib.repair_geodesics``).  ``component_labels``, ``bridges_from_points`` and ``repair_geodesics`` below
+restate the three steps in numpy.  At most 1024 components.
+
+Not here: more than one GPU, n_components > 64, radius neighbourhoods.
 """
 import os
 import pickle
@@ -33,6 +41,8 @@ from .mle import _points
 N_MAX = 12288                  # the largest matrix the eigensolver is exercised at in this project
 _SMALL_POS_RATIO = 1e-12       # an eigenvalue counts as positive above this fraction of the largest (sklearn's fp64 ratio)
 DEFAULT_KS = list(range(1, 11)) + list(range(11, 200, 10))        # isomap.py:51
+C_MAX = 1024                   # most connected components connect="closest" joins (523,776 pairs of them)
+CONNECT = ("raise", "closest")
 
 
 # ------------------------------------------------------------------------------------------- host arithmetic
@@ -43,6 +53,65 @@ def count_components(finite):
     if finite.ndim != 2 or finite.shape[0] != finite.shape[1]:
         raise ValueError(f"finite pattern must be [N, N], got {finite.shape}")
     return int(np.unique(finite.argmax(axis=1)).size)
+
+
+def _check_connect(connect):
+    if connect not in CONNECT:
+        raise ValueError(f"connect = {connect!r}, expected one of {CONNECT}")
+    return connect
+
+
+def _check_count(C):
+    if C > C_MAX:
+        raise ValueError(f"the neighbourhood graph has {C} connected components: connect='closest' joins at most {C_MAX}")
+    return C
+
+
+def component_labels(finite):
+    """Component labels [N] (int64) from the finite pattern [N, N] (bool) of a shortest-path matrix: 0 .. C - 1 in the order of each
+    component's smallest vertex, as ``scipy.sparse.csgraph.connected_components`` numbers them."""
+    finite = np.asarray(finite, dtype=bool)
+    if finite.ndim != 2 or finite.shape[0] != finite.shape[1]:
+        raise ValueError(f"finite pattern must be [N, N], got {finite.shape}")
+    first = finite.argmax(axis=1)
+    return np.searchsorted(np.unique(first), first).astype(np.int64)
+
+
+def bridges_from_points(X, labels):
+    """The edges scikit-learn joins the components with (``_fix_connected_components``, mode "distance"), in numpy fp64 from the fp32
+    values of X [N, D]: ``(i, j, w)``, int64 [B], int64 [B], fp64 [B], B = C (C - 1) / 2.  For every component a = 0 .. C - 1 and every
+    b < a, the pair (i in a, j in b) of smallest Euclidean distance w (the square root of the sum of squared differences); on an
+    exact tie the first in row-major order over (rank of i in a, rank of j in b), ranks by ascending index: ``D.argmin()`` on
+    ``X[idx_a]`` x ``X[idx_b]``.  More than 1024 components raise ``ValueError``."""
+    X = np.asarray(X, dtype=np.float32).astype(np.float64)
+    labels = np.asarray(labels).astype(np.int64)
+    if X.ndim != 2 or labels.shape != (X.shape[0],):
+        raise ValueError(f"X must be [N, D] and labels [N], got {X.shape} and {labels.shape}")
+    C = _check_count(int(labels.max()) + 1 if labels.size else 0)
+    members = [np.flatnonzero(labels == c) for c in range(C)]
+    bi, bj, bw = [], [], []
+    for a in range(C):
+        for b in range(a):
+            diff = X[members[a]][:, None, :] - X[members[b]][None, :, :]
+            d = np.sqrt((diff * diff).sum(axis=2))
+            ii, jj = np.unravel_index(d.argmin(), d.shape)
+            bi.append(members[a][ii]); bj.append(members[b][jj]); bw.append(d[ii, jj])
+    return np.array(bi, dtype=np.int64), np.array(bj, dtype=np.int64), np.array(bw, dtype=np.float64)
+
+
+def repair_geodesics(D0, bridges):
+    """All-pairs shortest paths of the graph behind D0 [N, N] (its shortest paths, +inf between components) plus the undirected edges
+    ``bridges`` = (i, j, w), in numpy fp64: the edges are min-ed in, then one Floyd-Warshall step per distinct endpoint (a path
+    that uses a new edge passes only endpoints between its two legs inside a component, and those legs are entries of D0)."""
+    D = np.array(D0, dtype=np.float64)
+    if D.ndim != 2 or D.shape[0] != D.shape[1]:
+        raise ValueError(f"D0 must be [N, N], got {D.shape}")
+    bi, bj, bw = (np.asarray(v) for v in bridges)
+    D[bi, bj] = np.minimum(D[bi, bj], bw)
+    D[bj, bi] = np.minimum(D[bj, bi], bw)
+    for k in np.unique(np.concatenate([bi, bj])).astype(np.int64):
+        np.minimum(D, D[:, k:k + 1] + D[k:k + 1, :], out=D)
+    return D
 
 
 def n_positive(lam):
@@ -124,44 +193,69 @@ def _n_rows(X):
     return int(X.shape[0]) if hasattr(X, "shape") else len(X)
 
 
-def geodesics(X, n_neighbors=5):
-    """Geodesic distances [N, N] (fp64 device tensor) of the points X over their ``n_neighbors``-nearest-neighbour graph.
+_NO_BRIDGES = (np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.float64))
 
-    Raises ``ValueError`` naming the number of connected components when some pair is unreachable.  scikit-learn instead
-    joins the components with extra edges (the closest pair of points between each two) and warns; we do not: a curve from
-    such a repaired graph measures the repair."""
+
+def _geodesics(X, n_neighbors, connect):
+    """(D, number of components of the neighbourhood graph, the bridges (i, j, w) as numpy): what ``geodesics`` documents."""
+    _check_connect(connect)
     Xd = _points(X)
     dist, idx, _ = _lib.knn(Xd, int(n_neighbors))
     D = _lib.geodesic_distances(_lib.knn_graph(dist, idx))
-    finite = torch.isfinite(D)
-    if not bool(finite.all()):
-        raise ValueError(f"the {n_neighbors}-nearest-neighbour graph of the {Xd.shape[0]} points has "
-                         f"{count_components(finite.cpu().numpy())} connected components: geodesic distances between them "
-                         "are infinite (raise n_neighbors)")
-    return D
+    if connect == "raise":
+        finite = torch.isfinite(D)
+        if not bool(finite.all()):
+            raise ValueError(f"the {n_neighbors}-nearest-neighbour graph of the {Xd.shape[0]} points has "
+                             f"{count_components(finite.cpu().numpy())} connected components: geodesic distances between them "
+                             "are infinite (raise n_neighbors)")
+        return D, 1, _NO_BRIDGES
+    labels, count = _lib.component_labels(D)
+    C = int(count)                                               # the one host read the default path spends on isfinite().all()
+    if C == 1:
+        return D, 1, _NO_BRIDGES
+    _check_count(C)
+    warnings.warn(f"isomap: the {n_neighbors}-nearest-neighbour graph of the {Xd.shape[0]} points has {C} connected components; "
+                  "connect='closest' joins every two of them by their closest pair of points, as scikit-learn does", UserWarning,
+                  stacklevel=3)
+    bi, bj, bw = _lib.component_bridges(Xd, labels, C)
+    D = _lib.repair_geodesics(D, bi, bj, bw, knn=(dist, idx))
+    return D, C, (bi.cpu().numpy(), bj.cpu().numpy(), bw.cpu().numpy())
 
 
-def _kernel_spectrum(X, n_neighbors, return_geodesics=False):
-    """(||K||_F^2, eigenvalues of K descending [numpy fp64], N): one geodesic matrix, one centring, one eigensolve."""
+def geodesics(X, n_neighbors=5, connect="raise"):
+    """Geodesic distances [N, N] (fp64 device tensor) of the points X over their ``n_neighbors``-nearest-neighbour graph.
+
+    ``connect="raise"``: raises ``ValueError`` naming the number of connected components when some pair is unreachable: a curve
+    from a repaired graph measures the repair.  ``connect="closest"``: what scikit-learn does instead.  It joins the components
+    with extra edges (the closest pair of points between each two), warns once with their number, and returns the shortest paths
+    of the joined graph; on a connected graph it changes nothing and does not warn."""
+    return _geodesics(X, n_neighbors, connect)[0]
+
+
+def _kernel_spectrum(X, n_neighbors, return_geodesics=False, connect="raise"):
+    """(||K||_F^2, eigenvalues of K descending [numpy fp64], N): one geodesic matrix, one centring, one eigensolve.
+    ``return_geodesics=True`` adds (D, number of components, bridges)."""
+    _check_connect(connect)
     N = _n_rows(X)
     if N > N_MAX:
         raise ValueError(f"N = {N} points: the eigensolver of this project is exercised up to N = {N_MAX}")
-    D = geodesics(X, n_neighbors)
+    D, C, bridges = _geodesics(X, n_neighbors, connect)
     K, fro2 = _lib.double_center(D)
     eig = _lib.sym_eigvals(K)                               # K is overwritten
     if bool(torch.isnan(eig).any()):
         eig = _lib.solve_with_fallbacks(lambda: _lib.sym_eigvals(_lib.double_center(D)[0]))
     out = float(fro2), eig.cpu().numpy()[::-1].copy(), N
-    return out + (D,) if return_geodesics else out
+    return out + (D, C, bridges) if return_geodesics else out
 
 
-def reconstruction_errors(X, ks, n_neighbors=5, return_eigenvalues=False):
+def reconstruction_errors(X, ks, n_neighbors=5, return_eigenvalues=False, connect="raise"):
     """``[Isomap(n_neighbors=n_neighbors, n_components=k).fit(X).reconstruction_error() for k in ks]`` as a list of floats.
     ``return_eigenvalues=True`` adds the eigenvalues of the centred kernel (descending, all N, fp64 numpy).  A k above the
     number of positive eigenvalues (those above 1e-12 of the largest) raises ``ValueError``.  scikit-learn raises where the top
     k include a significantly negative eigenvalue and sets tiny ones to zero without raising: in the narrow band of a k that
-    reaches only eigenvalues within 1e-12 of zero it returns a value where this function raises.  N is limited to 12288."""
-    fro2, lam, N = _kernel_spectrum(X, n_neighbors)
+    reaches only eigenvalues within 1e-12 of zero it returns a value where this function raises.  N is limited to 12288.
+    ``connect``: as in ``geodesics``."""
+    fro2, lam, N = _kernel_spectrum(X, n_neighbors, connect=connect)
     err = errors_from_eigenvalues(fro2, lam, N, ks)
     return (err, lam) if return_eigenvalues else err
 
@@ -173,18 +267,21 @@ class Isomap:
     """``sklearn.manifold.Isomap(n_neighbors, n_components)`` on the device path of this module: ``fit`` / ``fit_transform`` /
     ``transform`` / ``reconstruction_error``.  After ``fit``: ``embedding_`` [N, k] fp64 device tensor (= V sqrt(lambda), each
     column's entry of largest magnitude positive, as scikit-learn's ``svd_flip`` leaves it), ``dist_matrix_`` [N, N] fp64 device
-    tensor (the geodesic distances), ``eigenvalues_`` [k] fp64 numpy, descending.  A disconnected neighbourhood graph, N > 12288 and
-    an n_components above the number of positive eigenvalues raise ``ValueError`` as ``reconstruction_errors`` does; a basis whose
-    residual exceeds 1e-9 lambda_1 sqrt(k) raises ``RuntimeError``.  n_components <= 64."""
+    tensor (the geodesic distances), ``eigenvalues_`` [k] fp64 numpy, descending, ``n_connected_components_`` (int) of the
+    neighbourhood graph and ``bridges_`` = (i, j, w), numpy int64 [B], int64 [B], fp64 [B], the edges ``connect="closest"`` joined
+    them with (B = C (C - 1) / 2; empty for one component).  A disconnected neighbourhood graph (unless ``connect="closest"``, see
+    ``geodesics``), N > 12288 and an n_components above the number of positive eigenvalues raise ``ValueError`` as
+    ``reconstruction_errors`` does; a basis whose residual exceeds 1e-9 lambda_1 sqrt(k) raises ``RuntimeError``.  n_components <= 64."""
 
-    def __init__(self, n_neighbors=5, n_components=2):
-        self.n_neighbors, self.n_components = int(n_neighbors), int(n_components)
+    def __init__(self, n_neighbors=5, n_components=2, connect="raise"):
+        self.n_neighbors, self.n_components, self.connect = int(n_neighbors), int(n_components), _check_connect(connect)
         if not 1 <= self.n_components <= _lib.TOPVECS_MAX:
             raise ValueError(f"n_components = {n_components} outside 1..{_lib.TOPVECS_MAX}")
 
     def fit(self, X):
         k = self.n_components
-        fro2, lam, N, D = _kernel_spectrum(X, self.n_neighbors, return_geodesics=True)     # refuses N > 12288 before any device call
+        fro2, lam, N, D, C, bridges = _kernel_spectrum(X, self.n_neighbors, return_geodesics=True, connect=self.connect)   # refuses N > 12288 before any device call
+        self.n_connected_components_, self.bridges_ = int(C), bridges
         self._error = errors_from_eigenvalues(fro2, lam, N, [k])[0]           # raises for k beyond the positive eigenvalues
         self.plan_ = _lib.topvecs_plan(lam, k)
         K, _, (colmean, grand) = _lib.double_center(D, return_means=True)     # again: the eigenvalue solver has overwritten K
@@ -244,7 +341,7 @@ def _first_rows(loader, N):
     return torch.cat(rows, dim=0)[:N], (torch.cat(labels)[:N].cpu().numpy() if labels else None)
 
 
-def _embed(DataModule, X, y, N, ks, out_dir, n_neighbors, pos):
+def _embed(DataModule, X, y, N, ks, out_dir, n_neighbors, pos, connect="raise"):
     """The ``embed=True`` part of ``run``: embedding.pkl ({k: [N, k] array} for k in (2, 3)) and, with labels and scikit-learn,
     clf_scores.pkl ({k: accuracy} for every k <= 64 of ``ks``).  ONE fit, at the largest k asked for: column i of the embedding
     and of ``transform`` belongs to eigenvalue i whatever n_components is, so the embedding of k components is the first k
@@ -254,7 +351,7 @@ def _embed(DataModule, X, y, N, ks, out_dir, n_neighbors, pos):
     iso, refused = None, []
     while wanted and iso is None:
         try:
-            iso = Isomap(n_neighbors, wanted[-1]).fit(X)
+            iso = Isomap(n_neighbors, wanted[-1], connect=connect).fit(X)
         except ValueError as e:
             if "topvecs_plan" not in str(e):
                 raise
@@ -283,18 +380,20 @@ def _embed(DataModule, X, y, N, ks, out_dir, n_neighbors, pos):
     return emb, scores
 
 
-def run(config, N=1000, ks=None, out_dir='isomap', n_neighbors=5, embed=False):
+def run(config, N=1000, ks=None, out_dir='isomap', n_neighbors=5, embed=False, connect="raise"):
     """isomap.py:37-75 of the reference: the first N points of the train loader, the error for every k of ``ks`` (default the
     reference's list) into ``out_dir/reconstruction_error.pkl`` (a plain list of floats) and, when matplotlib imports,
     ``reconstruction_error.png``.  Values of k beyond the positive eigenvalues are cut off with one warning.  -> (ks, errors)
     ``embed=True`` also writes ``embedding.pkl`` (n_components 2 and 3) and, when the loaders yield labels and scikit-learn
-    imports, ``clf_scores.pkl``: the random-forest accuracy on the transformed test points for every k <= 64 of ``ks``."""
+    imports, ``clf_scores.pkl``: the random-forest accuracy on the transformed test points for every k <= 64 of ``ks``.
+    ``connect``: as in ``geodesics``; checked before the data are loaded."""
     from .lightning_data_modules.utils import create_lightning_datamodule
+    _check_connect(connect)
     ks = list(DEFAULT_KS if ks is None else ks)
     DataModule = create_lightning_datamodule(config)
     DataModule.setup()
     X, y = _first_rows(DataModule.train_dataloader(), N)
-    fro2, lam, n = _kernel_spectrum(X, n_neighbors)
+    fro2, lam, n = _kernel_spectrum(X, n_neighbors, connect=connect)
     pos = n_positive(lam)
     kept = [k for k in ks if k <= pos]
     if len(kept) < len(ks):
@@ -313,7 +412,7 @@ def run(config, N=1000, ks=None, out_dir='isomap', n_neighbors=5, embed=False):
         fig.subplots().plot(kept, values)
         fig.savefig(os.path.join(out_dir, 'reconstruction_error.png'), dpi=300, facecolor='white')
     if embed:
-        _embed(DataModule, X, y, N, kept, out_dir, n_neighbors, pos)
+        _embed(DataModule, X, y, N, kept, out_dir, n_neighbors, pos, connect)
     return kept, values
 
 
@@ -326,8 +425,12 @@ def main(argv=None):
     ap.add_argument('--n_neighbors', type=int, default=5)
     ap.add_argument('--out_dir', default='isomap')
     ap.add_argument('--embed', action='store_true', help='also write embedding.pkl and, with labels and scikit-learn, clf_scores.pkl')
+    ap.add_argument('--connect', choices=CONNECT, default='raise',
+                    help="a disconnected neighbourhood graph: 'raise' (default) or 'closest', scikit-learn's repair (join every two "
+                         "components by their closest pair of points, with a warning)")
     args = ap.parse_args(argv)
-    ks, values = run(read_config(args.config), N=args.N, out_dir=args.out_dir, n_neighbors=args.n_neighbors, embed=args.embed)
+    ks, values = run(read_config(args.config), N=args.N, out_dir=args.out_dir, n_neighbors=args.n_neighbors, embed=args.embed,
+                     connect=args.connect)
     for k, v in zip(ks, values):
         print(f'k = {k}  reconstruction error: {v}')
 

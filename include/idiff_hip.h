@@ -545,6 +545,35 @@ int64_t idiff_isomap_project_scratch_doubles(int c);
 int idiff_isomap_project_f64(const double *dist, const int64_t *idx, int M, int k, const double *D, int N, const double *A, int c,
                              const double *colmean, const double *grand, double *Z, double *scratch, void *stream);
 
+/* A disconnected neighbourhood graph joined the way scikit-learn joins it (sklearn.utils.graph._fix_connected_components,
+ * mode="distance"): between every two components one edge, the closest pair of points.  No host synchronisation, no allocation;
+ * IDIFF_EINVAL and nothing launched for arguments outside what is stated.
+ *
+ * component_labels: D [N, N] a shortest-path matrix (symmetric pattern of finite entries, finite diagonal), 1 <= N <= 2^20 ->
+ * labels [N] in 0 .. C - 1, numbered in the order of each component's smallest vertex (scipy's connected_components numbers
+ * them so), and *count = C (device scalar).  scratch: N int32.
+ *
+ * component_bridges: X [N, D] fp32, labels [N] with every value of 0 .. C - 1 present, 2 <= C <= 1024 -> for i = 1 .. C - 1 and
+ * j < i, at position i (i - 1) / 2 + j: bi = the point a of component i and bj = the point b of component j with the smallest
+ * sqrt(sum_d (a_d - b_d)^2), evaluated in fp64 from the fp32 coordinates (fused multiply-adds in ascending d), bw that distance.
+ * Equal distances: the smallest a, then the smallest b, whatever the launch order (two passes of unsigned 64-bit atomic
+ * minima; no floating-point atomics).  A label outside 0 .. C - 1 is dropped, never an address; a pair of components without
+ * points comes back as (-1, -1, +inf).  workspace: idiff_component_bridges_workspace_bytes(C) bytes, 8-byte aligned (0 for a
+ * C the call refuses).
+ *
+ * minplus: C = min(C, A (x) B) in the (min, +) semiring, A [m, p], B [p, n], C [m, n] fp64 with row pitches lda, ldb, ldc (in
+ * doubles, at least the row lengths), 1 <= m, n, p <= 2^20; C may not overlap A or B.  The device function of phases 2 and 3 of
+ * apsp over every pivot tile of p.  Non-negative entries or +inf, no NaN.  2 m n p fp64 operations.
+ *
+ * symmetrize_min: G = min(G, G^T) in place, G [N, N]: the tile pass that ends knn_graph. */
+int idiff_component_labels_f64(const double *D, int N, int32_t *labels, int32_t *count, int32_t *scratch, void *stream);
+int64_t idiff_component_bridges_workspace_bytes(int C);
+int idiff_component_bridges_f64(const float *X, int N, int D, const int32_t *labels, int C, void *workspace, int64_t workspace_bytes,
+                                int64_t *bi, int64_t *bj, double *bw, void *stream);
+int idiff_minplus_f64(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int m, int n, int p,
+                      void *stream);
+int idiff_symmetrize_min_f64(double *G, int N, void *stream);
+
 /* ------------------------------------------------------------------ image manifolds of known dimension */
 
 /* The two fixed image manifolds of lightning_data_modules/SyntheticDataset.py:81-183, one workgroup per image, out
