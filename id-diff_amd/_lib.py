@@ -75,6 +75,9 @@ _SIGNATURES = {
     "idiff_wino1d_pack_f32": (c_i, [c_p, c_p, c_i, c_i, c_p]),
     "idiff_conv2d_wino1d_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(Epilogue), c_p]),
     "idiff_conv2d_wino1d_gn_ok": (c_i, [c_i] * 6),
+    "idiff_conv2d_wino1d_normload_ok": (c_i, [c_i] * 5),
+    "idiff_conv2d_wino1d_normload_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(Epilogue), c_p, c_i, c_p]),
+    "idiff_groupnorm_coef_f32": (c_i, [c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p]),
     "idiff_conv2d_wino1d_gn_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(Epilogue), c_i, c_p, c_p, c_f, c_i, c_p]),
     "idiff_conv2d_winograd_split_ok": (c_i, [c_i] * 5),
     "idiff_winograd_split_weight_floats": (c_i64, [c_i, c_i]),
@@ -277,10 +280,21 @@ def with_groupnorm(ep, groups, gamma, beta, eps, act):
     return ep
 
 
+def with_normload(ep, coef, act):
+    """Ask the convolution that consumes ``ep`` to apply the GroupNorm (+ ``act``: "silu" or None) in FRONT of it in its own loader:
+    ``coef`` [B, Cin, 2] from groupnorm_coef, the input handed to the launch is the norm's RAW input.  Rides beside the C struct as
+    with_groupnorm's request does; conv2d_wino1d serves it through idiff_conv2d_wino1d_normload_f32, every other wrapper refuses it."""
+    _dev(coef, "coef")
+    ep.normload = (coef, ACT[act])
+    return ep
+
+
 def _ep_ref(epilogue, what):
     """The epilogue argument of a launch that has no fused GroupNorm: such a request is an error, never dropped."""
     if epilogue is None:
         return None
+    if getattr(epilogue, "normload", None) is not None:
+        raise RuntimeError(f"{what}: the epilogue asks for a GroupNorm in the loader (with_normload), which only conv2d_wino1d serves")
     if getattr(epilogue, "groupnorm", None) is not None:
         raise RuntimeError(f"{what}: the epilogue asks for a fused GroupNorm (with_groupnorm), which only conv2d_wino1d serves")
     return ctypes.byref(epilogue)
@@ -496,6 +510,16 @@ def _wino_conv(stem, packed_by, x, u, out, B, H, W, Cin, Cout, epilogue):
     if u.numel() != want:
         raise RuntimeError(f"conv2d_{stem}: a filter bank of {u.numel()} floats ({want} expected): pack it with {packed_by}")
     gn = getattr(epilogue, "groupnorm", None)
+    nl = getattr(epilogue, "normload", None)
+    if nl is not None and stem == "wino1d":
+        if gn is not None:
+            raise RuntimeError("conv2d_wino1d: a GroupNorm in the loader (with_normload) and one in the tail (with_groupnorm) in one launch")
+        coef, act = nl
+        if coef.numel() != B * Cin * 2:
+            raise RuntimeError(f"conv2d_wino1d: {coef.numel()} loader coefficients for [B, Cin, 2] = [{B}, {Cin}, 2]")
+        _check(lib().idiff_conv2d_wino1d_normload_f32(x.data_ptr(), u.data_ptr(), out.data_ptr(), B, H, W, Cin, Cout, ctypes.byref(epilogue),
+                                                      coef.data_ptr(), act, _stream()), "idiff_conv2d_wino1d_normload_f32")
+        return out
     if gn is not None and stem == "wino1d":
         groups, gamma, beta, eps, act = gn
         if gamma.numel() != Cout or beta.numel() != Cout:
@@ -574,6 +598,22 @@ def conv2d_wino1d_gn_ok(B, H, W, Cin, Cout, groups):
     """True when conv2d_wino1d also applies the GroupNorm (``groups`` groups) + activation behind it (with_groupnorm): maps of at most 256
     pixels in rows of at most 16, group widths that divide 64; off under IDIFF_NO_FUSED_GN and wherever conv2d_wino1d_ok is."""
     return bool(lib().idiff_conv2d_wino1d_gn_ok(B, H, W, Cin, Cout, groups))
+
+
+def conv2d_wino1d_normload_ok(B, H, W, Cin, Cout):
+    """True where conv2d_wino1d applies the GroupNorm (+ SiLU) in front of it in its loader (with_normload) and that was measured faster than
+    the pass: rows of 32 pixels; off under IDIFF_NO_FUSED_GN_LOAD, IDIFF_NO_PAIRS and wherever conv2d_wino1d_ok is."""
+    return bool(lib().idiff_conv2d_wino1d_normload_ok(B, H, W, Cin, Cout))
+
+
+def groupnorm_coef(ws1, ns1, C1, ws2, ns2, C2, B, HW, G, eps, gamma, beta, coef):
+    """coef [B, C1 + C2, 2] = (rstd gamma, beta - mean rstd gamma) from the producers' column sums (one launch, no pass over the activations)."""
+    _dev(coef, "coef"); _dev(gamma, "gamma"); _dev(beta, "beta")
+    if coef.numel() != B * (C1 + (C2 if ws2 is not None else 0)) * 2:
+        raise RuntimeError(f"groupnorm_coef: coef holds {coef.numel()} floats, [B, C, 2] = {B * (C1 + C2) * 2} expected")
+    _check(lib().idiff_groupnorm_coef_f32(ws1.data_ptr(), ns1, C1, _ptr(ws2), ns2, C2, B, HW, G, eps, gamma.data_ptr(), beta.data_ptr(),
+                                          coef.data_ptr(), _stream()), "idiff_groupnorm_coef_f32")
+    return coef
 
 
 def wino1d_pack(wt, Cin, Cout):

@@ -88,6 +88,33 @@ __global__ void gn_finalize2_kernel(const double *__restrict__ ws1, int ns1, int
   stats[2 * i + 1] = (float)(1.0 / sqrt(var + (double)eps));
 }
 
+// The GroupNorm as one affine pair per (sample, channel), for a consumer that applies it itself (the loader of wino1d_nl_kernel):
+// y = a x + b with a = rstd gamma, b = beta - mean rstd gamma.  The statistics from the column sums as gn_finalize2_kernel forms them (same
+// order, fp64); the pair is formed in fp64 as well and rounded once.
+__global__ void gn_coef_kernel(const double *__restrict__ ws1, int ns1, int C1, const double *__restrict__ ws2, int ns2, int C2, int B, int G,
+                               int HW, float eps, const float *__restrict__ gamma, const float *__restrict__ beta, float *__restrict__ coef) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * G) return;
+  const int b = i / G, g = i - b * G, Ctot = C1 + C2, cpg = Ctot / G;
+  double s = 0, q = 0;
+  for (int c = g * cpg; c < (g + 1) * cpg; ++c) {
+    const bool first = c < C1;
+    const double *w = first ? ws1 + ((int64_t)b * ns1 * C1 + c) * 2 : ws2 + ((int64_t)b * ns2 * C2 + (c - C1)) * 2;
+    const int ns = first ? ns1 : ns2, Cs = first ? C1 : C2;
+    for (int sp = 0; sp < ns; ++sp) { s += w[(int64_t)sp * Cs * 2]; q += w[(int64_t)sp * Cs * 2 + 1]; }
+  }
+  const double n = (double)cpg * HW;
+  const double mean = s / n;
+  double var = q / n - mean * mean;
+  if (var < 0) var = 0;
+  const double rstd = 1.0 / sqrt(var + (double)eps);
+  for (int c = g * cpg; c < (g + 1) * cpg; ++c) {
+    const double a = rstd * (double)gamma[c];
+    coef[((int64_t)b * Ctot + c) * 2] = (float)a;
+    coef[((int64_t)b * Ctot + c) * 2 + 1] = (float)((double)beta[c] - mean * a);
+  }
+}
+
 __global__ void __launch_bounds__(256)
 gn_apply_kernel(const float *__restrict__ x, int C, const float *__restrict__ x2, int C2, int HW, int G,
                 const float *__restrict__ stats, const float *__restrict__ gamma, const float *__restrict__ beta,
@@ -548,6 +575,17 @@ IDIFF_API int idiff_groupnorm_finalize_f32(const double *ws1, int nsplit1, int C
   hipLaunchKernelGGL(gn_finalize2_kernel, dim3(ceil_div(B * G, 256)), dim3(256), 0, (hipStream_t)stream, ws1, nsplit1, C1, ws2,
                      nsplit2, C2, B, G, HW, eps, stats);
   return launch_status("groupnorm_finalize");
+}
+
+IDIFF_API int idiff_groupnorm_coef_f32(const double *ws1, int nsplit1, int C1, const double *ws2, int nsplit2, int C2, int B, int HW, int G,
+                                       float eps, const float *gamma, const float *beta, float *coef, void *stream) {
+  if (!ws1 || !gamma || !beta || !coef || B <= 0 || HW <= 0 || C1 <= 0 || nsplit1 <= 0 || G <= 0) return fail("groupnorm_coef: bad arguments");
+  if (!ws2) { C2 = 0; nsplit2 = 0; }
+  if (ws2 && (C2 <= 0 || nsplit2 <= 0)) return fail("groupnorm_coef: second source needs C2, nsplit2 > 0");
+  if ((C1 + C2) % G) return fail("groupnorm_coef: channels not divisible by groups");
+  hipLaunchKernelGGL(gn_coef_kernel, dim3(ceil_div(B * G, 256)), dim3(256), 0, (hipStream_t)stream, ws1, nsplit1, C1, ws2, nsplit2, C2, B, G,
+                     HW, eps, gamma, beta, coef);
+  return launch_status("groupnorm_coef");
 }
 
 namespace {

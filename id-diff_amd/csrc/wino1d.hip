@@ -117,6 +117,8 @@ struct Wino1dParams {
   const float *gn_gamma, *gn_beta;                 // the fused GroupNorm of wino1d_gn_kernel: [Cout] each, groups of gn_cpg channels
   int gn_cpg, gn_act;
   float gn_eps;
+  const float *nl_coef;                            // wino1d_nl_kernel: [B][Cin][2] = (a, b) of the GroupNorm in FRONT of this convolution, x -> act(a x + b)
+  uint32_t nl_bytes;
   float c_nb2, c_na2, c_nab2, c_a, c_b;            // the transform's constants as kernel arguments (SGPR operands of plain fmas)
 #ifdef IDIFF_W1D_STAMP
   uint64_t *stamps;                                // diagnostic build (scripts/wino1d_stamps.py): 8 ticks of 100 MHz per workgroup
@@ -124,8 +126,11 @@ struct Wino1dParams {
 };
 
 // GN: the tail of wino1d_gn_kernel (GroupNorm + activation of the output inside the workgroup) instead of the epilogue's switches
-template <int W, bool GN>
+// NL: the loader of wino1d_nl_kernel (0: none): the GroupNorm that PRODUCES the input, as one affine pair per (image, channel), (NL = 2:) + SiLU,
+//     applied to the pixel registers in front of B^T d; W = 32 only (a block is half an image: one image's coefficients per workgroup)
+template <int W, bool GN, int NL = 0>
 __device__ __forceinline__ void r1_body(const Wino1dParams &p) {
+  static_assert(NL == 0 || (W == 32 && !GN), "the norm in the loader: 32-pixel rows, the plain tail");
   using G = R1Geo<W>;
   constexpr int TPR = G::TPR, RB = G::RB, POS = G::POS_BYTES, BRING = R1_BRING;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -296,6 +301,62 @@ __device__ __forceinline__ void r1_body(const Wino1dParams &p) {
     __builtin_amdgcn_sched_barrier(0);
   };
 
+  // ---------------------------------------------------------------- NL: act(a x + b) on the pixel registers
+  // The block's rows belong to ONE image (H % RB == 0, checked by the launcher), so a K step needs 16 (a, b) pairs, and lane lm the two of its
+  // channel pair: one 16-byte load per lane and step.  Every pixel register is rewritten in place exactly once between its arrival and the
+  // staging of the first row-tile that reads it (a tile's pixels 4, 5 are the next tile's 0, 1: row-tile 0 owns six pixels, the others four),
+  // in UNITS of one transcendental each (a pixel = two channels = four units), the K loop deals one unit to a gap:
+  //   0  z = a x + b (both channels), e0 = 2^(-log2(e) z0)     1  e1, 1 + e (both)     2  1 / (1 + e0)     3  1 / (1 + e1), x = z / (1 + e)
+  // act_apply's SiLU (v_exp_f32, v_rcp_f32) on the same argument.  The padding is zero AFTER the norm (silu(b) != 0): the neighbour pixels of
+  // the row's first and last segment and of the halo row's first and last tile -- loaded as zeros from beyond the descriptor -- are set to
+  // zero again by unit 3; rows outside the image are never staged (the fragments read the zero entry, which no unit touches).
+  const __amdgpu_buffer_rsrc_t rC = __builtin_amdgcn_make_buffer_rsrc((void *)p.nl_coef, 0, NL != 0 ? (int)p.nl_bytes : 0, 0x00020000);
+  const uint32_t c_lane = ((uint32_t)(row0 / p.H) * (uint32_t)p.Cin + 2u * (uint32_t)lm) * 8u;
+  float4 kn = make_float4(0.f, 0.f, 0.f, 0.f);                    // the pairs requested for the step after the one in ka, kb
+  float ka[2] = {0.f, 0.f}, kb[2] = {0.f, 0.f}, az[2] = {0.f, 0.f}, ae[2] = {0.f, 0.f};
+  auto fetch_coef = [&](int step) __attribute__((always_inline)) {
+    kn = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rC, (int)c_lane, min(step, nsteps - 1) * (R1_KC * 8), 0));
+  };
+  auto take_coef = [&]() __attribute__((always_inline)) { ka[0] = kn.x; kb[0] = kn.y; ka[1] = kn.z; kb[1] = kn.w; };
+  constexpr int NL_UNITS = 4 * (NPX + 6), NL_MAIN = 4 * NPX;       // 96 units, the halo tile's six pixels last
+  auto act_unit = [&](auto uu) __attribute__((always_inline)) {
+    constexpr int u = decltype(uu)::value, pi = u >> 2, q = u & 3;
+    f2 &d = pi < NPX ? px[0][pi < NPX ? pi : 0] : hp[pi >= NPX ? pi - NPX : 0];
+    const bool keep = pi == 0 ? m_l : pi == NPX - 1 ? m_r : pi == NPX ? h_c0 : pi == NPX + 5 ? h_c5 : true;
+    constexpr bool edge = pi == 0 || pi == NPX - 1 || pi == NPX || pi == NPX + 5;
+    if (NL == 1) {
+      if (q == 0) {
+        d.x = fmaf(ka[0], d.x, kb[0]); d.y = fmaf(ka[1], d.y, kb[1]);
+        if (edge) { d.x = keep ? d.x : 0.f; d.y = keep ? d.y : 0.f; }
+      }
+    } else {
+      if (q == 0) {
+        az[0] = fmaf(ka[0], d.x, kb[0]); az[1] = fmaf(ka[1], d.y, kb[1]);
+        ae[0] = __builtin_amdgcn_exp2f(az[0] * -1.44269504088896340736f); ae[1] = az[1] * -1.44269504088896340736f;
+      }
+      if (q == 1) { ae[1] = __builtin_amdgcn_exp2f(ae[1]); ae[0] += 1.0f; ae[1] += 1.0f; }
+      if (q == 2) ae[0] = __builtin_amdgcn_rcpf(ae[0]);
+      if (q == 3) {
+        ae[1] = __builtin_amdgcn_rcpf(ae[1]);
+        d.x = az[0] * ae[0]; d.y = az[1] * ae[1];
+        if (edge) { d.x = keep ? d.x : 0.f; d.y = keep ? d.y : 0.f; }
+      }
+    }
+  };
+  // units [U0, U1) at once (before the loop); the halo tile's only in the waves that hold one
+  auto act_range = [&](auto u0, auto u1) __attribute__((always_inline)) {
+    constexpr int U0 = decltype(u0)::value, U1 = decltype(u1)::value;
+    auto each = [&](auto self, auto uu) __attribute__((always_inline)) {
+      constexpr int u = decltype(uu)::value;
+      if constexpr (u < U1) {
+        if (u < NL_MAIN) act_unit(uu); else if (halo_wave) act_unit(uu);
+        self(self, std::integral_constant<int, u + 1>());
+      }
+    };
+    each(each, std::integral_constant<int, U0>());
+    __builtin_amdgcn_sched_barrier(0);
+  };
+
   // ---------------------------------------------------------------- contraction
   floatx16 acc[4][3];
 #pragma unroll
@@ -373,6 +434,20 @@ __device__ __forceinline__ void r1_body(const Wino1dParams &p) {
           tile_group(std::integral_constant<int, 4>(), std::integral_constant<int, (slot >= 52 ? slot - 52 : 0)>(), wbase, s + 2);
       }
 #endif
+      if constexpr (NL != 0) {
+        // The norm's units, one per gap at most, 96 over the 108: unit u in gap (81 + 9 u / 8) mod 108.  Row-tile 0's pixels (units 0 .. 23: gaps
+        // 81 .. 106) are those of the step after next, requested in gaps 19 .. 44 of this step and staged from gap 0 of the next; row-tiles
+        // 1, 2, 3 (gaps 0 .. 16, 18 .. 34, 36 .. 52) and the halo tile (54 .. 79) are done before their staging begins in gaps 23, 46, 68, 91
+        // and after their request, 57 gaps and more earlier.  The pairs change between the halo tile's last unit and row-tile 0's first.
+        if (!LAST) {
+          constexpr int gi = 12 * c + k, rel = (gi + 108 - 81) % 108, u = (rel * 8 + 8) / 9;
+          if constexpr (u < NL_UNITS && (u * 9) / 8 == rel) {
+            if (u < NL_MAIN) act_unit(std::integral_constant<int, u>()); else if (halo_wave) act_unit(std::integral_constant<int, u>());
+          }
+          if (gi == 40) fetch_coef(s + 2);
+          if (gi == 80) take_coef();
+        }
+      }
     };
     auto combo = [&](auto cc) __attribute__((always_inline)) {
       constexpr int c = decltype(cc)::value;
@@ -420,13 +495,21 @@ __device__ __forceinline__ void r1_body(const Wino1dParams &p) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
   IDIFF_W1D_T(1)                                     // first operands arrived
+  if constexpr (NL != 0) {
+    fetch_coef(0); take_coef();
+    act_range(std::integral_constant<int, 0>(), std::integral_constant<int, NL_UNITS>());
+  }
   tile_all(std::integral_constant<int, 0>(), 0u, 1); tile_all(std::integral_constant<int, 1>(), 0u, 1); tile_all(std::integral_constant<int, 2>(), 0u, 1);
   tile_all(std::integral_constant<int, 3>(), 0u, 1);
   if (halo_wave) tile_all(std::integral_constant<int, 4>(), 0u, 1);
+  if constexpr (NL != 0) {   // row-tile 0's pixels of step 1, which the loop's first step stages from its first gap on
+    fetch_coef(1); take_coef();
+    act_range(std::integral_constant<int, 0>(), std::integral_constant<int, 24>());
+  }
   __syncthreads();
   IDIFF_W1D_T(2)
-  {
-    int s = 0;                                        // at least two steps (Cin >= 32, checked by the launcher)
+  if (NL == 0 || nsteps > 1) {                        // at least two steps (Cin >= 32, checked by the launcher); the NL kernel also takes one
+    int s = 0;
     do step(s, std::false_type()); while (++s + 1 < nsteps);
   }
   step(nsteps - 1, std::true_type());
@@ -739,6 +822,11 @@ template <int W>
 __global__ void __launch_bounds__(R1_THREADS)
 wino1d_gn_kernel(const Wino1dParams p) { r1_body<W, true>(p); }
 
+// the same convolution of act(a x + b), (a, b) per (image, input channel): the GroupNorm (+ SiLU: NL = 2) in front of it, applied by the loader
+template <int NL>
+__global__ void __launch_bounds__(R1_THREADS)
+wino1d_nl_kernel(const Wino1dParams p) { r1_body<32, false, NL>(p); }
+
 // U[i][ky] = sum_kx G[i][kx] g[ky][kx] in fp64 for one (cin, cout) pair
 __device__ __forceinline__ void r1_u_of_pair(const float *wt, int Cin, int cin, int cout, double (&U)[18]) {
   double Gm[6][3];
@@ -750,12 +838,12 @@ __device__ __forceinline__ void r1_u_of_pair(const float *wt, int Cin, int cin, 
   }
 }
 
-bool r1_geometry_ok(int B, int H, int W, int Cin, int Cout) {
+bool r1_geometry_ok(int B, int H, int W, int Cin, int Cout, int min_cin = 2 * R1_KC) {
   if (B <= 0 || H <= 0 || Cin <= 0 || Cout <= 0) return false;
   if (W != 4 && W != 8 && W != 16 && W != 32 && W != 64) return false;
   const int RB = R1_PIXELS / W;
   if (H % 4 || (RB % H != 0 && H % RB != 0)) return false;                     // a block is whole images or a whole part of one
-  if (Cin % R1_KC || Cin < 2 * R1_KC || Cin > 1024 || Cout % R1_COUT) return false;
+  if (Cin % R1_KC || Cin < min_cin || Cin > 1024 || Cout % R1_COUT) return false;
   if ((int64_t)R1_NSLOT * Cin * Cout * 4 >= R1_X_LIMIT) return false;
   if ((int64_t)B * H * W * (Cin > Cout ? Cin : Cout) * 4 >= R1_X_LIMIT - 0x4000) return false;   // one buffer descriptor per tensor
   return true;
@@ -777,6 +865,11 @@ bool r1_gn_geometry_ok(int H, int W, int Cout, int groups) {
   if (W > 16 || H * W > 256 || 256 % (H * W)) return false;
   if (groups <= 0 || Cout % groups) return false;
   return R1_COUT % (Cout / groups) == 0;
+}
+
+// the norm in the loader: rows of 32 pixels and blocks (16 rows) that never straddle two images; one K step is enough for this kernel
+bool r1_nl_geometry_ok(int B, int H, int W, int Cin, int Cout) {
+  return W == 32 && H % (R1_PIXELS / 32) == 0 && r1_geometry_ok(B, H, W, Cin, Cout, R1_KC);
 }
 }  // namespace
 
@@ -801,13 +894,22 @@ IDIFF_API int idiff_wino1d_pack_f32(const float *wt, float *u, int Cin, int Cout
 
 namespace {
 struct R1GroupNorm { int groups; const float *gamma, *beta; float eps; int act; };
+struct R1NormLoad { const float *coef; int act; };
 
-// both entry points: gn == nullptr is idiff_conv2d_wino1d_f32
+// the three entry points: gn == nullptr and nl == nullptr is idiff_conv2d_wino1d_f32
 int r1_run(const float *x, const float *u, float *out, int B, int H, int W, int Cin, int Cout, const idiff_epilogue *ep, const R1GroupNorm *gn,
-           void *stream) {
+           const R1NormLoad *nl, void *stream) {
   using namespace idiff;
   if (B == 0) return 0;
-  if (!r1_geometry_ok(B, H, W, Cin, Cout))
+  if (nl) {
+    // nothing is launched unless a block's rows are one image's (one set of coefficients per workgroup)
+    if (!r1_nl_geometry_ok(B, H, W, Cin, Cout))
+      return fail("conv2d_wino1d_normload: geometry B=%d H=%d W=%d Cin=%d Cout=%d not supported: W = 32, H %% 16 == 0, Cin %% 16 == 0, "
+                  "Cout %% 64 == 0", B, H, W, Cin, Cout);
+    if (!nl->coef || ((uintptr_t)nl->coef & 15)) return fail("conv2d_wino1d_normload: the coefficients [B, Cin, 2] are required, 16-byte aligned");
+    if (nl->act != IDIFF_ACT_NONE && nl->act != IDIFF_ACT_SILU)
+      return fail("conv2d_wino1d_normload: the loader applies SiLU or no activation (code %d)", nl->act);
+  } else if (!r1_geometry_ok(B, H, W, Cin, Cout))
     return fail("conv2d_wino1d: geometry B=%d H=%d W=%d Cin=%d Cout=%d not supported (ask idiff_conv2d_wino1d_ok)", B, H, W, Cin, Cout);
   int64_t res_bytes = 0;
   if (int rc = wino_check_call("conv2d_wino1d", x, u, out, ep, B, H, W, Cout, R1_X_LIMIT, res_bytes)) return rc;
@@ -837,6 +939,11 @@ int r1_run(const float *x, const float *u, float *out, int B, int H, int W, int 
 #ifdef IDIFF_W1D_STAMP
   { const char *e = getenv("IDIFF_W1D_STAMP_PTR"); p.stamps = e ? reinterpret_cast<uint64_t *>(strtoull(e, nullptr, 0)) : nullptr; }
 #endif
+  if (nl) {
+    p.nl_coef = nl->coef; p.nl_bytes = (uint32_t)((int64_t)B * Cin * 8);
+    if (nl->act == IDIFF_ACT_SILU) return r1_launch<wino1d_nl_kernel<2>>(p, "conv2d_wino1d_normload", (hipStream_t)stream);
+    return r1_launch<wino1d_nl_kernel<1>>(p, "conv2d_wino1d_normload", (hipStream_t)stream);
+  }
   if (gn) {
     p.gn_gamma = gn->gamma; p.gn_beta = gn->beta; p.gn_cpg = Cout / gn->groups; p.gn_act = gn->act; p.gn_eps = gn->eps;
     switch (W) {
@@ -857,7 +964,7 @@ int r1_run(const float *x, const float *u, float *out, int B, int H, int W, int 
 
 IDIFF_API int idiff_conv2d_wino1d_f32(const float *x, const float *u, float *out, int B, int H, int W, int Cin, int Cout,
                                       const idiff_epilogue *ep, void *stream) {
-  return r1_run(x, u, out, B, H, W, Cin, Cout, ep, nullptr, stream);
+  return r1_run(x, u, out, B, H, W, Cin, Cout, ep, nullptr, nullptr, stream);
 }
 
 IDIFF_API int idiff_conv2d_wino1d_gn_ok(int B, int H, int W, int Cin, int Cout, int groups) {
@@ -869,5 +976,26 @@ IDIFF_API int idiff_conv2d_wino1d_gn_f32(const float *x, const float *u, float *
                                          const idiff_epilogue *ep, int groups, const float *gamma, const float *beta, float eps, int act,
                                          void *stream) {
   const R1GroupNorm gn = {groups, gamma, beta, eps, act};
-  return r1_run(x, u, out, B, H, W, Cin, Cout, ep, &gn, stream);
+  return r1_run(x, u, out, B, H, W, Cin, Cout, ep, &gn, nullptr, stream);
+}
+
+// Routed: where the loader's norm was MEASURED faster than the pass in front of the convolution (scripts/normload_shape_ab.py,
+// profiles/normload_shape_ab.txt, B = 2240, 32 x 32, median us of {groupnorm_apply_colstats + conv2d_wino1d} against {coefficients + this}):
+//   128 -> 128   453 + 1203 = 1656   against   8 + 1422 = 1430   (-13.7 %)
+//   256 -> 128   909 + 2077 = 2985   against  16 + 2512 = 2527   (-15.3 %)
+//   384 -> 128  1390 + 2997 = 4387   against  23 + 3684 = 3707   (-15.5 %)
+//   256 -> 256   917 + 4129 = 5046   against  16 + 4961 = 4977   (-1.4 %: inside the repetitions' spread -- not routed)
+// The K loop is 18 - 23 % slower with the norm's 96 units in it, whatever the class; the pass it replaces costs the same per input channel
+// while the loop's time grows with the cout tiles that stage the same input: one or two tiles win, four do not.
+IDIFF_API int idiff_conv2d_wino1d_normload_ok(int B, int H, int W, int Cin, int Cout) {
+  using namespace idiff;
+  if (option(OPT_NO_WINOGRAD) || option(OPT_NO_WINO43H) || option(OPT_NO_WINO1D) || option(OPT_NO_PAIRS) || option(OPT_NO_FUSED_GN_LOAD)) return 0;
+  if (!r1_nl_geometry_ok(B, H, W, Cin, Cout)) return 0;
+  return Cout / R1_COUT <= 2 ? 1 : 0;
+}
+
+IDIFF_API int idiff_conv2d_wino1d_normload_f32(const float *x, const float *u, float *out, int B, int H, int W, int Cin, int Cout,
+                                               const idiff_epilogue *ep, const float *coef, int act, void *stream) {
+  const R1NormLoad nl = {coef, act};
+  return r1_run(x, u, out, B, H, W, Cin, Cout, ep, nullptr, &nl, stream);
 }

@@ -333,7 +333,8 @@ class NCSNpp(NhwcExecutor):
         rs = _INV_SQRT2 if self.skip_rescale else 1.0
         c_in = x.C + (x2.C if x2 is not None else 0)
         assert c_in == mod.in_ch, (c_in, mod.in_ch)
-        h = self._gn_act(x, mod.GroupNorm_0, self.act_name, x2)
+        # (an up / down block's norm is read by the FIR as well: it stays a pass)
+        h = self._gn_act(x, mod.GroupNorm_0, self.act_name, x2, conv_cout=None if (mod.up or mod.down) else mod.out_ch)
         if mod.up or mod.down:
             assert x2 is None
             if self.fir:
@@ -342,7 +343,8 @@ class NCSNpp(NhwcExecutor):
                 h, x = self._box(h, mod.up), self._box(x, mod.up)
         w0, b0 = self._conv_w(pk, (idx, 0), mod.Conv_0)
         off = pk["dense_off"][idx]
-        h = self._conv_gn_act(h, w0, b0, mod.GroupNorm_1, self.act_name, rowbias=temb_all[:, off:off + mod.out_ch], normed=True)
+        h = self._conv_gn_act(h, w0, b0, mod.GroupNorm_1, self.act_name, rowbias=temb_all[:, off:off + mod.out_ch], normed=True,
+                              next_cout=mod.out_ch)
         # shortcut
         if hasattr(mod, "Conv_2") or hasattr(mod, "NIN_0"):
             # cat[x, x2] with equal row pitch: one two-source contraction; otherwise two K-slices through the residual epilogue

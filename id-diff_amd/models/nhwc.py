@@ -20,10 +20,13 @@ def _pad4(c):
 class _T:
     """An NHWC activation: buffer [B, H*W, C] + geometry (+ the per-tile column sums [B, nsplit, C, 2] its producing
     contraction wrote through epilogue.colstats, which let the consuming GroupNorm skip its statistics pass)."""
-    __slots__ = ("buf", "H", "W", "C", "stats", "norm")
+    __slots__ = ("buf", "H", "W", "C", "stats", "norm", "pending")
 
-    def __init__(self, buf, H, W, C, stats=None, norm=None):
+    def __init__(self, buf, H, W, C, stats=None, norm=None, pending=None):
         self.buf, self.H, self.W, self.C, self.stats = buf, H, W, C, stats
+        # set where a GroupNorm was NOT applied: ``buf`` is still the norm's raw input and the one 3x3 convolution that reads this tensor
+        # applies it in its loader: (coefficients [B, C, 2], activation, the norm's input _T, the module) -- see NhwcExecutor._gn_act
+        self.pending = pending
         # set on the output of a GroupNorm (and kept through the resamplers): (module, elements per normalised group, absolute gain of
         # what followed, modulated?) -- what HipScoreModel.pairs_admissible needs to decide whether the consumer may run on fp16 pairs
         self.norm = norm
@@ -139,13 +142,27 @@ class NhwcExecutor(HipScoreModel):
             y.stats = (torch.empty(y.buf.shape[0] * ns * y.C * 2, device=y.buf.device, dtype=torch.float64), ns)
             ep["colstats"] = y.stats[0]
 
-    def _gn_act(self, x, gn, act, x2=None, mod=None):
-        """GroupNorm (+ scale-shift modulation ``mod`` [B, 2*Ctot]) (+activation) of x (or of cat[x, x2])."""
+    def _gn_act(self, x, gn, act, x2=None, mod=None, conv_cout=None):
+        """GroupNorm (+ scale-shift modulation ``mod`` [B, 2*Ctot]) (+activation) of x (or of cat[x, x2]).
+        ``conv_cout``: the result's ONLY reader is a 3x3 stride-1 pad-1 convolution to that many channels whose epilogue groups are whole
+        images.  Where that convolution takes the ``wino1d`` route on rows of 32 pixels, the norm is unmodulated, of one source with column
+        sums, admitted to the fp16 pairs by ITS OWN gamma / beta (the record below: the tensor in memory stays the raw one) and the kernel's
+        query routes the class (IDIFF_NO_FUSED_GN_LOAD answers no), the pass is not made: one small launch turns the column sums into an
+        affine pair per (image, channel) and the tensor is handed on ``pending``; _conv applies a x + b and the activation in its loader.
+        cat[x, x2] stays on the pass (the loader reads one base pointer)."""
         B = x.buf.shape[0]
         HW = x.H * x.W
         C2 = x2.C if x2 is not None else 0
         G = gn.num_groups
         norm = (gn, ((x.C + C2) // G) * HW, 1.0, mod is not None)
+        if (conv_cout is not None and mod is None and x2 is None and x.stats is not None and x.pending is None and x.W == 32
+                and _lib.ACT[act] in (0, 1) and _lib.conv2d_wino1d_normload_ok(B, x.H, x.W, x.C, conv_cout)
+                and self.pairs_admissible(gn, norm[1], gain=1.0, transform=True, modulated=False)):
+            route = conv3x3_route(B, x.H, x.W, x.C, conv_cout, True, True)
+            if route is not None and route.name == "wino1d":
+                coef = torch.empty(B * x.C * 2, device=x.buf.device, dtype=torch.float32)
+                _lib.groupnorm_coef(x.stats[0], x.stats[1], x.C, None, 0, 0, B, HW, G, gn.eps, gn.weight.detach(), gn.bias.detach(), coef)
+                return _T(x.buf, x.H, x.W, x.C, norm=norm, pending=(coef, act, x, gn))
         if x.stats is not None and (x2 is None or x2.stats is not None) and x.C + C2 <= 1024 and B <= 65535:
             # both sources carry the column sums their producing contraction wrote: no pass over the activations, and the
             # statistics are finished inside the apply kernel (one launch per GroupNorm)
@@ -195,6 +212,10 @@ class NhwcExecutor(HipScoreModel):
         route = None
         if (kh, kw, stride, pad, ph) == (3, 3, 1, 1, 1):
             route = conv3x3_route(*geom, normed, ep["rows_per_group"] == OH * OW)
+        pending = x.pending
+        if pending is not None and (route is None or route.name != "wino1d" or not _lib.conv2d_wino1d_normload_ok(*geom)):
+            # not the convolution _gn_act foresaw (a switch flipped in between): the pass after all, never a raw tensor into a kernel
+            x, pending = self._gn_act(pending[2], pending[3], pending[1]), None
         if route is None:
             if stats or fuse_gn is not None:
                 self._colstats(y, _lib.conv2d_colstats_split(*geom, kh, kw, stride, pad, pad_hi), ep)
@@ -207,7 +228,7 @@ class NhwcExecutor(HipScoreModel):
         if key not in bank:
             bank[key] = (wt, getattr(_lib, route.pack)(wt, cin, cout, **form))
         # the fused tail takes bias and the per-image bias only: an activation or a scale in front of the norm stays two launches
-        if (fuse_gn is not None and route.name == "wino1d" and _lib.conv2d_wino1d_gn_ok(*geom, fuse_gn[0].num_groups)
+        if (fuse_gn is not None and pending is None and route.name == "wino1d" and _lib.conv2d_wino1d_gn_ok(*geom, fuse_gn[0].num_groups)
                 and not (set(ep) - {"rowbias", "ld_rowbias", "rows_per_group"})):
             gn, act = fuse_gn
             epilogue = _lib.with_groupnorm(_lib.make_epilogue(bias=bias, **ep), gn.num_groups, gn.weight.detach(), gn.bias.detach(), gn.eps, act)
@@ -216,19 +237,23 @@ class NhwcExecutor(HipScoreModel):
             return y, True
         if stats or fuse_gn is not None:
             self._colstats(y, getattr(_lib, route.split)(*geom), ep)
-        getattr(_lib, route.launch)(x.buf, bank[key][1], y.buf, *geom, epilogue=_lib.make_epilogue(bias=bias, **ep), **form)
+        epilogue = _lib.make_epilogue(bias=bias, **ep)
+        if pending is not None:
+            epilogue = _lib.with_normload(epilogue, pending[0], pending[1])
+        getattr(_lib, route.launch)(x.buf, bank[key][1], y.buf, *geom, epilogue=epilogue, **form)
         return (y, False) if fuse_gn is not None else y
 
-    def _conv_gn_act(self, x, wt, bias, gn, act, mod=None, **conv_args):
+    def _conv_gn_act(self, x, wt, bias, gn, act, mod=None, next_cout=None, **conv_args):
         """3x3 conv followed by GroupNorm ``gn`` (+ modulation ``mod``) + activation, the convolution's output read by nothing else
         (Conv_0 -> GroupNorm_1 of a residual block).  One launch where the convolution takes the ``wino1d`` route, the kernel's query admits
         the geometry and group count (maps of at most 256 pixels; IDIFF_NO_FUSED_GN answers no), the norm is unmodulated and the
         epilogue in front of it is bias + per-image bias only: the convolution's output then never reaches memory.  Otherwise the
-        convolution with column sums and _gn_act, as two launches."""
+        convolution with column sums and _gn_act, as two launches.  ``next_cout``: the norm's only reader is a 3x3 convolution to that many
+        channels (_gn_act's ``conv_cout``: on 32-pixel rows that convolution's loader applies the norm)."""
         if mod is not None:
             return self._gn_act(self._conv(x, wt, bias, stats=True, **conv_args), gn, act, mod=mod)
         y, fused = self._conv(x, wt, bias, fuse_gn=(gn, act), **conv_args)
-        return y if fused else self._gn_act(y, gn, act)
+        return y if fused else self._gn_act(y, gn, act, conv_cout=next_cout)
 
     def _pointwise(self, x, w, bias, stats=False, **ep):
         """1x1 conv / NIN on NHWC = plain GEMM over [B*HW, Cin]; w is [Cout, Cin]."""

@@ -51,7 +51,8 @@ const char *idiff_variant_flags(void);
  * SLOWER when the runtime maps it onto the caller's queue, which happens once a process has made a few streams),
  * IDIFF_NO_WINO43 (3x3 convolutions on the F(2x2,3x3) kernel instead of F(4x4,3x3)), IDIFF_NO_WINO43H (F(4x4,3x3) with its
  * contractions on the fp32 matrix cores instead of fp16 pairs), IDIFF_NO_FUSED_ATTN (idiff_attention256_ok and idiff_attention_heads_ok answer 0), IDIFF_NO_WINO1D (idiff_conv2d_wino1d_ok answers 0),
- * IDIFF_NO_FUSED_GN (idiff_conv2d_wino1d_gn_ok answers 0: the GroupNorm behind a row-wise convolution stays a launch of its own), IDIFF_NO_PAIRS (idiff_gemm_pairs_ok answers 0: the 1x1
+ * IDIFF_NO_FUSED_GN (idiff_conv2d_wino1d_gn_ok answers 0: the GroupNorm behind a row-wise convolution stays a launch of its own), IDIFF_NO_FUSED_GN_LOAD
+ * (idiff_conv2d_wino1d_normload_ok answers 0: the GroupNorm in front of a row-wise convolution stays a pass of its own), IDIFF_NO_PAIRS (idiff_gemm_pairs_ok answers 0: the 1x1
  * projections behind a GroupNorm stay on idiff_gemm_f32's six-product form), IDIFF_PAIRS_MIN_TILES (tests: the number of 128 x 128
  * tiles from which idiff_gemm_pairs_ok answers 1; default 256).
  * Returns the previous value, -1 for an unknown name.  No reference counterpart. */
@@ -304,6 +305,19 @@ int idiff_conv2d_wino1d_gn_ok(int B, int H, int W, int Cin, int Cout, int groups
 int idiff_conv2d_wino1d_gn_f32(const float *x, const float *u, float *out, int B, int H, int W, int Cin, int Cout,
                                const idiff_epilogue *ep, int groups, const float *gamma, const float *beta, float eps, int act,
                                void *stream);
+/* The same convolution with the GroupNorm (+ SiLU) in FRONT of it applied by the kernel's loader, for rows of 32 pixels: a workgroup (16
+ * rows) holds rows of one image, the statistics are complete before it starts (the producers' column sums), so the norm is one affine pair
+ * per (image, input channel) -- idiff_groupnorm_coef_f32 -- and
+ *     out = epilogue(conv(pad0(act(a[b][c] * x + b[b][c]))))
+ * with the padding zero AFTER the norm: the normalised tensor is never written or read.
+ *   idiff_conv2d_wino1d_normload_ok   1 where this form is served (W = 32, H % 16 == 0, Cin % 16 == 0, 16 <= Cin <= 1024, Cout % 64 == 0) and
+ *                                     routed (measured faster than the pass: Cout <= 128, csrc/wino1d.hip); 0 under IDIFF_NO_FUSED_GN_LOAD, IDIFF_NO_PAIRS and the switches of idiff_conv2d_wino1d_ok.
+ *   idiff_conv2d_wino1d_normload_f32  coef: [B, Cin, 2] floats (a, b), 16-byte aligned; act: IDIFF_ACT_SILU or IDIFF_ACT_NONE; the epilogue
+ *                                     of idiff_conv2d_wino1d_f32.  Whether the normalised input stays inside the fp16 pairs' range is the
+ *                                     caller's to decide from the GroupNorm's gamma / beta (the tensor in memory is the raw one). */
+int idiff_conv2d_wino1d_normload_ok(int B, int H, int W, int Cin, int Cout);
+int idiff_conv2d_wino1d_normload_f32(const float *x, const float *u, float *out, int B, int H, int W, int Cin, int Cout,
+                                     const idiff_epilogue *ep, const float *coef, int act, void *stream);
 
 /* Split-precision form of the same convolution: the 16 position-wise contractions run on the bf16 matrix cores with every
  * fp32 operand cut exactly into three bf16 pieces and six of the nine partial products kept (fp32 accumulation; what is
@@ -346,6 +360,11 @@ int idiff_groupnorm_apply_colstats_f32(const float *x, int C, const float *x2, i
                                        const double *ws1, int nsplit1, const double *ws2, int nsplit2, float eps,
                                        const float *gamma, const float *beta, const float *mod, int64_t ld_mod,
                                        int act, float *y, void *stream);
+/* The same GroupNorm as one affine pair per (sample, channel) for a consumer that applies it itself (idiff_conv2d_wino1d_normload_f32):
+ * coef [B, C1 + C2, 2] = (a, b) with a = rstd * gamma[c], b = beta[c] - mean * rstd * gamma[c], so that a * x + b is the norm of x.
+ * Statistics from the producers' column sums as idiff_groupnorm_finalize_f32 forms them; the pair is formed in fp64 and rounded once. */
+int idiff_groupnorm_coef_f32(const double *ws1, int nsplit1, int C1, const double *ws2, int nsplit2, int C2, int B, int HW, int G,
+                             float eps, const float *gamma, const float *beta, float *coef, void *stream);
 
 /* Row softmax of x [rows, cols] scaled by `scale` before the exponent (layerspp.py:82-84). In place allowed. */
 int idiff_softmax_rows_f32(const float *x, float *y, int64_t rows, int cols, float scale, void *stream);
