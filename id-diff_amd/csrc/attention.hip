@@ -34,10 +34,7 @@ constexpr int AT_PLANE = AT_T * 64;             // bytes: 256 rows x 32 halves
 constexpr int AT_CHUNK = 2 * AT_PLANE;          // hi | lo
 constexpr int AT_LDS = 2 * AT_CHUNK;            // two buffers: 65,536 B
 constexpr float AT_PSCALE = 1024.0f;
-#ifndef IDIFF_AT_LEAD
-#define IDIFF_AT_LEAD 3
-#endif
-constexpr int AT_LEAD = IDIFF_AT_LEAD;         // operand blocks requested from LDS ahead of their matrix instructions
+constexpr int AT_LEAD = 3;                      // operand blocks requested from LDS ahead of their matrix instructions
 
 struct AttnParams {
   const float *qk;        // [B * 256, ld_qk]: q in columns [0, C), k in [C, 2C)

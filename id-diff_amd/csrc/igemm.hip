@@ -302,18 +302,12 @@ constexpr uint32_t OOB = 0xFFFFFFFFu;
 // bf16 elements per LDS row of a split plane: 64 bytes, NO padding -- the four 16-byte chunks of a row are XOR-swizzled by
 // (row ^ (row >> 2)) & 3, which makes the b128 fragment reads of 16 consecutive rows hit every bank once, and the three
 // planes of a 128 x 32 + 128 x 32 tile pair take 48 KB instead of 60: THREE workgroups per CU instead of two (the k-tile
-// stamps of scripts/igemm_phases.py: 2300 cycles of LDS reads + MFMAs against 2170 of barrier / cutting / staging / fetch
+// stamps of profiles/HISTORY_r01_r03.md: 2300 cycles of LDS reads + MFMAs against 2170 of barrier / cutting / staging / fetch
 // per k-tile and wave, 13 k-cycles of prologue + epilogue per 8 k-tiles -- work that only other resident waves can cover).
 constexpr int SP = BK;
 __device__ __forceinline__ int split_swz(int row) { return (row ^ (row >> 2)) & 3; }
 
 __device__ __forceinline__ void split4(const float4 v, uint2 &p1, uint2 &p2, uint2 &p3) {
-#ifdef IDIFF_IGEMM_DIAG_NO_CUT   // timing-only build (scripts/igemm_ab.py): no cutting arithmetic, results wrong by construction
-  p1 = make_uint2(__float_as_uint(v.x), __float_as_uint(v.y));
-  p2 = make_uint2(__float_as_uint(v.z), __float_as_uint(v.w));
-  p3 = p1;
-  return;
-#endif
   const float x[4] = {v.x, v.y, v.z, v.w};
   uint32_t t1[4], t2[4], t3[4];
 #pragma unroll
@@ -356,9 +350,6 @@ __device__ __forceinline__ float4 buf_load4(__amdgpu_buffer_rsrc_t r, uint32_t b
 template <int BM, int BN, int WARPS_M, int WARPS_N, bool CONV, bool DBUF, int SPLIT>   // SPLIT: 0 fp32 MFMA, 1 three bf16, 2 fp16 pairs
 __global__ void __launch_bounds__(WARPS_M *WARPS_N * 64, (DBUF || SPLIT) ? 2 : 4)
 igemm_pipe_kernel(const IgemmParams p) {
-#ifdef IDIFF_IGEMM_PHASES
-  const uint64_t ph_entry = __builtin_amdgcn_s_memtime();
-#endif
   static_assert(!(SPLIT && DBUF), "the split form uses one LDS buffer");
   constexpr int T = WARPS_M * WARPS_N * 64;
   constexpr int WTM = BM / WARPS_M, WTN = BN / WARPS_N;
@@ -551,14 +542,6 @@ igemm_pipe_kernel(const IgemmParams p) {
   if (nkt > 1) fetch();
   __syncthreads();
 
-#ifdef IDIFF_IGEMM_PHASES   // diagnostic build only (scripts/igemm_phases.py): shader-clock ticks per phase of a k-tile
-  uint32_t ph[6] = {0, 0, 0, 0, 0, 0};
-  uint64_t ph_last = __builtin_amdgcn_s_memtime();
-  const uint64_t ph_first = ph_last;
-#define IDIFF_PH(k) { __builtin_amdgcn_sched_barrier(0); const uint64_t t_ = __builtin_amdgcn_s_memtime(); ph[k] += (uint32_t)(t_ - ph_last); ph_last = t_; __builtin_amdgcn_sched_barrier(0); }
-#else
-#define IDIFF_PH(k)
-#endif
   auto ktile = [&](int kt, auto first) {
     const int buf = DBUF ? (kt & 1) : 0;
     if (DBUF && !SPLIT) {
@@ -619,11 +602,7 @@ igemm_pipe_kernel(const IgemmParams p) {
 #pragma unroll
       for (int s = 0; s < BK / 16; ++s)
 #pragma unroll
-#ifdef IDIFF_IGEMM_DIAG_ONE_PRODUCT   // timing-only build: one of the six partial products (and a third of the fragment reads)
-        for (int t = 0; t < 1; ++t)
-#else
         for (int t = 0; t < 6; ++t)
-#endif
 #pragma unroll
           for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -660,33 +639,17 @@ igemm_pipe_kernel(const IgemmParams p) {
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i].w, bf[j].w, acc[i][j], 0, 0, 0);
         }
     }
-    IDIFF_PH(0)
     __syncthreads();
-    IDIFF_PH(1)
     if (!DBUF) {
       // single LDS buffer (half the LDS -> three workgroups per CU): restage between two barriers; the other
       // resident workgroups keep the matrix pipe busy meanwhile
       if (kt + 1 < nkt) stage(0);
-      IDIFF_PH(2)
-#ifdef IDIFF_IGEMM_DIAG_NO_FETCH   // timing-only build: operands fetched for the first two k-tiles only
-      if (kt + 2 < nkt) ++f_kt;
-#else
       if (kt + 2 < nkt) fetch();
-#endif
-      IDIFF_PH(3)
       __syncthreads();
-      IDIFF_PH(4)
     }
   };
-#ifdef IDIFF_IGEMM_PHASES
-  const uint64_t ph_loop0 = __builtin_amdgcn_s_memtime();
-  ph_last = ph_loop0;
-#endif
   ktile(0, std::true_type());
   for (int kt = 1; kt < nkt; ++kt) ktile(kt, std::false_type());
-#ifdef IDIFF_IGEMM_PHASES
-  const uint64_t ph_loop1 = __builtin_amdgcn_s_memtime();
-#endif
 
   if (SPLIT == 2) {
     const float inv = (p.scale_a ? p.scale_a[1] : 1.f) * (p.scale_b ? p.scale_b[1] : 1.f);    // powers of two: exact
@@ -702,11 +665,7 @@ igemm_pipe_kernel(const IgemmParams p) {
   const int col_l = lane & 31, row_l = (lane >> 5) * 4;
   // optional per-tile column statistics (sum, sum of squares in fp64) of the values being stored: the GroupNorm that
   // consumes this tensor then needs no pass of its own over HBM (idiff_epilogue.colstats)
-#ifdef IDIFF_IGEMM_PHASES
-  const bool want_stats = false;                   // epilogue.colstats carries the stamp buffer in this build
-#else
   const bool want_stats = p.has_ep && ep.colstats != nullptr;
-#endif
   double *red = reinterpret_cast<double *>(lds);   // [WARPS_M][BN][2]; operand staging is finished
   if (p.vec_ep && p.buf_ep) {
     // The form every contraction of the score networks takes.  As the vector form below (each wave turns its 32-row
@@ -936,19 +895,7 @@ igemm_pipe_kernel(const IgemmParams p) {
       dst[0] = a; dst[1] = b;
     }
   }
-#ifdef IDIFF_IGEMM_PHASES
-  if (p.has_ep && ep.colstats && lane == 0) {
-    // a buffer nothing else reads: [workgroup][wave][8]
-    const int64_t wg = ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    uint32_t *st = reinterpret_cast<uint32_t *>(ep.colstats) + (wg * (T / 64) + (tid >> 6)) * 8;
-    for (int k = 0; k < 5; ++k) st[k] = ph[k];
-    st[5] = (uint32_t)(ph_loop0 - ph_entry);                       // prologue: kernel entry to the first k-tile
-    st[6] = (uint32_t)(__builtin_amdgcn_s_memtime() - ph_loop1);   // epilogue
-    st[7] = (uint32_t)nkt;
-  }
-#endif
 }
-#undef IDIFF_PH
 
 template <int BM, int BN, int WARPS_M, int WARPS_N, bool CONV, bool DBUF = true, int SPLIT = 0>
 int launch_pipe(IgemmParams &p, int batch, hipStream_t st) {

@@ -76,14 +76,10 @@ constexpr size_t R1_LDS_BYTES = R1_Z_BYTES;
 constexpr uint32_t R1_STAGE_STRIDE = 0x10000;                      // the two stages 64 KB apart: the other stage is one XOR away
 constexpr uint32_t R1_INVALID = 0xFFFF8000u;                       // beyond any valid extent (the scalar offset is not range-checked)
 constexpr int64_t R1_X_LIMIT = 0xFFFF0000ll;
-#ifndef IDIFF_W1D_BRING
-#define IDIFF_W1D_BRING 3
-#endif
-#ifndef IDIFF_W1D_STORE_AUX
-#define IDIFF_W1D_STORE_AUX 0      // cache policy bits of the output stores (1 = sc0, 2 = nt, 16 = sc1)
-#endif
-constexpr int R1_BRING = IDIFF_W1D_BRING;                          // combinations of U requested ahead (register sets of 8)
+constexpr int R1_BRING = 3;                                        // combinations of U requested ahead (register sets of 8)
 static_assert(9 % R1_BRING == 0, "the ring of U registers must divide the nine combinations of a step");
+constexpr int R1_STORE_AUX = 0;                                    // cache policy bits of the output stores: nt, sc1 and both with sc0 all
+                                                                   // measured within noise of the default (profiles/r05_wino1d_loop_experiments.txt)
 
 // Where entry e of a stage lives: the entries of every second group of four trade places in pairs.  The 32 lanes of one pass of a ds_write_b32
 // are four loader threads' dwords of the entries e, e + 4, e + 8, e + 12 (32 bytes each); at e * 64 they would fall on two of the four
@@ -663,7 +659,7 @@ __device__ __forceinline__ void r1_body(const Wino1dParams &p) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) y[e] = idiff::act_apply((v[i][e] - mu[e]) * sc[e] + bet[e], ACT < 0 ? p.gn_act : ACT);
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uintx4, make_float4(y[0], y[1], y[2], y[3])), rO, (int)ooff, i * p.Cout * 4,
-                                               IDIFF_W1D_STORE_AUX);
+                                               R1_STORE_AUX);
       }
     };
     auto finish_gn_round = [&](auto round_c) __attribute__((always_inline)) {
@@ -753,7 +749,7 @@ __device__ __forceinline__ void r1_body(const Wino1dParams &p) {
         if (4 * j + a == 15)
 #endif
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uintx4, make_float4(y[a][0], y[a][1], y[a][2], y[a][3])), rO, (int)ooff,
-                                               (4 * j + a) * p.Cout * 4, IDIFF_W1D_STORE_AUX);
+                                               (4 * j + a) * p.Cout * 4, R1_STORE_AUX);
       }
     }
   };

@@ -39,32 +39,13 @@
 
 namespace {
 
-#ifndef IDIFF_W43_EARLY_WAVES
-#define IDIFF_W43_EARLY_WAVES 2
-#endif
-constexpr int F4_EARLY_WAVES = IDIFF_W43_EARLY_WAVES;   // waves 0 .. n-1 transform at the start of a step, the others late (A/B)
-#ifndef IDIFF_W43_MID_WAVES
-#define IDIFF_W43_MID_WAVES IDIFF_W43_EARLY_WAVES
-#endif
-#ifndef IDIFF_W43_MID_AT
-#define IDIFF_W43_MID_AT 3
-#endif
-constexpr int F4_MID_WAVES = IDIFF_W43_MID_WAVES, F4_MID_AT = IDIFF_W43_MID_AT;   // waves EARLY .. MID-1 transform in front of position MID_AT
-#ifndef IDIFF_W43_VRING
-#define IDIFF_W43_VRING 2
-#endif
-constexpr int F4_VRING = IDIFF_W43_VRING;   // V fragments in flight ahead of their MFMAs (register sets)
-#ifndef IDIFF_W43_LATE_AT
-#define IDIFF_W43_LATE_AT 6
-#endif
-constexpr int F4_LATE_AT = IDIFF_W43_LATE_AT;   // the late role transforms in front of this position of its step (A/B: scripts/wino43_ab.py)
+constexpr int F4_EARLY_WAVES = 2;                        // waves 0 .. n-1 transform at the start of a step, the others late
+constexpr int F4_LATE_AT = 6;                            // the late role transforms in front of this position of its step
+constexpr int F4_VRING = 2;                              // V fragments in flight ahead of their MFMAs (register sets)
 constexpr int F4_VSLOT = F4_TILES * F4_KC + 4;           // 260 = 4 mod 32: the six columns a lane group writes fall on distinct banks
 constexpr int F4_STAGE = F4_NPOS * F4_VSLOT;             // 9360 floats
 constexpr int F4_SCR_ROW = 7 * 4;                        // scratch row: 6 float4 + one of padding (28 dwords: rows on distinct banks)
-#ifndef IDIFF_W43_SCR_UNIT
-#define IDIFF_W43_SCR_UNIT 224
-#endif
-constexpr int F4_SCR_UNIT = IDIFF_W43_SCR_UNIT;                       // floats per unit (6 rows used): with this pitch the column reads of the
+constexpr int F4_SCR_UNIT = 224;                         // floats per unit (6 rows used): with this pitch the column reads of the
                                                          // four 16-lane groups of a ds_read_b128 fall on distinct banks as well (PMC:
                                                          // SQ_LDS_BANK_CONFLICT was 21 % of the LDS cycles at the dense pitch of 168)
 constexpr int F4_SCR_WAVE = 8 * F4_SCR_UNIT;             // 1792 floats per wave
@@ -89,9 +70,6 @@ __device__ __forceinline__ void f4_wave_lds_sync() {
 __global__ void __launch_bounds__(F4_THREADS, 2)   // two waves per SIMD: one 512-thread workgroup per CU
 winograd43_kernel(const Wino43Params p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-#ifdef IDIFF_W43_STAMP   // diagnostic build only (scripts/wino43_stamps.py): 100 MHz ticks at the phases of a workgroup's life
-  const uint64_t st_start = __builtin_amdgcn_s_memrealtime();
-#endif
   const int nwg = p.tiles_m * p.tiles_n;
   int bid = blockIdx.x;
   {
@@ -227,16 +205,9 @@ winograd43_kernel(const Wino43Params p) {
   stage(0);
   fetch();
   __syncthreads();
-#ifdef IDIFF_W43_STAMP
-  const uint64_t st_loop0 = __builtin_amdgcn_s_memrealtime();
-#endif
   if (wave < F4_EARLY_WAVES) run(std::integral_constant<int, 0>());
-  else if (wave < F4_MID_WAVES) run(std::integral_constant<int, F4_MID_AT>());
   else run(std::integral_constant<int, F4_LATE_AT>());
   step(nsteps - 1, std::integral_constant<int, 9>(), std::true_type());
-#ifdef IDIFF_W43_STAMP
-  const uint64_t st_loop1 = __builtin_amdgcn_s_memrealtime();
-#endif
 
   // ---------------------------------------------------------------- tail
   const idiff_epilogue &ep = p.ep;
@@ -274,17 +245,10 @@ winograd43_kernel(const Wino43Params p) {
     }
   };
 
-#ifdef IDIFF_W43_STAMP
-  const bool want_stats = false;            // epilogue.colstats carries the stamp buffer in this build
-#else
   const bool want_stats = has_ep && ep.colstats != nullptr;
-#endif
   double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};    // column sums of this thread's 16 pixels x 4 channels
   // accumulator register `reg` of lane l is tile row (reg & 3) + 8 (reg >> 2) + 4 (l >> 5), cout wh * 32 + (l & 31)
   float *zbase = lds + (size_t)(4 * (lane >> 5)) * 2 * F4_COUT + wh * 32 + (lane & 31);
-#ifdef IDIFF_W43_STAMP
-  uint64_t st_tail[4] = {0, 0, 0, 0};
-#endif
 #pragma unroll
   for (int pass = 0; pass < 2; ++pass) {
     // z_{i,b} for b = 2 pass, 2 pass + 1 and the three rows i of this wave's block: column block 1 parks, block 0 adds
@@ -326,9 +290,6 @@ winograd43_kernel(const Wino43Params p) {
         }
     }
     __syncthreads();
-#ifdef IDIFF_W43_STAMP
-    st_tail[2 * pass] = __builtin_amdgcn_s_memrealtime();       // z of this pass exchanged
-#endif
     __builtin_amdgcn_sched_barrier(0);
     prep();
 #pragma unroll
@@ -378,9 +339,6 @@ winograd43_kernel(const Wino43Params p) {
                                                so + a * rp, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
-#ifdef IDIFF_W43_STAMP
-    st_tail[2 * pass + 1] = __builtin_amdgcn_s_memrealtime();   // outputs of this pass stored (issued)
-#endif
   }
   if (want_stats) {
     // Per-tile partial sums meet in LDS ([32 tiles][64 channels][2] fp64 = 32 KB over the dead z area); one thread per (sample
@@ -407,15 +365,6 @@ winograd43_kernel(const Wino43Params p) {
       dst[0] = a; dst[1] = b;
     }
   }
-#ifdef IDIFF_W43_STAMP
-  if (has_ep && ep.colstats && tid == 0) {
-    uint64_t *st = reinterpret_cast<uint64_t *>(ep.colstats) + 10 * (int64_t)blockIdx.x;
-    st[6] = st_tail[0]; st[7] = st_tail[1]; st[8] = st_tail[2]; st[9] = st_tail[3];
-    st[0] = st_start; st[1] = st_loop0; st[2] = st_loop1; st[3] = __builtin_amdgcn_s_memrealtime();
-    st[4] = ((uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32) | (uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 4);   // XCC_ID, HW_ID
-    st[5] = (uint64_t)nsteps;
-  }
-#endif
 }
 
 // U = G g G^T in fp64 (f4_u_of_pair), rounded once
@@ -467,11 +416,9 @@ IDIFF_API int idiff_conv2d_winograd43_f32(const float *x, const float *u, float 
     return fail("conv2d_winograd43: geometry B=%d H=%d W=%d Cin=%d Cout=%d not supported (ask idiff_conv2d_winograd43_ok)", B, H, W, Cin, Cout);
   int64_t res_bytes = 0;
   if (int rc = wino_check_call("conv2d_winograd43", x, u, out, ep, B, H, W, Cout, F4_X_LIMIT, res_bytes)) return rc;
-#ifndef IDIFF_W43_STAMP
   if (ep && ep->colstats && idiff_conv2d_winograd43_colstats_split(B, H, W, Cin, Cout) <= 0)
     return fail("conv2d_winograd43: colstats needs whole workgroups per sample or whole samples per workgroup "
                 "(ask idiff_conv2d_winograd43_colstats_split)");
-#endif
   Wino43Params p = {};
   wino_fill(p, x, u, out, B, H, W, Cin, Cout, (int64_t)36 * Cin * Cout, res_bytes, ep, F4_COUT, true);
   wino_fill_tiles(p, 4, F4_TILES);

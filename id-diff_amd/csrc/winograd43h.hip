@@ -37,45 +37,12 @@ constexpr int H4_POS_BYTES = F4_TILES * H4_TILE_BYTES;                 // 2048
 constexpr int H4_STAGE_BYTES = F4_NPOS * H4_POS_BYTES;                 // 73,728
 constexpr int H4_SLOT_BYTES = PAIR_SLOT_BYTES;                         // 4096: one position of one (step, cout tile)
 constexpr int H4_PLANE_BYTES = PAIR_PLANE_BYTES;                       // 2048
-constexpr int H4_TOUCH_BYTES = 1024;                                   // landing zone of the look-ahead touches (see touch() in the kernel)
-constexpr size_t H4_LDS_BYTES = (2 * H4_STAGE_BYTES > (int)sizeof(float) * F4_Z_FLOATS ? 2 * H4_STAGE_BYTES : sizeof(float) * F4_Z_FLOATS) + H4_TOUCH_BYTES;
-#ifndef IDIFF_W43H_TOUCH_AHEAD
-#define IDIFF_W43H_TOUCH_AHEAD 4
-#endif
-#ifndef IDIFF_W43H_TOUCH_AT
-#define IDIFF_W43H_TOUCH_AT 8
-#endif
-#ifndef IDIFF_W43H_DMA_AT
-#define IDIFF_W43H_DMA_AT 0
-#endif
-#ifndef IDIFF_W43H_BRING
-#define IDIFF_W43H_BRING 3
-#endif
-constexpr int H4_BRING = IDIFF_W43H_BRING;     // positions of U requested ahead (register sets of 8)
-
-#ifndef IDIFF_W43H_STAGE_AT
-#define IDIFF_W43H_STAGE_AT 0
-#endif
-#ifndef IDIFF_W43H_U_AUX
-#define IDIFF_W43H_U_AUX 0          // cache policy bits of the U loads (1 = sc0, 2 = nt, 16 = sc1)
-#endif
-#ifndef IDIFF_W43H_X_AUX
-#define IDIFF_W43H_X_AUX 0          // ... of the patch loads
-#endif
-#ifndef IDIFF_W43H_COLORDER
-#define IDIFF_W43H_COLORDER 0
-#endif
-// the order in which a step's six patch columns are transformed, written and re-requested
-#if IDIFF_W43H_COLORDER == 1
-__device__ constexpr int H4_COL[6] = {0, 4, 1, 5, 2, 3};     // columns that neighbouring tiles share (4 = the right neighbour's 0, 5 = its 1) back to back
-#else
-__device__ constexpr int H4_COL[6] = {0, 1, 2, 3, 4, 5};
-#endif
-#ifndef IDIFF_W43H_COLS_PER_PART
-#define IDIFF_W43H_COLS_PER_PART 1
-#endif
-constexpr int H4_COLS_PER_PART = IDIFF_W43H_COLS_PER_PART;   // columns staged behind one position (1, 2, 3 or 6)
-constexpr int H4_STAGE_AT = IDIFF_W43H_STAGE_AT;   // the next step's staging starts behind this position (0 .. 2): seven parts, one per position
+// 1 KB behind the stages that nothing reads or writes: the landing zone of look-ahead touches of the patch's lines (tried, did not
+// pay, see profiles/r05_touch_ab.txt).  Kept so that the launch asks for the LDS size every figure under profiles/ was measured with.
+constexpr int H4_LDS_SPARE_BYTES = 1024;
+constexpr size_t H4_LDS_BYTES = (2 * H4_STAGE_BYTES > (int)sizeof(float) * F4_Z_FLOATS ? 2 * H4_STAGE_BYTES : sizeof(float) * F4_Z_FLOATS) + H4_LDS_SPARE_BYTES;
+constexpr int H4_BRING = 3;                    // positions of U requested ahead (register sets of 8): about one L2 round trip
+static_assert(9 % H4_BRING == 0, "the ring of U registers must divide the nine positions of a step (its phase then repeats every step)");
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
@@ -110,11 +77,6 @@ __device__ __forceinline__ void h4_bt_pairs(const H4Consts &k, const f2 P0, cons
 __global__ void __launch_bounds__(F4_THREADS, 2)
 winograd43h_kernel(const Wino43Params p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-#ifdef IDIFF_W43H_STAMP   // diagnostic build (scripts/wino43h_stamps.py): 100 MHz ticks at the phases of a workgroup's life; buffer in p.coef
-  const uint64_t st_start = __builtin_amdgcn_s_memrealtime();
-#endif
-  constexpr int BRING = H4_BRING;                // positions of U requested ahead; must divide 9 (the ring's phase then repeats every step)
-  static_assert(9 % H4_BRING == 0, "the ring of U registers must divide the nine positions of a step");
   char *const ldsb = reinterpret_cast<char *>(lds);
   const int nwg = p.tiles_m * p.tiles_n;
   int bid = blockIdx.x;
@@ -172,44 +134,13 @@ winograd43h_kernel(const Wino43Params p) {
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
       float v;
-#ifdef IDIFF_W43H_DIAG_NO_COL45   // timing-only builds: what the loop costs without the requests that repeat a neighbouring tile's (columns 4, 5 = the right
-      if (j >= 4) { dp[i >> 1][j][i & 1] = dp[i >> 1][j - 4][i & 1]; continue; }   // neighbour's 0, 1; rows 4, 5 = the lower neighbour's 0, 1)
-#endif
-#ifdef IDIFF_W43H_DIAG_NO_ROW45
-      if (i >= 4) { dp[i >> 1][j][i & 1] = dp[(i - 4) >> 1][j][i & 1]; continue; }
-#endif
       const uint32_t vo = i == 0 ? v_top : (i == 5 ? v_bot : v_mid);
       const int ro = i == 0 ? 0 : (i - 1) * row4;
-      if (j == 0) v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rX0, (int)(c0ok ? vo : invalid), choff + ro, IDIFF_W43H_X_AUX));
-      else if (j == 5) v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rX5, (int)(c5ok ? vo : invalid), choff + ro, IDIFF_W43H_X_AUX));
-      else v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rX, (int)vo, choff + ro + (j - 1) * (int)cin4, IDIFF_W43H_X_AUX));
+      if (j == 0) v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rX0, (int)(c0ok ? vo : invalid), choff + ro, 0));
+      else if (j == 5) v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rX5, (int)(c5ok ? vo : invalid), choff + ro, 0));
+      else v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rX, (int)vo, choff + ro + (j - 1) * (int)cin4, 0));
       dp[i >> 1][j][i & 1] = v;
     }
-  };
-  // Look-ahead touches -- an experiment that did NOT pay (A/B builds only, -DIDIFF_W43H_TOUCH): one dword per 64-byte chunk is 64 separate
-  // line requests per instruction, 192 per wave and step beside the 144 of the real patch requests: the texture-address path, which the
-  // kernel already keeps busy, pays more than the earlier arrival of the lines gives back.  The idea: the K loop's pace is set by the patch requests: they miss to HBM, and a wave's vector-memory operations retire in
-  // order, so every U request (an L2 hit) issued behind one of them waits out an HBM round trip -- at six of a step's nine positions
-  // (profiles/r04_wino43h_loop_experiments.txt).  Here each lane touches ONE dword of up to three 64-byte pixel chunks of the patch
-  // TOUCH_AHEAD steps ahead -- between them the lanes of a wave cover the 4 x 36 chunks their tiles will request -- so that the L2 has the
-  // lines when the real requests come: those then retire in an L2 round trip, and the one HBM-latency wait per step sits behind the
-  // touches, at one position.  The touches are LDS-DMA loads into a landing zone nobody reads: no destination registers.
-  auto touch = [&](int step) __attribute__((always_inline)) {
-#ifdef IDIFF_W43H_TOUCH           // OFF: measured 87.2 against 76.9 ms per forward (profiles/r05_touch_ab.txt)
-    typedef __attribute__((address_space(3))) void lds_void;
-    lds_void *zone = (lds_void *)(ldsb + 2 * H4_STAGE_BYTES + (wave & 3) * 256);
-    const int choff = min(step, nsteps - 1) * (H4_KC * 4);
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const int pix = (tid & 15) + 16 * q;             // this lane's pixel of its tile's 6 x 6 patch: pix = 6 i + j
-      const int i = (pix * 43) >> 8, j = pix - 6 * i;
-      // rows / columns outside the image are not special-cased: the address is then a neighbouring pixel's (a line some tile requests
-      // anyway) or beyond the tensor (no request at all: the descriptor's range check)
-      const bool ok = pix < 36 && v_mid != F4_INVALID;
-      const uint32_t off = v_mid + (uint32_t)((i - 1) * row4 + (j - 1) * (int)cin4);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rX, zone, 4, (int)(ok ? off : F4_INVALID), choff, 0, 0);
-    }
-#endif
   };
   // The dword (channels 2m, 2m + 1) this lane writes for every position: even lanes that of plane 0 (hi), odd lanes that of plane 1
   // (lo), which lies 32 bytes from it (bit 5 of the offset flipped)
@@ -220,15 +151,9 @@ winograd43h_kernel(const Wino43Params p) {
   const uint32_t sel0 = odd ? 0x01000504u : 0x05040100u, sel1 = sel0 + 0x02020202u;
   const H4Consts kc = {{p.c_nb2, p.c_na2}, {p.c_a, -p.c_a}, {p.c_b, -p.c_b}, p.c_nab2, p.c_nb2, p.c_na2, p.c_a, p.c_b};
   int f_step = 0;
-#ifdef IDIFF_W43H_DIAG_NO_VWRITE
-  uint32_t diag_sink = 0;
-#endif
   // The stage of a step in seven parts -- the transform along x (all rows), then one column at a time: transform along y, cut into pairs,
   // store, request the next step's column.  step() spreads them over the wave's positions (see there).
   auto stage_rows = [&]() __attribute__((always_inline)) {
-#ifdef IDIFF_W43H_DIAG_NO_STAGE   // timing-only build (scripts/wino43h_ab.py): no transform, no stage writes, no input loads
-    return;
-#endif
     // along x: two rows per instruction, in place
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
@@ -238,11 +163,7 @@ winograd43h_kernel(const Wino43Params p) {
       __builtin_amdgcn_sched_barrier(0);              // one row pair / column at a time: interleaved they need registers that do not exist
     }
   };
-  auto stage_col = [&](int buf, int j, bool last_col) __attribute__((always_inline)) {
-#ifdef IDIFF_W43H_DIAG_NO_STAGE
-    if (last_col) ++f_step;
-    (void)buf; return;
-#endif
+  auto stage_col = [&](int buf, int j) __attribute__((always_inline)) {
     char *Vd = ldsb + buf * H4_STAGE_BYTES + w_off;
     // along y: V(0, j), V(5, j) | V(1, j), V(2, j) | V(3, j), V(4, j); each pair is cut into its fp16 pairs and written
     f2 v[3];
@@ -261,42 +182,18 @@ winograd43h_kernel(const Wino43Params p) {
       const uint32_t give = odd ? xh : xl, keep = odd ? xl : xh;
       const uint32_t got = (uint32_t)__builtin_amdgcn_update_dpp((int)give, (int)give, 0xB1, 0xF, 0xF, false);   // quad_perm [1, 0, 3, 2]: every lane receives
       char *qa = Vd + (6 * row_lo[q] + j) * H4_POS_BYTES, *qb = Vd + (6 * row_hi[q] + j) * H4_POS_BYTES;
-#ifdef IDIFF_W43H_DIAG_NO_VWRITE  // timing-only build: the pairs are summed into one register instead of written
-      diag_sink += keep + got; (void)qa; (void)qb;
-#else
       *reinterpret_cast<uint32_t *>(qa) = __builtin_amdgcn_perm(got, keep, sel0);
       *reinterpret_cast<uint32_t *>(qb) = __builtin_amdgcn_perm(got, keep, sel1);
-#endif
     }
-#ifdef IDIFF_W43H_DIAG_NO_XLOAD   // timing-only build: the input is loaded for the first step only
-    if (f_step == 0)
-#endif
     fetch_col(j, f_step + 1);                         // the column's registers are free: the next step's column moves in
-    if (last_col) ++f_step;
+    if (j == 5) ++f_step;                             // the last column: the whole patch now holds the next step's requests
     __builtin_amdgcn_sched_barrier(0);
   };
   auto stage = [&](int buf) __attribute__((always_inline)) {       // all of it at once: the first step's, before the loop
     stage_rows();
 #pragma unroll
-    for (int q = 0; q < 6; ++q) stage_col(buf, H4_COL[q], q == 5);
+    for (int j = 0; j < 6; ++j) stage_col(buf, j);
   };
-
-#ifdef IDIFF_W43H_DIAG_DMA
-  // Timing-only build (scripts/wino43h_ab.py, results wrong by construction): what the K loop would cost if the transformed, pair-cut
-  // patches V came READY from HBM (written by the producing GroupNorm pass) and went global -> LDS by LDS-DMA -- no patch registers, no
-  // transform, no LDS stores; each wave moves its ninth of the 73,728-byte stage with nine 1 KB requests.  The source is the input tensor
-  // itself, read as a stream of stage-sized blocks (one per workgroup row and step, shared by the workgroups of the other cout tiles).
-  auto dma_stage = [&](int buf, int step) __attribute__((always_inline)) {
-    typedef __attribute__((address_space(3))) void lds_void;
-    const uint32_t blocks = (p.x_bytes - H4_STAGE_BYTES) / H4_STAGE_BYTES;
-    const uint32_t blk = ((uint32_t)tile_m * (uint32_t)nsteps + (uint32_t)min(step, nsteps - 1)) % (blocks ? blocks : 1u);
-    const int base = (int)(blk * (uint32_t)H4_STAGE_BYTES) + wave * (H4_STAGE_BYTES / 8);
-#pragma unroll
-    for (int i = 0; i < 9; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rX, (lds_void *)(ldsb + buf * H4_STAGE_BYTES + wave * (H4_STAGE_BYTES / 8) + i * 1024), 16,
-                                               lane * 16, base + i * 1024, 0, 0);
-  };
-#endif
 
   // ---------------------------------------------------------------- contraction
   floatx16 acc[9];
@@ -309,21 +206,18 @@ winograd43h_kernel(const Wino43Params p) {
   // V fragment of tile row fr: chunk fh of plane 0, chunk 2 + fh of plane 1 (bit 5 flipped), swizzled as the writer does
   const int a_off = pos0 * H4_POS_BYTES + fr * H4_TILE_BYTES + ((fh ^ ((fr >> 2) & 3)) << 4);
   const uint32_t u_lane = (uint32_t)((wh * 32 + fr) * (H4_KC * 2) + fh * 16);
-  halfx8 bh[BRING], bl[BRING];
+  halfx8 bh[H4_BRING], bl[H4_BRING];
   auto load_b = [&](int pp, int step) __attribute__((always_inline)) {
     const int slot = pos0 + (pp / 3) * 6 + (pp % 3);
     const int soff = ((step * p.tiles_n + tile_n) * F4_NPOS + slot) * H4_SLOT_BYTES;
-    bh[pp % BRING] = __builtin_bit_cast(halfx8, __builtin_amdgcn_raw_buffer_load_b128(rU, (int)u_lane, soff, IDIFF_W43H_U_AUX));
-    bl[pp % BRING] = __builtin_bit_cast(halfx8, __builtin_amdgcn_raw_buffer_load_b128(rU, (int)u_lane + H4_PLANE_BYTES, soff, IDIFF_W43H_U_AUX));
+    bh[pp % H4_BRING] = __builtin_bit_cast(halfx8, __builtin_amdgcn_raw_buffer_load_b128(rU, (int)u_lane, soff, 0));
+    bl[pp % H4_BRING] = __builtin_bit_cast(halfx8, __builtin_amdgcn_raw_buffer_load_b128(rU, (int)u_lane + H4_PLANE_BYTES, soff, 0));
   };
   // A step: nine positions, each three matrix instructions whose U operands were requested three positions earlier -- about one L2 round
-  // trip (~1600 clocks) per three positions, so the contraction alone is bound by that latency (stamps: 5200 clocks of a 9000-clock step
-  // when the staging was done in one block of 3000-3600 clocks beside it).  The next step's staging is therefore cut into seven parts and
-  // one part follows each of the first seven positions' matrix instructions: the wave does its vector work while its own loads fly.
-#ifdef IDIFF_W43H_STAMP
-  uint32_t ph_stage = 0, ph_wait = 0;                 // shader-clock ticks this wave spent in its staging parts / at the step barrier
-#define IDIFF_PH_T() ({ __builtin_amdgcn_sched_barrier(0); const uint64_t t_ = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); t_; })
-#endif
+  // trip (~1600 clocks) per three positions, so the contraction alone is bound by that latency (clock stamps: 5200 clocks of a 9000-clock
+  // step when the staging was done in one block of 3000-3600 clocks beside it).  The next step's staging is therefore cut into seven parts
+  // -- the rows behind position 0, column j behind position 1 + j -- and one part follows each of the first seven positions' matrix
+  // instructions: the wave does its vector work while its own loads fly.
   auto step = [&](int s, auto last) __attribute__((always_inline)) {
     constexpr bool LAST = decltype(last)::value;
     const int buf = s & 1;
@@ -336,106 +230,36 @@ winograd43h_kernel(const Wino43Params p) {
     for (int pp = 0; pp < 9; ++pp) {
       __builtin_amdgcn_sched_barrier(0);
       if (pp + 1 < 9) { ah[(pp + 1) & 1] = a_hi(pp + 1); al[(pp + 1) & 1] = a_lo(pp + 1); }
-      const halfx8 xh = ah[pp & 1], xl = al[pp & 1], yh = bh[pp % BRING], yl = bl[pp % BRING];
-#ifdef IDIFF_W43H_DIAG_NO_MFMA    // timing-only build: the operands are consumed by one vector instruction each instead
-      acc[pp][0] += (float)xh[0] + (float)xl[0] + (float)yh[0] + (float)yl[0];
-#else
+      const halfx8 xh = ah[pp & 1], xl = al[pp & 1], yh = bh[pp % H4_BRING], yl = bl[pp % H4_BRING];
       acc[pp] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh, yh, acc[pp], 0, 0, 0);
       acc[pp] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh, yl, acc[pp], 0, 0, 0);
       acc[pp] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xl, yh, acc[pp], 0, 0, 0);
-#endif
-#ifdef IDIFF_W43H_DIAG_NO_BLOAD   // timing-only build: U is loaded for the first step only
-      if (s == 0) { if (pp + BRING < 9) load_b(pp + BRING, s); }
-#else
-      if (pp + BRING < 9) load_b(pp + BRING, s); else if (!LAST) load_b(pp + BRING - 9, s + 1);
-#endif
-      if (!LAST && pp == IDIFF_W43H_TOUCH_AT) touch(s + IDIFF_W43H_TOUCH_AHEAD);
-#ifdef IDIFF_W43H_DIAG_DMA
-      if (!LAST && pp == IDIFF_W43H_DMA_AT) dma_stage(buf ^ 1, s + 1);
-#endif
+      if (pp + H4_BRING < 9) load_b(pp + H4_BRING, s); else if (!LAST) load_b(pp + H4_BRING - 9, s + 1);
       if (!LAST) {
         __builtin_amdgcn_sched_barrier(0);
-#ifdef IDIFF_W43H_STAMP
-        const uint64_t a_ = IDIFF_PH_T();
-#endif
-        if (pp == H4_STAGE_AT) stage_rows();
+        if (pp == 0) stage_rows();
 #pragma unroll
-        for (int q = 0; q < 6; ++q)
-          if (pp == H4_STAGE_AT + 1 + q / H4_COLS_PER_PART) stage_col(buf ^ 1, H4_COL[q], q == 5);
-#ifdef IDIFF_W43H_STAMP
-        ph_stage += (uint32_t)(IDIFF_PH_T() - a_);
-#endif
+        for (int j = 0; j < 6; ++j)
+          if (pp == 1 + j) stage_col(buf ^ 1, j);
       }
     }
-#ifdef IDIFF_W43H_STAMP
-    { const uint64_t a_ = IDIFF_PH_T(); __syncthreads(); ph_wait += (uint32_t)(IDIFF_PH_T() - a_); }
-#else
     __syncthreads();
-#endif
   };
 
-#ifdef IDIFF_W43H_STAMP
-  __builtin_amdgcn_sched_barrier(0);
-  const uint64_t st_pro0 = __builtin_amdgcn_s_memrealtime();     // set-up done, nothing requested yet
-  __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
-  for (int pp = 0; pp < BRING; ++pp) load_b(pp, 0);
+  for (int pp = 0; pp < H4_BRING; ++pp) load_b(pp, 0);
 #pragma unroll
-  for (int q = 0; q < 6; ++q) fetch_col(H4_COL[q], 0);
-#ifdef IDIFF_W43H_STAMP
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  const uint64_t st_pro1 = __builtin_amdgcn_s_memrealtime();     // first operands arrived
-  __builtin_amdgcn_sched_barrier(0);
-#endif
+  for (int j = 0; j < 6; ++j) fetch_col(j, 0);
   stage(0);
-#ifdef IDIFF_W43H_DIAG_DMA
-  dma_stage(0, 0);
-#endif
-#ifdef IDIFF_W43H_STAMP
-  __builtin_amdgcn_sched_barrier(0);
-  const uint64_t st_pro2 = __builtin_amdgcn_s_memrealtime();     // first stage written by this wave
-  __builtin_amdgcn_sched_barrier(0);
-#endif
   __syncthreads();
-#ifdef IDIFF_W43H_STAMP
-  const uint64_t st_loop0 = __builtin_amdgcn_s_memrealtime();
-#endif
   {
     int s = 0;                                        // at least two steps (Cin >= 32, checked by the launcher)
     do step(s, std::false_type()); while (++s + 1 < nsteps);
   }
   step(nsteps - 1, std::true_type());
-#ifdef IDIFF_W43H_STAMP
-  const uint64_t st_loop1 = __builtin_amdgcn_s_memrealtime();
-  uint64_t *st_out = p.stamps ? p.stamps + 8 * (int64_t)blockIdx.x : nullptr;
-  if (tid == 0 && st_out) { st_out[0] = st_start; st_out[1] = st_loop0; st_out[2] = st_loop1; }
-  // phase clocks of waves 0 and 4 (the two waves of one SIMD), lane 0 each
-  if ((tid == 0 || tid == 256) && p.stamps) {
-    uint64_t *q = p.stamps + 8 * (int64_t)gridDim.x + 4 * ((int64_t)blockIdx.x * 2 + (tid >> 8));
-    q[0] = ph_stage; q[1] = ph_wait; q[2] = ((st_pro0 - st_start) << 32) | ((st_pro1 - st_pro0) << 16) | (st_pro2 - st_pro1); q[3] = st_loop0 - st_pro2;
-  }
-#endif
 
-#ifdef IDIFF_W43H_DIAG_NO_VWRITE
-  if (diag_sink == 12345u) ldsb[tid] = 1;
-#endif
   const float descale = p.u[(int64_t)36 * p.Cin * p.Cout];
-#ifdef IDIFF_W43H_DIAG_NO_TAIL     // timing-only build: one store per lane instead of the tail
-  float diag_sum = 0.f;
-#pragma unroll
-  for (int i = 0; i < 9; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) diag_sum += acc[i][r];
-  if (diag_sum == 12345.f) p.out[tid] = descale;
-#else
-#ifdef IDIFF_W43H_STAMP
-  f4_tail<true>(p, lds, acc, tile0, tile_m, n0, wh, wa, wb, descale, st_out);
-#else
   f4_tail<true>(p, lds, acc, tile0, tile_m, n0, wh, wa, wb, descale);
-#endif
-#endif
 }
 
 bool h4_geometry_ok(int B, int H, int W, int Cin, int Cout) {
@@ -473,9 +297,6 @@ IDIFF_API int idiff_conv2d_winograd43h_f32(const float *x, const float *u, float
   Wino43Params p = {};
   wino_fill(p, x, u, out, B, H, W, Cin, Cout, (int64_t)36 * Cin * Cout, res_bytes, ep, F4_COUT, true);
   wino_fill_tiles(p, 4, F4_TILES);
-#ifdef IDIFF_W43H_STAMP
-  { const char *e = getenv("IDIFF_W43H_STAMP_PTR"); p.stamps = e ? reinterpret_cast<uint64_t *>(strtoull(e, nullptr, 0)) : nullptr; }
-#endif
   static AttrGuard guard;
   const void *fn = reinterpret_cast<const void *>(winograd43h_kernel);
   if (int rc = set_dynamic_lds_once(guard, &fn, 1, (int)H4_LDS_BYTES, "conv2d_winograd43h")) return rc;
