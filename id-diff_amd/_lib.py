@@ -138,6 +138,8 @@ _SIGNATURES = {
     "idiff_isomap_project_f64": (c_i, [c_p, c_p, c_i, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p]),
     "idiff_render_squares_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
     "idiff_render_gaussians_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
+    "idiff_ksphere_union_ok": (c_i, [c_i, c_i, c_i]),
+    "idiff_ksphere_union_score_f32": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -1329,3 +1331,45 @@ def render_gaussians(std, centres, S, out=None):
         k = int(bad.nonzero()[0][0])
         raise ValueError(f"render_gaussians: centre {k} = {tuple(int(v) for v in c[k])} is outside the {S} x {S} image")
     return _render("idiff_render_gaussians_f32", std, c, S, out)
+
+
+# ------------------------------------------------------------------------------------------- union of k-spheres
+def ksphere_union_ok(n, J, P):
+    """True where ksphere_union_score serves frames of P columns in all, J components, in R^n (idiff_ksphere_union_ok: host only)."""
+    return bool(lib().idiff_ksphere_union_ok(int(n), int(J), int(P)))
+
+
+def ksphere_union_score(x, qcat, comp, sigma, mult=None, out=None, refused=None):
+    """out [B, n] = mult[b] (-x_b + sum_j w_j (R_j A_j / r_j) Q_j Q_j^T x_b): the exact score of the noised union of spheres times
+    mult sigma^2, one launch (idiff_ksphere_union_score_f32).  x [B, n] fp32, qcat [n, P] fp64, sigma [B] and mult [B] (or None) fp32 on
+    the device; comp: HOST rows (first column, columns, radius, log weight), one per component.  Returns (out, refused): refused is
+    a device int32 [1] the launch ADDS its count of refused rows to (made and zeroed here when not given); those rows are NaN.
+    A shape the kernel does not serve is a RuntimeError before any launch."""
+    import numpy as np
+    _dev(x, "x"); _dev(qcat, "qcat", dtype=torch.float64); _dev(sigma, "sigma")
+    if x.ndim != 2 or qcat.ndim != 2 or qcat.shape[0] != x.shape[1] or sigma.numel() != x.shape[0]:
+        raise RuntimeError(f"ksphere_union_score: x {tuple(x.shape)}, qcat {tuple(qcat.shape)}, sigma {tuple(sigma.shape)}")
+    B, n = x.shape
+    P = qcat.shape[1]
+    tab = np.ascontiguousarray(np.asarray(comp, dtype=np.float64))
+    if tab.ndim != 2 or tab.shape[1] != 4 or tab.shape[0] < 1:
+        raise ValueError(f"ksphere_union_score: expected a host table [J, 4], got {tuple(tab.shape)}")
+    J = tab.shape[0]
+    if not ksphere_union_ok(n, J, P):
+        raise RuntimeError(f"ksphere_union_score: n = {n}, J = {J}, P = {P} is not served (idiff_ksphere_union_ok): at most 8 components "
+                           "of at most 128 columns each, and the frames must fit the LDS")
+    if mult is not None:
+        _dev(mult, "mult")
+        if mult.numel() != B:
+            raise RuntimeError(f"ksphere_union_score: mult holds {mult.numel()} values for {B} rows")
+    if out is None:
+        out = torch.empty_like(x)
+    _dev(out, "out")
+    if out.shape != x.shape:
+        raise RuntimeError(f"ksphere_union_score: out {tuple(out.shape)} for x {tuple(x.shape)}")
+    if refused is None:
+        refused = torch.zeros(1, device=x.device, dtype=torch.int32)
+    _dev(refused, "refused", dtype=torch.int32)
+    _check(lib().idiff_ksphere_union_score_f32(x.data_ptr(), qcat.data_ptr(), tab.ctypes.data, sigma.data_ptr(), _ptr(mult), out.data_ptr(),
+                                               refused.data_ptr(), B, n, J, P, _stream()), "idiff_ksphere_union_score_f32")
+    return out, refused

@@ -610,6 +610,26 @@ int idiff_symmetrize_min_f64(double *G, int N, void *stream);
 int idiff_render_squares_f32(const float *coef, const int *rects, float *out, int N, int K, int S, void *stream);
 int idiff_render_gaussians_f32(const double *std, const int *centres, float *out, int N, int K, int S, void *stream);
 
+/* ------------------------------------------------------------------ exact score of a noised union of k-spheres */
+
+/* The mixture of J uniform distributions on R_j S^{k_j} inside span Q_j (Q_j [n, p_j] orthonormal, p_j = k_j + 1), convolved with
+ * N(0, sigma^2 I): out[b, :] = mult[b] (-x_b + sum_j w_j (R_j A_j / r_j) Q_j Q_j^T x_b), i.e. mult[b] sigma[b]^2 times the score
+ * (csrc/ksphere_union.hip has the formulas; models/ksphere_union_exact.py: reference_score restates them in numpy).  One launch, x
+ * read once, out written once, every operation between the two in fp64, one rounding to fp32.
+ *
+ * x, out [B, n] fp32; Qcat [n, P] fp64 row-major = [Q_0 | ... | Q_{J-1}]; sigma [B] fp32; mult [B] fp32 or NULL (= 1); all device
+ * pointers.  comp is a HOST table [J, 4] of doubles (first column off_j, columns p_j, radius R_j, log pi_j): the frames must tile
+ * [0, P) in order.  A row in which a component with kappa_j = r_j R_j / sigma^2 < max(32, p_j^2 / 16) cannot be shown to have
+ * weight exactly 0 in fp64, or that has no component above that threshold, is REFUSED: written as NaN, and *refused (device int32,
+ * zeroed by the caller) is incremented.
+ *
+ * idiff_ksphere_union_ok (host only, nothing launched) = 1 where the launch is served: 1 <= J <= 8, J <= P <= 128 J (the launch also
+ * checks p_j <= 128 and p_j <= n), and, Qcat being kept in LDS beside at least two waves' tiles, with Pst = 16 ceil(P / 16) + 2 and
+ * n4 = 4 ceil(n / 4):   8 n Pst + 384 + 2 (128 Pst + 64 n4 + 4224) <= 163840 bytes. */
+int idiff_ksphere_union_ok(int n, int J, int P);
+int idiff_ksphere_union_score_f32(const float *x, const double *Qcat, const double *comp, const float *sigma, const float *mult,
+                                  float *out, int *refused, int B, int n, int J, int P, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
