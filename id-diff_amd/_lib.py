@@ -53,6 +53,9 @@ _SIGNATURES = {
                              ctypes.POINTER(Epilogue), c_p]),
     "idiff_gemm_2src_f32": (c_i, [c_p, c_p, c_i64, c_i, c_p, c_i64, c_p, c_i64, c_i, c_i, c_i, ctypes.POINTER(Epilogue), c_p]),
     "idiff_conv2d_nhwc_f32": (c_i, [c_p, c_p, c_p] + [c_i] * 10 + [ctypes.POINTER(Epilogue), c_p]),
+    "idiff_gemm_route": (ctypes.c_char_p, [c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_i, c_i, c_i, c_i,
+                                           ctypes.POINTER(Epilogue), c_i]),
+    "idiff_conv2d_route": (ctypes.c_char_p, [c_p, c_p, c_p] + [c_i] * 10 + [ctypes.POINTER(Epilogue)]),
     "idiff_gemm_colstats_split": (c_i, [c_i, c_i, c_i, c_i64, c_i64, c_i]),
     "idiff_conv2d_colstats_split": (c_i, [c_i] * 10),
     "idiff_conv2d_winograd_ok": (c_i, [c_i] * 5),
@@ -489,6 +492,26 @@ def conv2d_nhwc(x, wt, out, B, H, W, Cin, Cout, KH, KW, stride, pad, epilogue=No
     _check(lib().idiff_conv2d_nhwc_f32(x.data_ptr(), wt.data_ptr(), out.data_ptr(), B, H, W, Cin, Cout, KH, KW, stride,
                                        pad, pad if pad_hi is None else pad_hi, ep, _stream()), "idiff_conv2d_nhwc_f32")
     return out
+
+
+def _addr(t):
+    return t if isinstance(t, int) else t.data_ptr()
+
+
+def gemm_route(a, bt, out, M, N, K, lda, ldb, ldc, epilogue=None, batch=1, stride_a=0, stride_b=0, stride_c=0, pairs=False):
+    """"<family> <tile> <arithmetic> <epilogue form>" of the launch ``gemm`` (``pairs``: ``gemm_pairs``) would make for these arguments
+    (idiff_gemm_route), None if it refuses them.  a / bt / out: tensors or raw addresses (only null and 16-byte alignment matter);
+    nothing is launched."""
+    name = lib().idiff_gemm_route(_addr(a), lda, stride_a, _addr(bt), ldb, stride_b, _addr(out), ldc, stride_c, M, N, K, batch,
+                                  _ep_ref(epilogue, "gemm_route"), int(bool(pairs)))
+    return None if name is None else name.decode()
+
+
+def conv2d_route(x, wt, out, B, H, W, Cin, Cout, KH, KW, stride, pad, epilogue=None, pad_hi=None):
+    """The same for ``conv2d_nhwc`` (idiff_conv2d_route)."""
+    name = lib().idiff_conv2d_route(_addr(x), _addr(wt), _addr(out), B, H, W, Cin, Cout, KH, KW, stride, pad, pad if pad_hi is None else pad_hi,
+                                    _ep_ref(epilogue, "conv2d_route"))
+    return None if name is None else name.decode()
 
 
 # ---- Winograd convolutions.  Five kernel forms, named by the stem of their entry points (idiff_<stem>_weight_floats,

@@ -897,6 +897,7 @@ igemm_pipe_kernel(const IgemmParams p) {
   }
 }
 
+// (p.vec_ep / p.buf_ep and the extents that go with them: igemm_choose)
 template <int BM, int BN, int WARPS_M, int WARPS_N, bool CONV, bool DBUF = true, int SPLIT = 0>
 int launch_pipe(IgemmParams &p, int batch, hipStream_t st) {
   p.tiles_m = idiff::ceil_div(p.M, BM);
@@ -912,68 +913,144 @@ int launch_pipe(IgemmParams &p, int batch, hipStream_t st) {
     const void *fn = reinterpret_cast<const void *>(kern);
     if (int rc = idiff::set_dynamic_lds_once(guard, &fn, 1, (int)lds_bytes, "igemm")) return rc;
   }
-  {
-    const idiff_epilogue &e = p.ep;
-    const bool al = (p.N % 4 == 0) && (p.ldc % 4 == 0) && (p.strideC % 4 == 0) && aligned16(p.C) &&
-                    (!p.has_ep || ((!e.bias || aligned16(e.bias)) && (!e.rowbias || (aligned16(e.rowbias) && e.ld_rowbias % 4 == 0)) &&
-                                   (!e.residual || (aligned16(e.residual) && e.ld_residual % 4 == 0))));
-    p.vec_ep = al && !idiff::option(idiff::OPT_SCALAR_EPILOGUE);
-    // 32-bit addressing of C and the residual (igemm_pipe_kernel's first epilogue form): extents below 0xE0000000 so that
-    // an out-of-range start stays out of range after the row steps of one tile are added
-    const int64_t c_bytes = ((int64_t)(p.M - 1) * p.ldc + p.N) * 4;
-    const int64_t res_bytes = (p.has_ep && e.residual) ? ((int64_t)(p.M - 1) * e.ld_residual + p.N) * 4 : 0;
-    const int64_t pitch = p.ldc > e.ld_residual ? p.ldc : e.ld_residual;
-    p.buf_ep = p.vec_ep && c_bytes < 0xE0000000ll && res_bytes < 0xE0000000ll && (int64_t)BM * pitch * 4 < 0x0FFFFFF0ll;
-    p.c_bytes = p.buf_ep ? (uint32_t)c_bytes : 0; p.res_bytes = p.buf_ep ? (uint32_t)res_bytes : 0;
-  }
   dim3 grid(p.tiles_m * p.tiles_n, batch);
   hipLaunchKernelGGL(kern, grid, dim3(WARPS_M * WARPS_N * 64), lds_bytes, st, p);
   return idiff::launch_status(CONV ? "igemm_pipe_conv" : "igemm_pipe_linear");
 }
 
-// Rows per workgroup tile the pipelined dispatcher picks for (M, N, batch); keep in step with dispatch_pipe.
-int pipe_tile_rows(int M, int N, int batch) {
-  const int64_t wg_big = (int64_t)idiff::ceil_div(M, 128) * idiff::ceil_div(N, 128) * batch;
-  if (N > 64 && wg_big >= 256) return 128;
-  const int64_t wg_mid = (int64_t)idiff::ceil_div(M, 128) * idiff::ceil_div(N, 64) * batch;
-  if (wg_mid >= 256 || M >= 4096) return 128;
-  return 64;
-}
+// ---- which kernel and which epilogue form a contraction takes: ONE host function, called by every launcher below and by the route
+// queries (idiff_gemm_route / idiff_conv2d_route), which launch nothing.
+enum IgemmFamily { FAM_PIPE, FAM_DIRECT_VEC, FAM_DIRECT_SCALAR, FAM_NARROW };
+enum IgemmArith { AR_FP32, AR_FP32_1BUF, AR_SPLIT, AR_PAIRS };            // AR_FP32_1BUF: the single-LDS-buffer fp32 form (four workgroups per CU)
+enum IgemmEpForm { EPF_BUF_BLOCK, EPF_BUF_ROW, EPF_VEC64, EPF_SCALAR };   // the three forms of igemm_pipe_kernel's tail; the first by its group handling
+struct IgemmPlan { int family, bm, bn, arith, ep_form; };
+// what a caller asks of igemm_choose: the pipelined kernel with the tile and arithmetic chosen by size and switches, the pipelined kernel
+// on fp16 pairs (one tile), or the general kernel with / without 16-byte operand loads
+enum IgemmWant { WANT_PIPE, WANT_PAIRS, WANT_DIRECT_VEC, WANT_DIRECT_SCALAR };
 
-template <bool CONV>
-int dispatch_pipe(IgemmParams &p, int batch, hipStream_t st) {
+IgemmPlan igemm_choose(IgemmParams &p, int batch, int want) {
+  IgemmPlan c = {};
   const int64_t wg_big = (int64_t)idiff::ceil_div(p.M, 128) * idiff::ceil_div(p.N, 128) * batch;
-  if (!idiff::option(idiff::OPT_NO_SPLIT)) {
+  const int64_t wg_mid = (int64_t)idiff::ceil_div(p.M, 128) * idiff::ceil_div(p.N, 64) * batch;
+  auto tile = [&](int bm, int bn, int arith) { c.bm = bm; c.bn = bn; c.arith = arith; };
+  if (want == WANT_DIRECT_VEC || want == WANT_DIRECT_SCALAR) {
+    // Pick the largest tile that still yields >= ~2 workgroups per CU pair; small problems get small tiles.
+    c.family = want == WANT_DIRECT_VEC ? FAM_DIRECT_VEC : FAM_DIRECT_SCALAR;
+    c.ep_form = EPF_SCALAR;                          // igemm_kernel has the one tail
+    if (p.N > 64 && wg_big >= 256) tile(128, 128, AR_FP32);
+    else if (wg_mid >= 256 || p.M >= 4096) tile(128, 64, AR_FP32);
+    else tile(64, 64, AR_FP32);
+    return c;
+  }
+  c.family = FAM_PIPE;
+  if (want == WANT_PAIRS) tile(128, 128, AR_PAIRS);
+  else if (!idiff::option(idiff::OPT_NO_SPLIT)) {
     // split-precision products on the bf16 matrix cores (see split4): single LDS buffer (60 KB at 128 x 128: two workgroups
     // per CU), the same tile choice as below.  (A double-buffered form with the splitting of tile t + 1 interleaved between
     // the matrix instructions of tile t by sched_group_barrier was built and measured: 118-128 TFLOP/s against 140-180 for
     // this one -- at 32 k per tile a 128 x 128 workgroup asks the L2 for 32 KB per 1600 matrix-pipe cycles, which is what
     // bounds it, not the instruction mix.)
-    if (p.N > 64 && wg_big >= 256) return launch_pipe<128, 128, 2, 2, CONV, false, 1>(p, batch, st);
-    if (p.N <= 32 && p.M >= 4096) return launch_pipe<128, 32, 4, 1, CONV, false, 1>(p, batch, st);
-    const int64_t wg_mid_s = (int64_t)idiff::ceil_div(p.M, 128) * idiff::ceil_div(p.N, 64) * batch;
-    if (wg_mid_s >= 256 || p.M >= 4096) return launch_pipe<128, 64, 2, 2, CONV, false, 1>(p, batch, st);
-    return launch_pipe<64, 64, 2, 2, CONV, false, 1>(p, batch, st);
+    if (p.N > 64 && wg_big >= 256) tile(128, 128, AR_SPLIT);
+    else if (p.N <= 32 && p.M >= 4096) tile(128, 32, AR_SPLIT);
+    else if (wg_mid >= 256 || p.M >= 4096) tile(128, 64, AR_SPLIT);
+    else tile(64, 64, AR_SPLIT);
   }
   // >= 4 workgroups per CU available: single LDS buffer, 128 registers, four resident workgroups per CU
   // (measured 135-142 TFLOP/s vs 124-135 for the double-buffered two-workgroup form)
-  if (p.N > 64 && wg_big >= 1024 && !idiff::option(idiff::OPT_DBUF_ONLY)) return launch_pipe<128, 128, 2, 2, CONV, false>(p, batch, st);
-  if (p.N > 64 && wg_big >= 256) return launch_pipe<128, 128, 2, 2, CONV>(p, batch, st);
+  else if (p.N > 64 && wg_big >= 1024 && !idiff::option(idiff::OPT_DBUF_ONLY)) tile(128, 128, AR_FP32_1BUF);
+  else if (p.N > 64 && wg_big >= 256) tile(128, 128, AR_FP32);
   // narrow outputs (the 3-channel image conv at the end of the U-Nets): one 32-wide MFMA column instead of two
-  if (p.N <= 32 && p.M >= 4096) return launch_pipe<128, 32, 4, 1, CONV>(p, batch, st);
-  const int64_t wg_mid = (int64_t)idiff::ceil_div(p.M, 128) * idiff::ceil_div(p.N, 64) * batch;
-  if (wg_mid >= 256 || p.M >= 4096) return launch_pipe<128, 64, 2, 2, CONV>(p, batch, st);
-  return launch_pipe<64, 64, 2, 2, CONV>(p, batch, st);
+  else if (p.N <= 32 && p.M >= 4096) tile(128, 32, AR_FP32);
+  else if (wg_mid >= 256 || p.M >= 4096) tile(128, 64, AR_FP32);
+  else tile(64, 64, AR_FP32);
+  // the tail: 16-byte accesses when every operand it touches allows them, else one element at a time
+  const idiff_epilogue &e = p.ep;
+  const bool al = (p.N % 4 == 0) && (p.ldc % 4 == 0) && (p.strideC % 4 == 0) && aligned16(p.C) &&
+                  (!p.has_ep || ((!e.bias || aligned16(e.bias)) && (!e.rowbias || (aligned16(e.rowbias) && e.ld_rowbias % 4 == 0)) &&
+                                 (!e.residual || (aligned16(e.residual) && e.ld_residual % 4 == 0))));
+  p.vec_ep = al && !idiff::option(idiff::OPT_SCALAR_EPILOGUE);
+  // 32-bit addressing of C and the residual (igemm_pipe_kernel's first epilogue form): extents below 0xE0000000 so that
+  // an out-of-range start stays out of range after the row steps of one tile are added
+  const int64_t c_bytes = ((int64_t)(p.M - 1) * p.ldc + p.N) * 4;
+  const int64_t res_bytes = (p.has_ep && e.residual) ? ((int64_t)(p.M - 1) * e.ld_residual + p.N) * 4 : 0;
+  const int64_t pitch = p.ldc > e.ld_residual ? p.ldc : e.ld_residual;
+  p.buf_ep = p.vec_ep && c_bytes < 0xE0000000ll && res_bytes < 0xE0000000ll && (int64_t)c.bm * pitch * 4 < 0x0FFFFFF0ll;
+  p.c_bytes = p.buf_ep ? (uint32_t)c_bytes : 0; p.res_bytes = p.buf_ep ? (uint32_t)res_bytes : 0;
+  // (the kernel folds the group terms per 32-row block under the same condition: `block_groups`)
+  c.ep_form = !p.vec_ep ? EPF_SCALAR : !p.buf_ep ? EPF_VEC64 : (e.rows_per_group % 32 == 0 ? EPF_BUF_BLOCK : EPF_BUF_ROW);
+  return c;
 }
 
-template <bool CONV, bool VEC>
-int dispatch(IgemmParams &p, int batch, hipStream_t st) {
-  // Pick the largest tile that still yields >= ~2 workgroups per CU pair; small problems get small tiles.
-  const int64_t wg_big = (int64_t)idiff::ceil_div(p.M, 128) * idiff::ceil_div(p.N, 128) * batch;
-  if (p.N > 64 && wg_big >= 256) return launch_cfg<128, 128, 2, 2, CONV, VEC>(p, batch, st);
-  const int64_t wg_mid = (int64_t)idiff::ceil_div(p.M, 128) * idiff::ceil_div(p.N, 64) * batch;
-  if (wg_mid >= 256 || p.M >= 4096) return launch_cfg<128, 64, 2, 2, CONV, VEC>(p, batch, st);
-  return launch_cfg<64, 64, 2, 2, CONV, VEC>(p, batch, st);
+template <bool CONV>
+int igemm_launch(const IgemmPlan &c, IgemmParams &p, int batch, hipStream_t st) {
+  const int t = c.bm * 1000 + c.bn;
+  if (c.family == FAM_DIRECT_VEC || c.family == FAM_DIRECT_SCALAR) {
+    // (the convolution's loader always reads 16 bytes: Cin % 4 == 0)
+    const bool vec = c.family == FAM_DIRECT_VEC;
+    if constexpr (CONV) {
+      if (vec && t == 128128) return launch_cfg<128, 128, 2, 2, true, true>(p, batch, st);
+      if (vec && t == 128064) return launch_cfg<128, 64, 2, 2, true, true>(p, batch, st);
+      if (vec && t == 64064) return launch_cfg<64, 64, 2, 2, true, true>(p, batch, st);
+    } else {
+      if (t == 128128) return vec ? launch_cfg<128, 128, 2, 2, false, true>(p, batch, st) : launch_cfg<128, 128, 2, 2, false, false>(p, batch, st);
+      if (t == 128064) return vec ? launch_cfg<128, 64, 2, 2, false, true>(p, batch, st) : launch_cfg<128, 64, 2, 2, false, false>(p, batch, st);
+      if (t == 64064) return vec ? launch_cfg<64, 64, 2, 2, false, true>(p, batch, st) : launch_cfg<64, 64, 2, 2, false, false>(p, batch, st);
+    }
+  } else if (c.family == FAM_PIPE) {
+    switch (c.arith) {
+      case AR_PAIRS:
+        if constexpr (!CONV) { if (t == 128128) return launch_pipe<128, 128, 2, 2, false, false, 2>(p, batch, st); }
+        break;
+      case AR_SPLIT:
+        if (t == 128128) return launch_pipe<128, 128, 2, 2, CONV, false, 1>(p, batch, st);
+        if (t == 128032) return launch_pipe<128, 32, 4, 1, CONV, false, 1>(p, batch, st);
+        if (t == 128064) return launch_pipe<128, 64, 2, 2, CONV, false, 1>(p, batch, st);
+        if (t == 64064) return launch_pipe<64, 64, 2, 2, CONV, false, 1>(p, batch, st);
+        break;
+      case AR_FP32_1BUF:
+        if (t == 128128) return launch_pipe<128, 128, 2, 2, CONV, false>(p, batch, st);
+        break;
+      case AR_FP32:
+        if (t == 128128) return launch_pipe<128, 128, 2, 2, CONV>(p, batch, st);
+        if (t == 128032) return launch_pipe<128, 32, 4, 1, CONV>(p, batch, st);
+        if (t == 128064) return launch_pipe<128, 64, 2, 2, CONV>(p, batch, st);
+        if (t == 64064) return launch_pipe<64, 64, 2, 2, CONV>(p, batch, st);
+        break;
+    }
+  }
+  return idiff::fail("igemm: no kernel for the plan (family %d, tile %d x %d, arithmetic %d)", c.family, c.bm, c.bn, c.arith);
+}
+
+// Rows per workgroup tile the pipelined kernel gets for (M, N, batch): the column sums' layout follows it.
+int pipe_tile_rows(int M, int N, int batch) {
+  IgemmParams p = {};
+  p.M = M; p.N = N;
+  idiff::set_epilogue(p, nullptr);
+  return igemm_choose(p, batch, WANT_PIPE).bm;
+}
+
+// The plan as text, for the route queries: "<family> <tile> <arithmetic> <epilogue form>".
+const char *igemm_plan_name(const IgemmPlan &c) {
+  static const char *const fam[] = {"pipe", "direct-vec", "direct-scalar", "narrow"};
+  static const char *const ar[] = {"fp32", "fp32-1buf", "split", "pairs"};
+  static const char *const epf[] = {"buf-block", "buf-row", "vec64", "scalar"};
+  static thread_local char text[64];
+  if (c.family == FAM_NARROW) snprintf(text, sizeof(text), "narrow c%d fp32 %s", c.bn, c.ep_form == 2 ? "elem" : c.ep_form == 1 ? "row" : "none");
+  else snprintf(text, sizeof(text), "%s %dx%d %s %s", fam[c.family], c.bm, c.bn, ar[c.arith], epf[c.ep_form]);
+  return text;
+}
+
+// choose, then report (a route query: `probe` receives the plan and nothing is launched) or launch
+template <bool CONV>
+int igemm_run(IgemmParams &p, int batch, int want, hipStream_t st, IgemmPlan *probe) {
+  const IgemmPlan c = igemm_choose(p, batch, want);
+  // the column sums are per whole row tile (idiff_gemm_colstats_split / idiff_conv2d_colstats_split answer 0 otherwise): the rows a
+  // partial last tile computes beyond M would be summed with the others
+  if (p.has_ep && p.ep.colstats && c.family == FAM_PIPE && p.M % c.bm)
+    return idiff::fail("%s: colstats with M = %d rows in tiles of %d: no whole tiles (ask idiff_%s_colstats_split first)", CONV ? "conv2d" : "gemm",
+                       p.M, c.bm, CONV ? "conv2d" : "gemm");
+  if (probe) { *probe = c; return 0; }
+  return igemm_launch<CONV>(c, p, batch, st);
 }
 
 // The fast kernel addresses an operand through one 32-bit-offset buffer descriptor (< 4 GiB).  Larger problems
@@ -991,12 +1068,14 @@ constexpr int64_t BUF_LIMIT = 0xFFFFFFF0ll;
 
 }  // namespace
 
-IDIFF_API int idiff_gemm_f32(const float *A, int64_t lda, int64_t strideA, const float *Bt, int64_t ldb,
-                             int64_t strideB, float *C, int64_t ldc, int64_t strideC, int M, int N, int K,
-                             int batch, const idiff_epilogue *ep, void *stream) {
+namespace {
+// idiff_gemm_f32, or -- `probe` -- its decisions alone: the plan of the launch it would make (of the first one when the rows are cut
+// in two), nothing launched
+int gemm_front(const float *A, int64_t lda, int64_t strideA, const float *Bt, int64_t ldb, int64_t strideB, float *C, int64_t ldc,
+               int64_t strideC, int M, int N, int K, int batch, const idiff_epilogue *ep, void *stream, IgemmPlan *probe) {
   using namespace idiff;
   if (M < 0 || N < 0 || K <= 0 || batch < 0) return fail("gemm: bad sizes M=%d N=%d K=%d batch=%d", M, N, K, batch);
-  if (M == 0 || N == 0 || batch == 0) return 0;
+  if (M == 0 || N == 0 || batch == 0) { if (probe) probe->family = -1; return 0; }
   if (!A || !Bt || !C) return fail("gemm: null pointer");
   if (lda < K || ldb < K || ldc < N) return fail("gemm: leading dimension smaller than the row length");
   if (batch > 65535) return fail("gemm: batch %d exceeds grid.y", batch);
@@ -1015,19 +1094,26 @@ IDIFF_API int idiff_gemm_f32(const float *A, int64_t lda, int64_t strideA, const
     if (mid > 0) {
       idiff_epilogue lo, hi;
       if (ep) { lo = *ep; hi = shift_epilogue(*ep, mid); }
-      int rc = idiff_gemm_f32(A, lda, 0, Bt, ldb, 0, C, ldc, 0, mid, N, K, 1, ep ? &lo : nullptr, stream);
-      if (rc) return rc;
-      return idiff_gemm_f32(A + (int64_t)mid * lda, lda, 0, Bt, ldb, 0, C + (int64_t)mid * ldc, ldc, 0, M - mid, N, K, 1,
-                            ep ? &hi : nullptr, stream);
+      int rc = gemm_front(A, lda, 0, Bt, ldb, 0, C, ldc, 0, mid, N, K, 1, ep ? &lo : nullptr, stream, probe);
+      if (rc || probe) return rc;
+      return gemm_front(A + (int64_t)mid * lda, lda, 0, Bt, ldb, 0, C + (int64_t)mid * ldc, ldc, 0, M - mid, N, K, 1,
+                        ep ? &hi : nullptr, stream, nullptr);
     }
   }
   if (vec && a_bytes < BUF_LIMIT && b_bytes < BUF_LIMIT && !idiff::option(idiff::OPT_NO_PIPE)) {
     p.a_bytes = (uint32_t)a_bytes; p.b_bytes = (uint32_t)b_bytes;
-    return dispatch_pipe<false>(p, batch, st);
+    return igemm_run<false>(p, batch, WANT_PIPE, st, probe);
   }
   if (ep && ep->colstats) return fail("gemm: colstats requested for a problem the pipelined kernel does not take "
                                       "(ask idiff_gemm_colstats_split first)");
-  return vec ? dispatch<false, true>(p, batch, st) : dispatch<false, false>(p, batch, st);
+  return igemm_run<false>(p, batch, vec ? WANT_DIRECT_VEC : WANT_DIRECT_SCALAR, st, probe);
+}
+}  // namespace
+
+IDIFF_API int idiff_gemm_f32(const float *A, int64_t lda, int64_t strideA, const float *Bt, int64_t ldb,
+                             int64_t strideB, float *C, int64_t ldc, int64_t strideC, int M, int N, int K,
+                             int batch, const idiff_epilogue *ep, void *stream) {
+  return gemm_front(A, lda, strideA, Bt, ldb, strideB, C, ldc, strideC, M, N, K, batch, ep, stream, nullptr);
 }
 
 namespace {
@@ -1071,12 +1157,14 @@ IDIFF_API int idiff_gemm_pairs_scale_f32(const float *Bt, int64_t ldb, int N, in
   return launch_status("gemm_pairs_scale");
 }
 
-IDIFF_API int idiff_gemm_pairs_f32(const float *A, int64_t lda, int64_t strideA, const float *Bt, int64_t ldb, int64_t strideB,
-                                   const float *w_scale, int weight_is_a, const float *act_scale, float *C, int64_t ldc, int64_t strideC,
-                                   int M, int N, int K, int batch, const idiff_epilogue *ep, void *stream) {
+namespace {
+// idiff_gemm_pairs_f32, or its decisions alone (`probe`, as gemm_front)
+int pairs_front(const float *A, int64_t lda, int64_t strideA, const float *Bt, int64_t ldb, int64_t strideB, const float *w_scale,
+                int weight_is_a, const float *act_scale, float *C, int64_t ldc, int64_t strideC, int M, int N, int K, int batch,
+                const idiff_epilogue *ep, void *stream, IgemmPlan *probe) {
   using namespace idiff;
   if (M < 0 || N < 0 || K <= 0 || batch < 0) return fail("gemm_pairs: bad sizes M=%d N=%d K=%d batch=%d", M, N, K, batch);
-  if (M == 0 || N == 0 || batch == 0) return 0;
+  if (M == 0 || N == 0 || batch == 0) { if (probe) probe->family = -1; return 0; }
   if (!A || !Bt || !C || !w_scale) return fail("gemm_pairs: null pointer");
   if (lda < K || ldb < K || ldc < N) return fail("gemm_pairs: leading dimension smaller than the row length");
   if (!pairs_geometry_ok(M, N, K, batch)) return fail("gemm_pairs: M=%d N=%d K=%d batch=%d not served (ask idiff_gemm_pairs_ok)", M, N, K, batch);
@@ -1092,7 +1180,27 @@ IDIFF_API int idiff_gemm_pairs_f32(const float *A, int64_t lda, int64_t strideA,
   p.a_bytes = (uint32_t)a_bytes; p.b_bytes = (uint32_t)b_bytes;
   p.scale_a = weight_is_a ? w_scale : act_scale; p.scale_b = weight_is_a ? act_scale : w_scale;
   idiff::set_epilogue(p, ep);
-  return launch_pipe<128, 128, 2, 2, false, false, 2>(p, batch, (hipStream_t)stream);
+  return igemm_run<false>(p, batch, WANT_PAIRS, (hipStream_t)stream, probe);
+}
+}  // namespace
+
+IDIFF_API int idiff_gemm_pairs_f32(const float *A, int64_t lda, int64_t strideA, const float *Bt, int64_t ldb, int64_t strideB,
+                                   const float *w_scale, int weight_is_a, const float *act_scale, float *C, int64_t ldc, int64_t strideC,
+                                   int M, int N, int K, int batch, const idiff_epilogue *ep, void *stream) {
+  return pairs_front(A, lda, strideA, Bt, ldb, strideB, w_scale, weight_is_a, act_scale, C, ldc, strideC, M, N, K, batch, ep, stream, nullptr);
+}
+
+IDIFF_API const char *idiff_gemm_route(const void *A, int64_t lda, int64_t strideA, const void *Bt, int64_t ldb, int64_t strideB,
+                                       const void *C, int64_t ldc, int64_t strideC, int M, int N, int K, int batch,
+                                       const idiff_epilogue *ep, int pairs) {
+  IgemmPlan c = {};
+  const float *a = (const float *)A, *bt = (const float *)Bt;
+  float *out = (float *)const_cast<void *>(C);
+  // (the pair form only asks of its scale that there is one)
+  const int rc = pairs ? pairs_front(a, lda, strideA, bt, ldb, strideB, bt, 0, nullptr, out, ldc, strideC, M, N, K, batch, ep, nullptr, &c)
+                       : gemm_front(a, lda, strideA, bt, ldb, strideB, out, ldc, strideC, M, N, K, batch, ep, nullptr, &c);
+  if (rc) return nullptr;
+  return c.family < 0 ? "none" : igemm_plan_name(c);
 }
 
 IDIFF_API int idiff_gemm_pairs_2src_f32(const float *A1, const float *A2, int64_t lda, int K1, const float *act_scale, const float *Bt,
@@ -1115,7 +1223,7 @@ IDIFF_API int idiff_gemm_pairs_2src_f32(const float *A1, const float *A2, int64_
   p.a_bytes = (uint32_t)a1_bytes; p.a2_bytes = (uint32_t)a2_bytes; p.b_bytes = (uint32_t)b_bytes;
   p.scale_a = act_scale; p.scale_b = w_scale;
   idiff::set_epilogue(p, ep);
-  return launch_pipe<128, 128, 2, 2, false, false, 2>(p, 1, (hipStream_t)stream);
+  return igemm_run<false>(p, 1, WANT_PAIRS, (hipStream_t)stream, nullptr);
 }
 
 namespace {
@@ -1200,17 +1308,18 @@ IDIFF_API int idiff_gemm_2src_f32(const float *A1, const float *A2, int64_t lda,
   p.A = A1; p.A2 = A2; p.K1 = K1; p.Bt = Bt; p.C = C; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
   p.a_bytes = (uint32_t)a1_bytes; p.a2_bytes = (uint32_t)a2_bytes; p.b_bytes = (uint32_t)b_bytes;
   idiff::set_epilogue(p, ep);
-  return dispatch_pipe<false>(p, 1, (hipStream_t)stream);
+  return igemm_run<false>(p, 1, WANT_PIPE, (hipStream_t)stream, nullptr);
 }
 
-IDIFF_API int idiff_conv2d_nhwc_f32(const float *x, const float *wt, float *out, int B, int H, int W, int Cin,
-                                    int Cout, int KH, int KW, int stride, int pad_lo, int pad_hi,
-                                    const idiff_epilogue *ep, void *stream) {
+namespace {
+// idiff_conv2d_nhwc_f32, or its decisions alone (`probe`, as gemm_front; of the first half when the batch is cut in two)
+int conv_front(const float *x, const float *wt, float *out, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad_lo,
+               int pad_hi, const idiff_epilogue *ep, void *stream, IgemmPlan *probe) {
   using namespace idiff;
   if (B < 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || stride <= 0 || pad_lo < 0 || pad_hi < 0)
     return fail("conv2d: bad geometry");
   if (Cin % 4 != 0) return fail("conv2d: Cin must be a multiple of 4 (pad the channels), got %d", Cin);
-  if (B == 0) return 0;
+  if (B == 0) { if (probe) probe->family = -1; return 0; }
   if (!x || !wt || !out) return fail("conv2d: null pointer");
   if (!aligned16(x) || !aligned16(wt)) return fail("conv2d: x and wt must be 16-byte aligned");
   const int OH = (H + pad_lo + pad_hi - KH) / stride + 1, OW = (W + pad_lo + pad_hi - KW) / stride + 1;
@@ -1219,8 +1328,14 @@ IDIFF_API int idiff_conv2d_nhwc_f32(const float *x, const float *wt, float *out,
   const int64_t M64 = (int64_t)B * OH * OW;
   if (M64 > 0x7fffffff) return fail("conv2d: B*OH*OW overflows int32");
   // the 128 -> 3 image heads: ten times fewer multiplications on the vector ALUs than padded to an MFMA column
-  if (conv3x3_narrow_ok(B, H, W, Cin, Cout, KH, KW, stride, pad_lo, pad_hi, ep))
+  if (conv3x3_narrow_ok(B, H, W, Cin, Cout, KH, KW, stride, pad_lo, pad_hi, ep)) {
+    if (probe) {   // the per-group scale is folded per image row where a group never ends inside one, else per element (conv3x3_narrow_kernel)
+      const int rpg = (ep && ep->rows_per_group > 0) ? ep->rows_per_group : 1;
+      *probe = IgemmPlan{FAM_NARROW, 0, Cout, AR_FP32, !(ep && ep->rowscale) ? 0 : rpg % W == 0 ? 1 : 2};
+      return 0;
+    }
     return conv3x3_narrow(x, wt, out, B, H, W, Cin, Cout, ep, (hipStream_t)stream);
+  }
   IgemmParams p = {};
   p.A = x; p.Bt = wt; p.C = out;
   p.M = (int)M64; p.N = Cout; p.K = KH * KW * Cin;
@@ -1240,17 +1355,33 @@ IDIFF_API int idiff_conv2d_nhwc_f32(const float *x, const float *wt, float *out,
     if (m_lo % rpg == 0) {
       idiff_epilogue lo, hi;
       if (ep) { lo = *ep; hi = shift_epilogue(*ep, m_lo); }
-      int rc = idiff_conv2d_nhwc_f32(x, wt, out, b_lo, H, W, Cin, Cout, KH, KW, stride, pad_lo, pad_hi, ep ? &lo : nullptr, stream);
-      if (rc) return rc;
-      return idiff_conv2d_nhwc_f32(x + (int64_t)b_lo * H * W * Cin, wt, out + m_lo * Cout, B - b_lo, H, W, Cin, Cout, KH, KW,
-                                   stride, pad_lo, pad_hi, ep ? &hi : nullptr, stream);
+      int rc = conv_front(x, wt, out, b_lo, H, W, Cin, Cout, KH, KW, stride, pad_lo, pad_hi, ep ? &lo : nullptr, stream, probe);
+      if (rc || probe) return rc;
+      return conv_front(x + (int64_t)b_lo * H * W * Cin, wt, out + m_lo * Cout, B - b_lo, H, W, Cin, Cout, KH, KW,
+                        stride, pad_lo, pad_hi, ep ? &hi : nullptr, stream, nullptr);
     }
   }
   if (fast_ok && a_bytes < BUF_LIMIT) {
     p.a_bytes = (uint32_t)a_bytes; p.b_bytes = (uint32_t)b_bytes;
-    return dispatch_pipe<true>(p, 1, (hipStream_t)stream);
+    return igemm_run<true>(p, 1, WANT_PIPE, (hipStream_t)stream, probe);
   }
-  return dispatch<true, true>(p, 1, (hipStream_t)stream);
+  return igemm_run<true>(p, 1, WANT_DIRECT_VEC, (hipStream_t)stream, probe);
+}
+}  // namespace
+
+IDIFF_API int idiff_conv2d_nhwc_f32(const float *x, const float *wt, float *out, int B, int H, int W, int Cin,
+                                    int Cout, int KH, int KW, int stride, int pad_lo, int pad_hi,
+                                    const idiff_epilogue *ep, void *stream) {
+  return conv_front(x, wt, out, B, H, W, Cin, Cout, KH, KW, stride, pad_lo, pad_hi, ep, stream, nullptr);
+}
+
+IDIFF_API const char *idiff_conv2d_route(const void *x, const void *wt, const void *out, int B, int H, int W, int Cin, int Cout, int KH,
+                                         int KW, int stride, int pad_lo, int pad_hi, const idiff_epilogue *ep) {
+  IgemmPlan c = {};
+  if (conv_front((const float *)x, (const float *)wt, (float *)const_cast<void *>(out), B, H, W, Cin, Cout, KH, KW, stride, pad_lo, pad_hi, ep,
+                 nullptr, &c))
+    return nullptr;
+  return c.family < 0 ? "none" : igemm_plan_name(c);
 }
 
 

@@ -102,13 +102,18 @@ int pair_bank_pack(const char *name, const float *wt, float *u, int Cin, int Cou
 }
 
 // ---------------------------------------------------------------- validation of a convolution call (after the form's own geometry check)
-// what every form asks of its operands: no null pointer, 16-byte alignment, a residual the tail can read 16 bytes at a time
+// what every form asks of its operands: no null pointer, 16-byte alignment, a residual, bias and per-group bias the tail can read 16 bytes
+// at a time
 inline int wino_check_operands(const char *name, const float *x, const float *u, const float *out, const idiff_epilogue *ep, int Cout) {
   using namespace idiff;
   if (!x || !u || !out) return fail("%s: null pointer", name);
   if (((uintptr_t)x & 15) || ((uintptr_t)u & 15) || ((uintptr_t)out & 15)) return fail("%s: x, u and out must be 16-byte aligned", name);
   if (ep && ep->residual && (((uintptr_t)ep->residual & 15) || ep->ld_residual % 4 || ep->ld_residual < Cout || ep->ld_residual > 0x7fffffff / 4))
     return fail("%s: residual must be 16-byte aligned with a row pitch >= Cout that is a multiple of 4", name);
+  // every tail reads bias and the per-group bias four channels at a time; there is no scalar form to fall back to
+  if (ep && ep->bias && ((uintptr_t)ep->bias & 15)) return fail("%s: bias must be 16-byte aligned", name);
+  if (ep && ep->rowbias && (((uintptr_t)ep->rowbias & 15) || ep->ld_rowbias % 4))
+    return fail("%s: rowbias must be 16-byte aligned with a row pitch that is a multiple of 4", name);
   return 0;
 }
 

@@ -210,6 +210,26 @@ int idiff_gemm_2src_f32(const float *A1, const float *A2, int64_t lda, int K1, c
 int idiff_conv2d_nhwc_f32(const float *x, const float *wt, float *out, int B, int H, int W, int Cin, int Cout,
                           int KH, int KW, int stride, int pad_lo, int pad_hi, const idiff_epilogue *ep, void *stream);
 
+/* Which kernel and which form of its tail idiff_gemm_f32 (pairs = 0) / idiff_gemm_pairs_f32 (pairs != 0) / idiff_conv2d_nhwc_f32 would
+ * launch for these arguments: the launchers and these queries call the same chooser (csrc/igemm.hip: igemm_choose) under the same thread
+ * options; pointers are only inspected for null and for 16-byte alignment.  "<family> <tile> <arithmetic> <epilogue form>":
+ *   family     "pipe" (pipelined, buffer-addressed operands), "direct-vec" / "direct-scalar" (the general kernel with 16-byte / 4-byte
+ *              operand loads), "narrow" (conv3x3 to <= 4 channels on the vector ALUs; tile "c<Cout>")
+ *   tile       rows x columns of a workgroup: "128x128", "128x64", "128x32", "64x64"
+ *   arithmetic "split" (three bf16 pieces, six products), "fp32", "fp32-1buf" (fp32, single LDS buffer), "pairs" (fp16 pairs)
+ *   epilogue   "buf-block" (C and residual through buffer descriptors, group terms folded per 32-row block: rows_per_group % 32 == 0),
+ *              "buf-row" (the same with the group terms per row), "vec64" (16-byte accesses through 64-bit addresses: C or the residual
+ *              beyond 0xE0000000 bytes, or a tile's rows spanning 0x0FFFFFF0 bytes), "scalar" (one element at a time: an operand of the
+ *              tail that is not 16-byte aligned, N / ldc / a pitch not a multiple of 4, IDIFF_SCALAR_EPILOGUE; always for "direct-*");
+ *              "narrow": "row" / "elem" (rowscale folded per image row / applied per element) or "none" (no rowscale)
+ * idiff_gemm_2src_f32 / idiff_gemm_pairs_2src_f32 take the route of the one-source call with A = A1.  A problem cut in two on the host
+ * (an operand beyond 4 GiB) reports its first half.  "none" when there is nothing to launch (an empty problem), NULL for arguments the
+ * launcher refuses (idiff_last_error says why).  Launches nothing; no reference counterpart. */
+const char *idiff_gemm_route(const void *A, int64_t lda, int64_t strideA, const void *Bt, int64_t ldb, int64_t strideB, const void *C,
+                             int64_t ldc, int64_t strideC, int M, int N, int K, int batch, const idiff_epilogue *ep, int pairs);
+const char *idiff_conv2d_route(const void *x, const void *wt, const void *out, int B, int H, int W, int Cin, int Cout, int KH, int KW,
+                               int stride, int pad_lo, int pad_hi, const idiff_epilogue *ep);
+
 /* Fused GroupNorm statistics: when `rows_per_sample` consecutive output rows form one sample, these return the number of
  * workgroup row-tiles per sample (`nsplit`: epilogue.colstats is then laid out [samples, nsplit, N, 2]) or 0 when the
  * fused statistics are unavailable for the problem (general kernel, operands beyond 4 GiB, tiles straddling samples). */

@@ -147,6 +147,10 @@ def _refusal_cases():
         conv("misaligned_x", x=_X + 4); conv("misaligned_u", u=_U + 8); conv("misaligned_out", out=_OUT + 4)
         conv("geometry", H=7 if entry == "winograd" else 6)
         conv("zero_batch", B=0)
+        # bias and the per-group bias are read 16 bytes at a time by every tail
+        conv("misaligned_bias", ep=dict(bias=_ROWB + 4))
+        conv("misaligned_rowbias", ep=dict(rowbias=_ROWB + 8, ld_rowbias=_COUT, rows_per_group=_H * _W))
+        conv("rowbias_pitch_not_4", ep=dict(rowbias=_ROWB, ld_rowbias=_COUT + 2, rows_per_group=_H * _W))
         if entry == "wino1d_gn":          # a residual, or a row group that is not the image, breaks a second condition of the fused GroupNorm
             continue
         conv("misaligned_residual", ep=dict(residual=_RES + 4, ld_residual=_COUT))
@@ -175,6 +179,7 @@ def _call_refusal(handle, symbol, args):
 
 
 # Return code and idiff_last_error() of every case, recorded from the library of the commit before the launchers' host code was merged.
+# (The bias / rowbias cases at the end of the table came later, with the checks they pin.)
 # conv2d_winograd reported a bad residual in two texts of its own; it now says what the other three entries say, and for its four residual
 # cases the words its old text has in common with theirs are what is pinned (_UNIFIED; the old text stands above each).
 _REFUSALS = {
@@ -254,6 +259,22 @@ _REFUSALS = {
     'wino1d_pack-null_wt': (1001, 'wino1d_pack: null pointer'),
     'wino1d_pack-null_u': (1001, 'wino1d_pack: null pointer'),
     'wino1d_pack-misaligned_u': (1001, 'wino1d_pack: u must be 16-byte aligned'),
+    # since the Winograd front end checks what its tails read 16 bytes at a time beside the residual
+    'winograd-misaligned_bias': (1001, 'conv2d_winograd: bias must be 16-byte aligned'),
+    'winograd-misaligned_rowbias': (1001, 'conv2d_winograd: rowbias must be 16-byte aligned with a row pitch that is a multiple of 4'),
+    'winograd-rowbias_pitch_not_4': (1001, 'conv2d_winograd: rowbias must be 16-byte aligned with a row pitch that is a multiple of 4'),
+    'winograd43-misaligned_bias': (1001, 'conv2d_winograd43: bias must be 16-byte aligned'),
+    'winograd43-misaligned_rowbias': (1001, 'conv2d_winograd43: rowbias must be 16-byte aligned with a row pitch that is a multiple of 4'),
+    'winograd43-rowbias_pitch_not_4': (1001, 'conv2d_winograd43: rowbias must be 16-byte aligned with a row pitch that is a multiple of 4'),
+    'winograd43h-misaligned_bias': (1001, 'conv2d_winograd43h: bias must be 16-byte aligned'),
+    'winograd43h-misaligned_rowbias': (1001, 'conv2d_winograd43h: rowbias must be 16-byte aligned with a row pitch that is a multiple of 4'),
+    'winograd43h-rowbias_pitch_not_4': (1001, 'conv2d_winograd43h: rowbias must be 16-byte aligned with a row pitch that is a multiple of 4'),
+    'wino1d-misaligned_bias': (1001, 'conv2d_wino1d: bias must be 16-byte aligned'),
+    'wino1d-misaligned_rowbias': (1001, 'conv2d_wino1d: rowbias must be 16-byte aligned with a row pitch that is a multiple of 4'),
+    'wino1d-rowbias_pitch_not_4': (1001, 'conv2d_wino1d: rowbias must be 16-byte aligned with a row pitch that is a multiple of 4'),
+    'wino1d_gn-misaligned_bias': (1001, 'conv2d_wino1d: bias must be 16-byte aligned'),
+    'wino1d_gn-misaligned_rowbias': (1001, 'conv2d_wino1d: rowbias must be 16-byte aligned with a row pitch that is a multiple of 4'),
+    'wino1d_gn-rowbias_pitch_not_4': (1001, 'conv2d_wino1d: rowbias must be 16-byte aligned with a row pitch that is a multiple of 4'),
 }
 _UNIFIED = ("winograd-misaligned_residual", "winograd-residual_pitch_not_4", "winograd-residual_pitch_below_cout",
             "winograd-residual_pitch_above_int")

@@ -518,3 +518,101 @@ def test_conv3x3_route_table(switch, net, B, normed, per_image):
     with _lib.thread_option(switch, 1) if switch else contextlib.nullcontext():
         got = tuple(getattr(nhwc.conv3x3_route(B, *s, normed, per_image), "name", "igemm") for s in shapes)
     assert got == _ROUTES[(switch, net, B, normed, per_image)]
+
+
+# ---- the implicit GEMM's chooser (csrc/igemm.hip: igemm_choose), asked through the route queries that launch nothing
+_P = 0x10000          # fabricated, 16-byte aligned: the queries inspect pointers for null and alignment only
+_IGEMM_ROUTES = [
+    # (switches, "gemm" | "pairs" | "conv", geometry, epilogue fields, route; None = refused)
+    ((), "gemm", dict(M=300, N=72, K=64), None, "pipe 64x64 split buf-row"),                     # no epilogue: one row per group
+    ((), "gemm", dict(M=300, N=72, K=64), dict(rowscale=_P, rows_per_group=64), "pipe 64x64 split buf-block"),
+    ((), "gemm", dict(M=300, N=72, K=64), dict(rowscale=_P, rows_per_group=100), "pipe 64x64 split buf-row"),
+    ((), "gemm", dict(M=300, N=72, K=64), dict(bias=_P + 4), "pipe 64x64 split scalar"),
+    ((), "gemm", dict(M=300, N=72, K=64), dict(rowbias=_P, ld_rowbias=74), "pipe 64x64 split scalar"),
+    ((), "gemm", dict(M=300, N=72, K=64), dict(residual=_P, ld_residual=74), "pipe 64x64 split scalar"),
+    ((), "gemm", dict(M=300, N=72, K=64, C=_P + 8), None, "pipe 64x64 split scalar"),
+    ((), "gemm", dict(M=300, N=72, K=64, ldc=74), None, "pipe 64x64 split scalar"),
+    ((), "gemm", dict(M=300, N=65, K=64), None, "pipe 64x64 split scalar"),
+    (("IDIFF_SCALAR_EPILOGUE",), "gemm", dict(M=300, N=72, K=64), None, "pipe 64x64 split scalar"),
+    ((), "gemm", dict(M=300, N=72, K=101), None, "direct-scalar 64x64 fp32 scalar"),
+    ((), "gemm", dict(M=300, N=72, K=64, A=_P + 4), None, "direct-scalar 64x64 fp32 scalar"),
+    (("IDIFF_NO_PIPE",), "gemm", dict(M=300, N=72, K=64), None, "direct-vec 64x64 fp32 scalar"),
+    (("IDIFF_NO_SPLIT",), "gemm", dict(M=300, N=72, K=64), None, "pipe 64x64 fp32 buf-row"),
+    # a tile's rows span 0x0FFFFFF0 bytes: 64-bit addresses (64 rows at ldc = 2^20; one row less of pitch stays on descriptors)
+    ((), "gemm", dict(M=70, N=64, K=64, ldc=1 << 20), None, "pipe 64x64 split vec64"),
+    ((), "gemm", dict(M=70, N=64, K=64, ldc=(1 << 20) - 4), None, "pipe 64x64 split buf-row"),
+    ((), "gemm", dict(M=70, N=64, K=64), dict(residual=_P, ld_residual=1 << 20), "pipe 64x64 split vec64"),
+    ((), "gemm", dict(M=4096, N=64, K=64, ldc=1 << 19), None, "pipe 128x64 split vec64"),       # 128-row tiles: half the pitch
+    ((), "gemm", dict(M=940000, N=1024, K=64), None, "pipe 128x128 split vec64"),                # C beyond 0xE0000000 bytes
+    ((), "gemm", dict(M=900000, N=1024, K=64), None, "pipe 128x128 split buf-row"),
+    # tiles
+    ((), "gemm", dict(M=4096, N=64, K=64), None, "pipe 128x64 split buf-row"),
+    ((), "gemm", dict(M=4095, N=64, K=64), None, "pipe 64x64 split buf-row"),
+    ((), "gemm", dict(M=4096, N=32, K=64), None, "pipe 128x32 split buf-row"),
+    ((), "gemm", dict(M=128 * 128, N=256, K=64), None, "pipe 128x128 split buf-row"),            # 256 tiles of 128 x 128
+    ((), "gemm", dict(M=128 * 127, N=256, K=64), None, "pipe 128x64 split buf-row"),
+    ((), "gemm", dict(M=128, N=65, K=64, batch=256), None, "pipe 128x128 split scalar"),
+    (("IDIFF_NO_SPLIT",), "gemm", dict(M=128 * 128, N=256, K=64), None, "pipe 128x128 fp32 buf-row"),
+    (("IDIFF_NO_SPLIT",), "gemm", dict(M=128 * 512, N=256, K=64), None, "pipe 128x128 fp32-1buf buf-row"),
+    (("IDIFF_NO_SPLIT", "IDIFF_DBUF_ONLY"), "gemm", dict(M=128 * 512, N=256, K=64), None, "pipe 128x128 fp32 buf-row"),
+    (("IDIFF_NO_SPLIT",), "gemm", dict(M=4096, N=32, K=64), None, "pipe 128x32 fp32 buf-row"),
+    (("IDIFF_NO_PIPE",), "gemm", dict(M=128 * 128, N=256, K=64), None, "direct-vec 128x128 fp32 scalar"),
+    (("IDIFF_NO_PIPE",), "gemm", dict(M=4096, N=64, K=64), None, "direct-vec 128x64 fp32 scalar"),
+    # fp16 pairs: one tile, the same tails
+    ((), "pairs", dict(M=300, N=128, K=64), None, None),                                        # not served below 256 tiles
+    (("IDIFF_PAIRS_MIN_TILES",), "pairs", dict(M=300, N=128, K=64), dict(rowscale=_P, rows_per_group=100), "pipe 128x128 pairs buf-row"),
+    (("IDIFF_PAIRS_MIN_TILES",), "pairs", dict(M=300, N=128, K=64), dict(rowscale=_P, rows_per_group=128), "pipe 128x128 pairs buf-block"),
+    (("IDIFF_PAIRS_MIN_TILES",), "pairs", dict(M=300, N=128, K=64, ldc=1 << 20), None, "pipe 128x128 pairs vec64"),
+    # nothing to launch, and what the launcher refuses
+    ((), "gemm", dict(M=0, N=72, K=64), None, "none"),
+    ((), "gemm", dict(M=300, N=72, K=64, A=0), None, None),
+    ((), "gemm", dict(M=300, N=72, K=64, ldc=64), None, None),
+    ((), "gemm", dict(M=300, N=72, K=64), dict(colstats=_P, rows_per_group=100), None),          # 300 rows: no whole tiles of 64
+    ((), "gemm", dict(M=256, N=64, K=64), dict(colstats=_P, rows_per_group=64), "pipe 64x64 split buf-block"),
+    ((), "gemm", dict(M=256, N=64, K=101), dict(colstats=_P, rows_per_group=64), None),          # the general kernel has no column sums
+    # convolutions: (B, H, W, Cin, Cout, k, stride, pad_lo, pad_hi)
+    ((), "conv", (3, 8, 8, 32, 64, 3, 1, 1, 1), dict(rowscale=_P, rows_per_group=64), "pipe 64x64 split buf-block"),
+    ((), "conv", (5, 4, 4, 64, 32, 1, 1, 0, 0), dict(rowscale=_P, rows_per_group=16), "pipe 64x64 split buf-row"),
+    ((), "conv", (2, 9, 7, 8, 12, 3, 2, 0, 1), None, "direct-vec 64x64 fp32 scalar"),           # Cin % 32: the general kernel
+    ((), "conv", (2, 32, 32, 4, 128, 3, 1, 1, 1), None, "pipe 64x64 split buf-row"),            # the 4-channel stem
+    (("IDIFF_NO_PIPE",), "conv", (3, 8, 8, 32, 64, 3, 1, 1, 1), None, "direct-vec 64x64 fp32 scalar"),
+    ((), "conv", (64, 32, 32, 128, 128, 3, 1, 1, 1), None, "pipe 128x128 split buf-row"),
+    ((), "conv", (2, 5, 28, 128, 3, 3, 1, 1, 1), None, "narrow c3 fp32 none"),
+    ((), "conv", (2, 5, 28, 128, 3, 3, 1, 1, 1), dict(rowscale=_P, rows_per_group=140), "narrow c3 fp32 row"),
+    ((), "conv", (2, 5, 28, 128, 3, 3, 1, 1, 1), dict(rowscale=_P, rows_per_group=35), "narrow c3 fp32 elem"),
+    ((), "conv", (2, 5, 28, 128, 3, 3, 1, 1, 1), dict(rowbias=_P, ld_rowbias=4, rows_per_group=140), "pipe 64x64 split scalar"),
+    ((), "conv", (2, 5, 28, 128, 3, 3, 1, 1, 1), dict(residual=_P, ld_residual=4), "pipe 64x64 split scalar"),
+    (("IDIFF_NO_PIPE",), "conv", (2, 5, 28, 128, 3, 3, 1, 1, 1), None, "direct-vec 64x64 fp32 scalar"),
+    ((), "conv", (2, 32, 32, 128, 5, 3, 1, 1, 1), None, "pipe 64x64 split scalar"),             # five channels: not the narrow head
+    ((), "conv", (0, 8, 8, 32, 64, 3, 1, 1, 1), None, "none"),
+    ((), "conv", (3, 8, 8, 30, 64, 3, 1, 1, 1), None, None),                                    # Cin % 4
+    ((), "conv", (5, 4, 4, 64, 32, 1, 1, 0, 0), dict(colstats=_P, rows_per_group=16), None),     # 80 rows: no whole tiles of 64
+]
+
+
+@pytest.mark.parametrize("switches,kind,geom,ep,want", _IGEMM_ROUTES, ids=lambda v: str(v) if not isinstance(v, (dict, tuple)) else None)
+def test_igemm_route_table(switches, kind, geom, ep, want):
+    """Family, tile, arithmetic and tail form of idiff_gemm_f32 / idiff_gemm_pairs_f32 / idiff_conv2d_nhwc_f32 by sizes, pitches, pointer
+    alignment, epilogue and switches: the launchers call the chooser these queries call, so the table pins what they launch -- without a
+    GPU.  The thresholds: 256 / 1024 workgroups and M >= 4096 for the tiles; N, ldc and the tail operands' pitches % 4 and 16-byte
+    alignment for the 16-byte tail; 0xE0000000 bytes of C or residual and 0x0FFFFFF0 bytes per tile for the descriptor-addressed one;
+    rows_per_group % 32 for the block-folded group terms."""
+    import contextlib
+    import os
+    from id_diff_amd import _lib
+    if not os.path.exists(_lib.library_path()):
+        pytest.skip("libidiff_hip.so is not built")
+    e = None if ep is None else _lib.Epilogue(**dict(dict(rows_per_group=1, out_scale=1.0), **ep))
+    with contextlib.ExitStack() as stack:
+        for s in switches:
+            stack.enter_context(_lib.thread_option(s, 1))
+        if kind == "conv":
+            B, H, W, Cin, Cout, k, stride, lo, hi = geom
+            got = _lib.conv2d_route(_P, _P, _P, B, H, W, Cin, Cout, k, k, stride, lo, epilogue=e, pad_hi=hi)
+        else:
+            g = dict(geom)
+            M, N, K = g.pop("M"), g.pop("N"), g.pop("K")
+            got = _lib.gemm_route(g.pop("A", _P), _P, g.pop("C", _P), M, N, K, K, K, g.pop("ldc", N), epilogue=e, batch=g.pop("batch", 1),
+                                  stride_a=M * K, stride_b=N * K, stride_c=M * N, pairs=kind == "pairs")
+            assert not g
+    assert got == want
