@@ -61,6 +61,34 @@ template <class P> inline void set_epilogue(P &p, const idiff_epilogue *ep) {
   if (p.ep.rows_per_group <= 0) p.ep.rows_per_group = 1;
 }
 
+// ---- the host cut.  The fast kernels address an operand through one 32-bit-offset buffer descriptor (< 4 GiB).  Rows are independent,
+// so a larger problem runs as two row ranges (igemm.hip: matrices and NHWC convolutions; winograd.hip), each cut again if it must be.
+// The epilogue of the range that starts at row m0, which must be a multiple of rows_per_group:
+inline idiff_epilogue shift_epilogue(const idiff_epilogue &ep, int64_t m0) {
+  idiff_epilogue e = ep;
+  const int64_t g0 = m0 / (ep.rows_per_group > 0 ? ep.rows_per_group : 1);
+  if (e.rowbias) e.rowbias += g0 * ep.ld_rowbias;
+  if (e.residual) e.residual += m0 * ep.ld_residual;
+  if (e.rowscale) e.rowscale += g0;
+  return e;
+}
+// The row to cut `units` units of `unit_rows` rows at (a matrix: rows of 1; a convolution: images of OH * OW), or 0: there is none, and
+// the caller falls back or refuses.  Matrices are cut at the last whole row group below the middle, images after the middle one or not
+// at all.
+inline int64_t host_cut_row(int64_t units, int64_t unit_rows, const idiff_epilogue *ep) {
+  const int64_t rpg = (ep && ep->rows_per_group > 0) ? ep->rows_per_group : 1;
+  const int64_t half = units / 2 * unit_rows;
+  return unit_rows == 1 ? half / rpg * rpg : half % rpg ? 0 : half;
+}
+// run(r0, r1, ep) for the rows [0, cut) and [cut, rows), each with its epilogue (first_only: a route query, which reports the first range)
+template <class Run> inline int run_cut(int64_t rows, int64_t cut, const idiff_epilogue *ep, bool first_only, Run run) {
+  if (int rc = run((int64_t)0, cut, ep)) return rc;
+  if (first_only) return 0;
+  idiff_epilogue hi;
+  if (ep) hi = shift_epilogue(*ep, cut);
+  return run(cut, rows, ep ? &hi : nullptr);
+}
+
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

@@ -928,17 +928,23 @@ struct IgemmPlan { int family, bm, bn, arith, ep_form; };
 // on fp16 pairs (one tile), or the general kernel with / without 16-byte operand loads
 enum IgemmWant { WANT_PIPE, WANT_PAIRS, WANT_DIRECT_VEC, WANT_DIRECT_SCALAR };
 
-IgemmPlan igemm_choose(IgemmParams &p, int batch, int want) {
+// The fast kernel addresses an operand through one 32-bit-offset buffer descriptor: an extent is the bytes from the first element of
+// `rows` rows of `row_len` floats, `ld` apart, to the end of the last one, and must stay below BUF_LIMIT.
+constexpr int64_t BUF_LIMIT = 0xFFFFFFF0ll;
+int64_t extent_bytes(int64_t rows, int64_t ld, int64_t row_len) { return ((rows - 1) * ld + row_len) * 4; }
+
+// the tile and the arithmetic, by size and switches alone (ep_form: that of the general kernel's one tail)
+IgemmPlan igemm_tile(int M, int N, int batch, int want) {
   IgemmPlan c = {};
-  const int64_t wg_big = (int64_t)idiff::ceil_div(p.M, 128) * idiff::ceil_div(p.N, 128) * batch;
-  const int64_t wg_mid = (int64_t)idiff::ceil_div(p.M, 128) * idiff::ceil_div(p.N, 64) * batch;
+  const int64_t wg_big = (int64_t)idiff::ceil_div(M, 128) * idiff::ceil_div(N, 128) * batch;
+  const int64_t wg_mid = (int64_t)idiff::ceil_div(M, 128) * idiff::ceil_div(N, 64) * batch;
   auto tile = [&](int bm, int bn, int arith) { c.bm = bm; c.bn = bn; c.arith = arith; };
+  c.ep_form = EPF_SCALAR;
   if (want == WANT_DIRECT_VEC || want == WANT_DIRECT_SCALAR) {
     // Pick the largest tile that still yields >= ~2 workgroups per CU pair; small problems get small tiles.
     c.family = want == WANT_DIRECT_VEC ? FAM_DIRECT_VEC : FAM_DIRECT_SCALAR;
-    c.ep_form = EPF_SCALAR;                          // igemm_kernel has the one tail
-    if (p.N > 64 && wg_big >= 256) tile(128, 128, AR_FP32);
-    else if (wg_mid >= 256 || p.M >= 4096) tile(128, 64, AR_FP32);
+    if (N > 64 && wg_big >= 256) tile(128, 128, AR_FP32);
+    else if (wg_mid >= 256 || M >= 4096) tile(128, 64, AR_FP32);
     else tile(64, 64, AR_FP32);
     return c;
   }
@@ -950,19 +956,26 @@ IgemmPlan igemm_choose(IgemmParams &p, int batch, int want) {
     // the matrix instructions of tile t by sched_group_barrier was built and measured: 118-128 TFLOP/s against 140-180 for
     // this one -- at 32 k per tile a 128 x 128 workgroup asks the L2 for 32 KB per 1600 matrix-pipe cycles, which is what
     // bounds it, not the instruction mix.)
-    if (p.N > 64 && wg_big >= 256) tile(128, 128, AR_SPLIT);
-    else if (p.N <= 32 && p.M >= 4096) tile(128, 32, AR_SPLIT);
-    else if (wg_mid >= 256 || p.M >= 4096) tile(128, 64, AR_SPLIT);
+    if (N > 64 && wg_big >= 256) tile(128, 128, AR_SPLIT);
+    else if (N <= 32 && M >= 4096) tile(128, 32, AR_SPLIT);
+    else if (wg_mid >= 256 || M >= 4096) tile(128, 64, AR_SPLIT);
     else tile(64, 64, AR_SPLIT);
   }
   // >= 4 workgroups per CU available: single LDS buffer, 128 registers, four resident workgroups per CU
   // (measured 135-142 TFLOP/s vs 124-135 for the double-buffered two-workgroup form)
-  else if (p.N > 64 && wg_big >= 1024 && !idiff::option(idiff::OPT_DBUF_ONLY)) tile(128, 128, AR_FP32_1BUF);
-  else if (p.N > 64 && wg_big >= 256) tile(128, 128, AR_FP32);
+  else if (N > 64 && wg_big >= 1024 && !idiff::option(idiff::OPT_DBUF_ONLY)) tile(128, 128, AR_FP32_1BUF);
+  else if (N > 64 && wg_big >= 256) tile(128, 128, AR_FP32);
   // narrow outputs (the 3-channel image conv at the end of the U-Nets): one 32-wide MFMA column instead of two
-  else if (p.N <= 32 && p.M >= 4096) tile(128, 32, AR_FP32);
-  else if (wg_mid >= 256 || p.M >= 4096) tile(128, 64, AR_FP32);
+  else if (N <= 32 && M >= 4096) tile(128, 32, AR_FP32);
+  else if (wg_mid >= 256 || M >= 4096) tile(128, 64, AR_FP32);
   else tile(64, 64, AR_FP32);
+  return c;
+}
+
+// the tile, and for the pipelined kernel the form of its tail with the fields of `p` that go with it (vec_ep, buf_ep, c_bytes, res_bytes)
+IgemmPlan igemm_choose(IgemmParams &p, int batch, int want) {
+  IgemmPlan c = igemm_tile(p.M, p.N, batch, want);
+  if (c.family != FAM_PIPE) return c;
   // the tail: 16-byte accesses when every operand it touches allows them, else one element at a time
   const idiff_epilogue &e = p.ep;
   const bool al = (p.N % 4 == 0) && (p.ldc % 4 == 0) && (p.strideC % 4 == 0) && aligned16(p.C) &&
@@ -971,8 +984,8 @@ IgemmPlan igemm_choose(IgemmParams &p, int batch, int want) {
   p.vec_ep = al && !idiff::option(idiff::OPT_SCALAR_EPILOGUE);
   // 32-bit addressing of C and the residual (igemm_pipe_kernel's first epilogue form): extents below 0xE0000000 so that
   // an out-of-range start stays out of range after the row steps of one tile are added
-  const int64_t c_bytes = ((int64_t)(p.M - 1) * p.ldc + p.N) * 4;
-  const int64_t res_bytes = (p.has_ep && e.residual) ? ((int64_t)(p.M - 1) * e.ld_residual + p.N) * 4 : 0;
+  const int64_t c_bytes = extent_bytes(p.M, p.ldc, p.N);
+  const int64_t res_bytes = (p.has_ep && e.residual) ? extent_bytes(p.M, e.ld_residual, p.N) : 0;
   const int64_t pitch = p.ldc > e.ld_residual ? p.ldc : e.ld_residual;
   p.buf_ep = p.vec_ep && c_bytes < 0xE0000000ll && res_bytes < 0xE0000000ll && (int64_t)c.bm * pitch * 4 < 0x0FFFFFF0ll;
   p.c_bytes = p.buf_ep ? (uint32_t)c_bytes : 0; p.res_bytes = p.buf_ep ? (uint32_t)res_bytes : 0;
@@ -1021,14 +1034,6 @@ int igemm_launch(const IgemmPlan &c, IgemmParams &p, int batch, hipStream_t st) 
   return idiff::fail("igemm: no kernel for the plan (family %d, tile %d x %d, arithmetic %d)", c.family, c.bm, c.bn, c.arith);
 }
 
-// Rows per workgroup tile the pipelined kernel gets for (M, N, batch): the column sums' layout follows it.
-int pipe_tile_rows(int M, int N, int batch) {
-  IgemmParams p = {};
-  p.M = M; p.N = N;
-  idiff::set_epilogue(p, nullptr);
-  return igemm_choose(p, batch, WANT_PIPE).bm;
-}
-
 // The plan as text, for the route queries: "<family> <tile> <arithmetic> <epilogue form>".
 const char *igemm_plan_name(const IgemmPlan &c) {
   static const char *const fam[] = {"pipe", "direct-vec", "direct-scalar", "narrow"};
@@ -1053,70 +1058,33 @@ int igemm_run(IgemmParams &p, int batch, int want, hipStream_t st, IgemmPlan *pr
   return igemm_launch<CONV>(c, p, batch, st);
 }
 
-// The fast kernel addresses an operand through one 32-bit-offset buffer descriptor (< 4 GiB).  Larger problems
-// are cut into row ranges on the host (rows are independent): this returns the epilogue of the range that
-// starts at row m0, which must be a multiple of rows_per_group.
-idiff_epilogue shift_epilogue(const idiff_epilogue &ep, int64_t m0) {
-  idiff_epilogue e = ep;
-  const int64_t g0 = m0 / (ep.rows_per_group > 0 ? ep.rows_per_group : 1);
-  if (e.rowbias) e.rowbias += g0 * ep.ld_rowbias;
-  if (e.residual) e.residual += m0 * ep.ld_residual;
-  if (e.rowscale) e.rowscale += g0;
-  return e;
+// ---- "the pipelined kernel takes this shape", one statement per family.  The front ends below add pointer alignment and batch strides;
+// the colstats queries at the end of the file, which decide whether the executor allocates column sums at all, ask nothing else.
+enum PipeServes { PIPE_NO, PIPE_YES, PIPE_A_BEYOND };   // the last: only A exceeds one buffer descriptor -- what the host cut is for
+bool pitches16(int K, int64_t lda, int64_t ldb) { return K % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0; }   // every row starts a 16-byte load
+// K1: the split column of two sources with one pitch, which extend as far as their K1 and K - K1 columns
+int pipe_fits_linear(int M, int N, int K, int64_t lda, int64_t ldb, int K1 = 0) {
+  if (!pitches16(K, lda, ldb) || extent_bytes(N, ldb, K) >= BUF_LIMIT) return PIPE_NO;
+  return extent_bytes(M, lda, K1 > K - K1 ? K1 : K - K1) < BUF_LIMIT ? PIPE_YES : PIPE_A_BEYOND;
 }
-constexpr int64_t BUF_LIMIT = 0xFFFFFFF0ll;
+int pipe_serves_linear(int M, int N, int K, int64_t lda, int64_t ldb, int K1 = 0) {
+  return idiff::option(idiff::OPT_NO_PIPE) ? PIPE_NO : pipe_fits_linear(M, N, K, lda, ldb, K1);
+}
+int pipe_serves_conv(int B, int H, int W, int Cin, int Cout, int KH, int KW) {
+  const int64_t K = (int64_t)KH * KW * Cin;
+  if ((Cin % BK && Cin != 4) || KH * KW > 32 || idiff::option(idiff::OPT_NO_PIPE) || extent_bytes(Cout, K, K) >= BUF_LIMIT) return PIPE_NO;
+  return extent_bytes((int64_t)B * H * W, Cin, Cin) < BUF_LIMIT ? PIPE_YES : PIPE_A_BEYOND;
+}
 
-}  // namespace
-
-namespace {
-// idiff_gemm_f32, or -- `probe` -- its decisions alone: the plan of the launch it would make (of the first one when the rows are cut
-// in two), nothing launched
-int gemm_front(const float *A, int64_t lda, int64_t strideA, const float *Bt, int64_t ldb, int64_t strideB, float *C, int64_t ldc,
-               int64_t strideC, int M, int N, int K, int batch, const idiff_epilogue *ep, void *stream, IgemmPlan *probe) {
-  using namespace idiff;
-  if (M < 0 || N < 0 || K <= 0 || batch < 0) return fail("gemm: bad sizes M=%d N=%d K=%d batch=%d", M, N, K, batch);
-  if (M == 0 || N == 0 || batch == 0) { if (probe) probe->family = -1; return 0; }
-  if (!A || !Bt || !C) return fail("gemm: null pointer");
-  if (lda < K || ldb < K || ldc < N) return fail("gemm: leading dimension smaller than the row length");
-  if (batch > 65535) return fail("gemm: batch %d exceeds grid.y", batch);
+// what the linear and the convolution front end fill alike
+IgemmParams igemm_params(const float *A, int64_t lda, const float *Bt, int64_t ldb, float *C, int64_t ldc, int M, int N, int K,
+                         const idiff_epilogue *ep) {
   IgemmParams p = {};
-  p.A = A; p.Bt = Bt; p.C = C; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
-  p.strideA = strideA; p.strideB = strideB; p.strideC = strideC; p.M = M; p.N = N; p.K = K;
+  p.A = A; p.Bt = Bt; p.C = C; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
   idiff::set_epilogue(p, ep);
-  const bool vec = (K % 4 == 0) && (lda % 4 == 0) && (ldb % 4 == 0) && (strideA % 4 == 0) && (strideB % 4 == 0) &&
-                   aligned16(A) && aligned16(Bt);
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t a_bytes = ((int64_t)(M - 1) * lda + K) * 4, b_bytes = ((int64_t)(N - 1) * ldb + K) * 4;
-  if (vec && batch == 1 && a_bytes >= BUF_LIMIT && b_bytes < BUF_LIMIT && !idiff::option(idiff::OPT_NO_PIPE)) {
-    if (ep && ep->colstats) return fail("gemm: colstats is not available for operands beyond 4 GiB");
-    const int rpg = (ep && ep->rows_per_group > 0) ? ep->rows_per_group : 1;
-    const int mid = (M / 2 / rpg) * rpg;
-    if (mid > 0) {
-      idiff_epilogue lo, hi;
-      if (ep) { lo = *ep; hi = shift_epilogue(*ep, mid); }
-      int rc = gemm_front(A, lda, 0, Bt, ldb, 0, C, ldc, 0, mid, N, K, 1, ep ? &lo : nullptr, stream, probe);
-      if (rc || probe) return rc;
-      return gemm_front(A + (int64_t)mid * lda, lda, 0, Bt, ldb, 0, C + (int64_t)mid * ldc, ldc, 0, M - mid, N, K, 1,
-                        ep ? &hi : nullptr, stream, nullptr);
-    }
-  }
-  if (vec && a_bytes < BUF_LIMIT && b_bytes < BUF_LIMIT && !idiff::option(idiff::OPT_NO_PIPE)) {
-    p.a_bytes = (uint32_t)a_bytes; p.b_bytes = (uint32_t)b_bytes;
-    return igemm_run<false>(p, batch, WANT_PIPE, st, probe);
-  }
-  if (ep && ep->colstats) return fail("gemm: colstats requested for a problem the pipelined kernel does not take "
-                                      "(ask idiff_gemm_colstats_split first)");
-  return igemm_run<false>(p, batch, vec ? WANT_DIRECT_VEC : WANT_DIRECT_SCALAR, st, probe);
-}
-}  // namespace
-
-IDIFF_API int idiff_gemm_f32(const float *A, int64_t lda, int64_t strideA, const float *Bt, int64_t ldb,
-                             int64_t strideB, float *C, int64_t ldc, int64_t strideC, int M, int N, int K,
-                             int batch, const idiff_epilogue *ep, void *stream) {
-  return gemm_front(A, lda, strideA, Bt, ldb, strideB, C, ldc, strideC, M, N, K, batch, ep, stream, nullptr);
+  return p;
 }
 
-namespace {
 // {s, 1 / s} with s the power of two that brings max |Bt| into [2^11, 2^12) (1 for an all-zero matrix); one workgroup
 __global__ void __launch_bounds__(256) pairs_scale_kernel(const float *__restrict__ bt, int64_t ldb, int N, int K, float *__restrict__ out) {
   __shared__ float red[256];
@@ -1155,75 +1123,6 @@ IDIFF_API int idiff_gemm_pairs_scale_f32(const float *Bt, int64_t ldb, int N, in
   if (N <= 0 || K <= 0 || ldb < K) return fail("gemm_pairs_scale: bad shape N=%d K=%d ldb=%lld", N, K, (long long)ldb);
   hipLaunchKernelGGL(pairs_scale_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, Bt, ldb, N, K, scale);
   return launch_status("gemm_pairs_scale");
-}
-
-namespace {
-// idiff_gemm_pairs_f32, or its decisions alone (`probe`, as gemm_front)
-int pairs_front(const float *A, int64_t lda, int64_t strideA, const float *Bt, int64_t ldb, int64_t strideB, const float *w_scale,
-                int weight_is_a, const float *act_scale, float *C, int64_t ldc, int64_t strideC, int M, int N, int K, int batch,
-                const idiff_epilogue *ep, void *stream, IgemmPlan *probe) {
-  using namespace idiff;
-  if (M < 0 || N < 0 || K <= 0 || batch < 0) return fail("gemm_pairs: bad sizes M=%d N=%d K=%d batch=%d", M, N, K, batch);
-  if (M == 0 || N == 0 || batch == 0) { if (probe) probe->family = -1; return 0; }
-  if (!A || !Bt || !C || !w_scale) return fail("gemm_pairs: null pointer");
-  if (lda < K || ldb < K || ldc < N) return fail("gemm_pairs: leading dimension smaller than the row length");
-  if (!pairs_geometry_ok(M, N, K, batch)) return fail("gemm_pairs: M=%d N=%d K=%d batch=%d not served (ask idiff_gemm_pairs_ok)", M, N, K, batch);
-  const bool vec = (lda % 4 == 0) && (ldb % 4 == 0) && (strideA % 4 == 0) && (strideB % 4 == 0) && aligned16(A) && aligned16(Bt);
-  const int64_t a_bytes = ((int64_t)(M - 1) * lda + K) * 4, b_bytes = ((int64_t)(N - 1) * ldb + K) * 4;
-  if (!vec || a_bytes >= BUF_LIMIT || b_bytes >= BUF_LIMIT)
-    return fail("gemm_pairs: operands must be 16-byte aligned with row pitches and batch strides that are multiples of 4, one "
-                "batch slice inside 4 GiB");
-  if (ep && ep->colstats && batch != 1) return fail("gemm_pairs: colstats only for unbatched problems");
-  IgemmParams p = {};
-  p.A = A; p.Bt = Bt; p.C = C; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
-  p.strideA = strideA; p.strideB = strideB; p.strideC = strideC;
-  p.a_bytes = (uint32_t)a_bytes; p.b_bytes = (uint32_t)b_bytes;
-  p.scale_a = weight_is_a ? w_scale : act_scale; p.scale_b = weight_is_a ? act_scale : w_scale;
-  idiff::set_epilogue(p, ep);
-  return igemm_run<false>(p, batch, WANT_PAIRS, (hipStream_t)stream, probe);
-}
-}  // namespace
-
-IDIFF_API int idiff_gemm_pairs_f32(const float *A, int64_t lda, int64_t strideA, const float *Bt, int64_t ldb, int64_t strideB,
-                                   const float *w_scale, int weight_is_a, const float *act_scale, float *C, int64_t ldc, int64_t strideC,
-                                   int M, int N, int K, int batch, const idiff_epilogue *ep, void *stream) {
-  return pairs_front(A, lda, strideA, Bt, ldb, strideB, w_scale, weight_is_a, act_scale, C, ldc, strideC, M, N, K, batch, ep, stream, nullptr);
-}
-
-IDIFF_API const char *idiff_gemm_route(const void *A, int64_t lda, int64_t strideA, const void *Bt, int64_t ldb, int64_t strideB,
-                                       const void *C, int64_t ldc, int64_t strideC, int M, int N, int K, int batch,
-                                       const idiff_epilogue *ep, int pairs) {
-  IgemmPlan c = {};
-  const float *a = (const float *)A, *bt = (const float *)Bt;
-  float *out = (float *)const_cast<void *>(C);
-  // (the pair form only asks of its scale that there is one)
-  const int rc = pairs ? pairs_front(a, lda, strideA, bt, ldb, strideB, bt, 0, nullptr, out, ldc, strideC, M, N, K, batch, ep, nullptr, &c)
-                       : gemm_front(a, lda, strideA, bt, ldb, strideB, out, ldc, strideC, M, N, K, batch, ep, nullptr, &c);
-  if (rc) return nullptr;
-  return c.family < 0 ? "none" : igemm_plan_name(c);
-}
-
-IDIFF_API int idiff_gemm_pairs_2src_f32(const float *A1, const float *A2, int64_t lda, int K1, const float *act_scale, const float *Bt,
-                                        int64_t ldb, const float *w_scale, float *C, int64_t ldc, int M, int N, int K,
-                                        const idiff_epilogue *ep, void *stream) {
-  using namespace idiff;
-  if (M < 0 || N < 0 || K <= 0 || K1 <= 0 || K1 >= K) return fail("gemm_pairs_2src: bad sizes M=%d N=%d K=%d K1=%d", M, N, K, K1);
-  if (M == 0 || N == 0) return 0;
-  if (!A1 || !A2 || !Bt || !C || !w_scale) return fail("gemm_pairs_2src: null pointer");
-  if (K1 % BK) return fail("gemm_pairs_2src: the split column K1 = %d must be a multiple of %d", K1, BK);
-  if (lda < K1 || lda < K - K1 || ldb < K || ldc < N) return fail("gemm_pairs_2src: leading dimension smaller than the row length");
-  if (!pairs_geometry_ok(M, N, K, 1)) return fail("gemm_pairs_2src: M=%d N=%d K=%d not served (ask idiff_gemm_pairs_ok)", M, N, K);
-  const int64_t a1_bytes = ((int64_t)(M - 1) * lda + K1) * 4, a2_bytes = ((int64_t)(M - 1) * lda + (K - K1)) * 4;
-  const int64_t b_bytes = ((int64_t)(N - 1) * ldb + K) * 4;
-  const bool vec = (lda % 4 == 0) && (ldb % 4 == 0) && aligned16(A1) && aligned16(A2) && aligned16(Bt);
-  if (!vec || a1_bytes >= BUF_LIMIT || a2_bytes >= BUF_LIMIT || b_bytes >= BUF_LIMIT)
-    return fail("gemm_pairs_2src: operands must be 16-byte aligned with row pitches that are multiples of 4 and lie inside 4 GiB");
-  IgemmParams p = {};
-  p.A = A1; p.A2 = A2; p.K1 = K1; p.Bt = Bt; p.C = C; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
-  p.a_bytes = (uint32_t)a1_bytes; p.a2_bytes = (uint32_t)a2_bytes; p.b_bytes = (uint32_t)b_bytes;
-  p.scale_a = act_scale; p.scale_b = w_scale;
-  idiff::set_epilogue(p, ep);
-  return igemm_run<false>(p, 1, WANT_PAIRS, (hipStream_t)stream, nullptr);
 }
 
 namespace {
@@ -1277,42 +1176,126 @@ IDIFF_API int idiff_pairs_act_scale_f32(const double *ws1, int nsplit1, int C1, 
   return launch_status("pairs_act_scale");
 }
 
+namespace {
+// ---- one front end for idiff_gemm_f32, idiff_gemm_pairs_f32, idiff_gemm_2src_f32 and idiff_gemm_pairs_2src_f32: the call as its entry
+// point received it
+struct LinearCall {
+  const char *name;                    // of the entry point, for its messages
+  const float *A, *A2;                 // two_src: columns K1.. of A are the columns of A2 (same row pitch)
+  int K1;
+  bool two_src;
+  const float *Bt;
+  float *C;
+  int64_t lda, ldb, ldc, strideA, strideB, strideC;
+  int M, N, K, batch;
+  const idiff_epilogue *ep;
+  int want;                            // WANT_PIPE; WANT_PAIRS: w_scale (required) for the weight, act_scale for the other operand
+  const float *w_scale, *act_scale;
+  int weight_is_a;
+};
+
+// validate, cut on the host if A exceeds one buffer descriptor, fill the kernel arguments, run -- or, `probe`, report the plan of the
+// launch it would make (of the first one when the rows are cut in two) and launch nothing
+int linear_front(const LinearCall &c, hipStream_t st, IgemmPlan *probe) {
+  using namespace idiff;
+  const bool pairs = c.want == WANT_PAIRS, colstats = c.ep && c.ep->colstats;
+  if (c.M < 0 || c.N < 0 || c.K <= 0 || c.batch < 0 || (c.two_src && (c.K1 <= 0 || c.K1 >= c.K)))
+    return c.two_src ? fail("%s: bad sizes M=%d N=%d K=%d K1=%d", c.name, c.M, c.N, c.K, c.K1)
+                     : fail("%s: bad sizes M=%d N=%d K=%d batch=%d", c.name, c.M, c.N, c.K, c.batch);
+  if (c.M == 0 || c.N == 0 || c.batch == 0) { if (probe) probe->family = -1; return 0; }
+  if (!c.A || (c.two_src && !c.A2) || !c.Bt || !c.C || (pairs && !c.w_scale)) return fail("%s: null pointer", c.name);
+  if (c.K1 % BK) return fail("%s: the split column K1 = %d must be a multiple of %d", c.name, c.K1, BK);
+  if (c.lda < c.K1 || c.lda < c.K - c.K1 || c.ldb < c.K || c.ldc < c.N) return fail("%s: leading dimension smaller than the row length", c.name);
+  if (pairs && !pairs_geometry_ok(c.M, c.N, c.K, c.batch))
+    return fail("%s: M=%d N=%d K=%d batch=%d not served (ask idiff_gemm_pairs_ok)", c.name, c.M, c.N, c.K, c.batch);
+  if (c.batch > 65535) return fail("%s: batch %d exceeds grid.y", c.name, c.batch);
+  // operands allow 16-byte loads; the pair form is asked for by name and does not read IDIFF_NO_PIPE (idiff_gemm_pairs_ok does)
+  const bool vec = pitches16(c.K, c.lda, c.ldb) && c.strideA % 4 == 0 && c.strideB % 4 == 0 && aligned16(c.A) &&
+                   (!c.two_src || aligned16(c.A2)) && aligned16(c.Bt);
+  const int serves = !vec ? PIPE_NO : (pairs ? pipe_fits_linear : pipe_serves_linear)(c.M, c.N, c.K, c.lda, c.ldb, c.K1);
+  if (serves == PIPE_A_BEYOND && c.batch == 1 && !pairs) {
+    if (colstats) return fail("%s: colstats is not available for operands beyond 4 GiB", c.name);
+    if (const int64_t cut = host_cut_row(c.M, 1, c.ep))
+      return run_cut(c.M, cut, c.ep, probe != nullptr, [&](int64_t r0, int64_t r1, const idiff_epilogue *e) {
+        LinearCall h = c;
+        h.A += r0 * c.lda; h.C += r0 * c.ldc; h.M = (int)(r1 - r0); h.ep = e;
+        if (c.two_src) h.A2 += r0 * c.lda;
+        h.strideA = h.strideB = h.strideC = 0;
+        return linear_front(h, st, probe);
+      });
+    // no row to cut at: one source falls through to the general kernel, two have nowhere to go
+    if (c.two_src) return fail("%s: cannot split %d rows inside an epilogue row group of %d", c.name, c.M, c.ep ? c.ep->rows_per_group : 1);
+  }
+  IgemmParams p = igemm_params(c.A, c.lda, c.Bt, c.ldb, c.C, c.ldc, c.M, c.N, c.K, c.ep);
+  p.strideA = c.strideA; p.strideB = c.strideB; p.strideC = c.strideC;
+  if (serves != PIPE_YES) {
+    if (pairs) return fail("%s: operands must be 16-byte aligned with row pitches and batch strides that are multiples of 4, one "
+                           "batch slice inside 4 GiB", c.name);
+    if (c.two_src) return fail("%s: operands must be 16-byte aligned with K %% 4 == 0 and lda %% 4 == 0 (use two idiff_gemm_f32 calls)", c.name);
+    if (colstats) return fail("%s: colstats requested for a problem the pipelined kernel does not take "
+                              "(ask idiff_gemm_colstats_split first)", c.name);
+    return igemm_run<false>(p, c.batch, vec ? WANT_DIRECT_VEC : WANT_DIRECT_SCALAR, st, probe);
+  }
+  if (pairs && colstats && c.batch != 1) return fail("%s: colstats only for unbatched problems", c.name);
+  p.a_bytes = (uint32_t)extent_bytes(c.M, c.lda, c.two_src ? c.K1 : c.K); p.b_bytes = (uint32_t)extent_bytes(c.N, c.ldb, c.K);
+  if (c.two_src) { p.A2 = c.A2; p.K1 = c.K1; p.a2_bytes = (uint32_t)extent_bytes(c.M, c.lda, c.K - c.K1); }
+  if (pairs) { p.scale_a = c.weight_is_a ? c.w_scale : c.act_scale; p.scale_b = c.weight_is_a ? c.act_scale : c.w_scale; }
+  return igemm_run<false>(p, c.batch, c.want, st, probe);
+}
+
+LinearCall linear_call(const char *name, const float *A, int64_t lda, int64_t strideA, const float *Bt, int64_t ldb, int64_t strideB, float *C,
+                       int64_t ldc, int64_t strideC, int M, int N, int K, int batch, const idiff_epilogue *ep, int want) {
+  return LinearCall{name, A, nullptr, 0, false, Bt, C, lda, ldb, ldc, strideA, strideB, strideC, M, N, K, batch, ep, want, nullptr, nullptr, 0};
+}
+LinearCall linear_call_2src(const char *name, const float *A1, const float *A2, int64_t lda, int K1, const float *Bt, int64_t ldb, float *C,
+                            int64_t ldc, int M, int N, int K, const idiff_epilogue *ep, int want) {
+  LinearCall c = linear_call(name, A1, lda, 0, Bt, ldb, 0, C, ldc, 0, M, N, K, 1, ep, want);
+  c.A2 = A2; c.K1 = K1; c.two_src = true;
+  return c;
+}
+}  // namespace
+
+IDIFF_API int idiff_gemm_f32(const float *A, int64_t lda, int64_t strideA, const float *Bt, int64_t ldb,
+                             int64_t strideB, float *C, int64_t ldc, int64_t strideC, int M, int N, int K,
+                             int batch, const idiff_epilogue *ep, void *stream) {
+  return linear_front(linear_call("gemm", A, lda, strideA, Bt, ldb, strideB, C, ldc, strideC, M, N, K, batch, ep, WANT_PIPE), (hipStream_t)stream,
+                      nullptr);
+}
+
+IDIFF_API int idiff_gemm_pairs_f32(const float *A, int64_t lda, int64_t strideA, const float *Bt, int64_t ldb, int64_t strideB,
+                                   const float *w_scale, int weight_is_a, const float *act_scale, float *C, int64_t ldc, int64_t strideC,
+                                   int M, int N, int K, int batch, const idiff_epilogue *ep, void *stream) {
+  LinearCall c = linear_call("gemm_pairs", A, lda, strideA, Bt, ldb, strideB, C, ldc, strideC, M, N, K, batch, ep, WANT_PAIRS);
+  c.w_scale = w_scale; c.act_scale = act_scale; c.weight_is_a = weight_is_a;
+  return linear_front(c, (hipStream_t)stream, nullptr);
+}
+
 IDIFF_API int idiff_gemm_2src_f32(const float *A1, const float *A2, int64_t lda, int K1, const float *Bt, int64_t ldb,
                                   float *C, int64_t ldc, int M, int N, int K, const idiff_epilogue *ep, void *stream) {
-  using namespace idiff;
-  if (M < 0 || N < 0 || K <= 0 || K1 <= 0 || K1 >= K) return fail("gemm_2src: bad sizes M=%d N=%d K=%d K1=%d", M, N, K, K1);
-  if (M == 0 || N == 0) return 0;
-  if (!A1 || !A2 || !Bt || !C) return fail("gemm_2src: null pointer");
-  if (K1 % BK) return fail("gemm_2src: the split column K1 = %d must be a multiple of %d", K1, BK);
-  if (lda < K1 || lda < K - K1 || ldb < K || ldc < N) return fail("gemm_2src: leading dimension smaller than the row length");
-  const int64_t a1_bytes = ((int64_t)(M - 1) * lda + K1) * 4, a2_bytes = ((int64_t)(M - 1) * lda + (K - K1)) * 4;
-  const int64_t b_bytes = ((int64_t)(N - 1) * ldb + K) * 4;
-  const bool vec = (K % 4 == 0) && (lda % 4 == 0) && (ldb % 4 == 0) && aligned16(A1) && aligned16(A2) && aligned16(Bt);
-  if (vec && (a1_bytes >= BUF_LIMIT || a2_bytes >= BUF_LIMIT) && b_bytes < BUF_LIMIT && M > 1 && !idiff::option(idiff::OPT_NO_PIPE)) {
-    // rows are independent: cut them until each half fits one buffer descriptor (as idiff_gemm_f32 does)
-    if (ep && ep->colstats) return fail("gemm_2src: colstats is not available for operands beyond 4 GiB");
-    const int rpg = (ep && ep->rows_per_group > 0) ? ep->rows_per_group : 1;
-    int mid = (M / 2 / rpg) * rpg;
-    if (mid <= 0) mid = M / 2;
-    if (mid % rpg) return fail("gemm_2src: cannot split %d rows inside an epilogue row group of %d", M, rpg);
-    idiff_epilogue lo, hi;
-    if (ep) { lo = *ep; hi = shift_epilogue(*ep, mid); }
-    int rc = idiff_gemm_2src_f32(A1, A2, lda, K1, Bt, ldb, C, ldc, mid, N, K, ep ? &lo : nullptr, stream);
-    if (rc) return rc;
-    return idiff_gemm_2src_f32(A1 + (int64_t)mid * lda, A2 + (int64_t)mid * lda, lda, K1, Bt, ldb, C + (int64_t)mid * ldc, ldc,
-                               M - mid, N, K, ep ? &hi : nullptr, stream);
-  }
-  if (!vec || a1_bytes >= BUF_LIMIT || a2_bytes >= BUF_LIMIT || b_bytes >= BUF_LIMIT || idiff::option(idiff::OPT_NO_PIPE))
-    return fail("gemm_2src: operands must be 16-byte aligned with K %% 4 == 0 and lda %% 4 == 0 (use two idiff_gemm_f32 calls)");
-  IgemmParams p = {};
-  p.A = A1; p.A2 = A2; p.K1 = K1; p.Bt = Bt; p.C = C; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
-  p.a_bytes = (uint32_t)a1_bytes; p.a2_bytes = (uint32_t)a2_bytes; p.b_bytes = (uint32_t)b_bytes;
-  idiff::set_epilogue(p, ep);
-  return igemm_run<false>(p, 1, WANT_PIPE, (hipStream_t)stream, nullptr);
+  return linear_front(linear_call_2src("gemm_2src", A1, A2, lda, K1, Bt, ldb, C, ldc, M, N, K, ep, WANT_PIPE), (hipStream_t)stream, nullptr);
+}
+
+IDIFF_API int idiff_gemm_pairs_2src_f32(const float *A1, const float *A2, int64_t lda, int K1, const float *act_scale, const float *Bt,
+                                        int64_t ldb, const float *w_scale, float *C, int64_t ldc, int M, int N, int K,
+                                        const idiff_epilogue *ep, void *stream) {
+  LinearCall c = linear_call_2src("gemm_pairs_2src", A1, A2, lda, K1, Bt, ldb, C, ldc, M, N, K, ep, WANT_PAIRS);
+  c.w_scale = w_scale; c.act_scale = act_scale;
+  return linear_front(c, (hipStream_t)stream, nullptr);
+}
+
+IDIFF_API const char *idiff_gemm_route(const void *A, int64_t lda, int64_t strideA, const void *Bt, int64_t ldb, int64_t strideB,
+                                       const void *C, int64_t ldc, int64_t strideC, int M, int N, int K, int batch,
+                                       const idiff_epilogue *ep, int pairs) {
+  IgemmPlan plan = {};
+  LinearCall c = linear_call(pairs ? "gemm_pairs" : "gemm", (const float *)A, lda, strideA, (const float *)Bt, ldb, strideB,
+                             (float *)const_cast<void *>(C), ldc, strideC, M, N, K, batch, ep, pairs ? WANT_PAIRS : WANT_PIPE);
+  c.w_scale = c.Bt;   // (the pair form only asks of its scale that there is one)
+  if (linear_front(c, nullptr, &plan)) return nullptr;
+  return plan.family < 0 ? "none" : igemm_plan_name(plan);
 }
 
 namespace {
-// idiff_conv2d_nhwc_f32, or its decisions alone (`probe`, as gemm_front; of the first half when the batch is cut in two)
+// idiff_conv2d_nhwc_f32, or its decisions alone (`probe`, as linear_front; of the first half when the batch is cut in two)
 int conv_front(const float *x, const float *wt, float *out, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad_lo,
                int pad_hi, const idiff_epilogue *ep, void *stream, IgemmPlan *probe) {
   using namespace idiff;
@@ -1336,36 +1319,25 @@ int conv_front(const float *x, const float *wt, float *out, int B, int H, int W,
     }
     return conv3x3_narrow(x, wt, out, B, H, W, Cin, Cout, ep, (hipStream_t)stream);
   }
-  IgemmParams p = {};
-  p.A = x; p.Bt = wt; p.C = out;
-  p.M = (int)M64; p.N = Cout; p.K = KH * KW * Cin;
-  p.lda = 0; p.ldb = p.K; p.ldc = Cout;
-  p.H = H; p.W = W; p.Cin = Cin; p.OH = OH; p.OW = OW; p.KW = KW; p.stride = stride; p.pad = pad;
-  idiff::set_epilogue(p, ep);
-  const int64_t a_bytes = (int64_t)B * H * W * Cin * 4, b_bytes = (int64_t)Cout * p.K * 4;
-  const bool fast_ok = (Cin % BK == 0 || Cin == 4) && KH * KW <= 32 && b_bytes < BUF_LIMIT && !idiff::option(idiff::OPT_NO_PIPE);
-  if (ep && ep->colstats && !(fast_ok && a_bytes < BUF_LIMIT))
+  const int serves = pipe_serves_conv(B, H, W, Cin, Cout, KH, KW);
+  if (ep && ep->colstats && serves != PIPE_YES)
     return fail("conv2d: colstats requested for a problem the pipelined kernel does not take "
                 "(ask idiff_conv2d_colstats_split first)");
-  if (fast_ok && a_bytes >= BUF_LIMIT && B > 1) {
-    // split the batch (images are independent) so that each half fits one buffer descriptor
-    const int rpg = (ep && ep->rows_per_group > 0) ? ep->rows_per_group : 1;
-    const int b_lo = B / 2;
-    const int64_t m_lo = (int64_t)b_lo * OH * OW;
-    if (m_lo % rpg == 0) {
-      idiff_epilogue lo, hi;
-      if (ep) { lo = *ep; hi = shift_epilogue(*ep, m_lo); }
-      int rc = conv_front(x, wt, out, b_lo, H, W, Cin, Cout, KH, KW, stride, pad_lo, pad_hi, ep ? &lo : nullptr, stream, probe);
-      if (rc || probe) return rc;
-      return conv_front(x + (int64_t)b_lo * H * W * Cin, wt, out + m_lo * Cout, B - b_lo, H, W, Cin, Cout, KH, KW,
-                        stride, pad_lo, pad_hi, ep ? &hi : nullptr, stream, nullptr);
-    }
+  if (serves == PIPE_A_BEYOND && B > 1) {
+    // images are independent: cut the batch so that each half fits one buffer descriptor; a middle image that ends inside an epilogue
+    // row group falls through to the general kernel
+    if (const int64_t cut = host_cut_row(B, OH * OW, ep))
+      return run_cut(M64, cut, ep, probe != nullptr, [&](int64_t r0, int64_t r1, const idiff_epilogue *e) {
+        return conv_front(x + r0 / (OH * OW) * H * W * Cin, wt, out + r0 * Cout, (int)((r1 - r0) / (OH * OW)), H, W, Cin, Cout, KH, KW, stride,
+                          pad_lo, pad_hi, e, stream, probe);
+      });
   }
-  if (fast_ok && a_bytes < BUF_LIMIT) {
-    p.a_bytes = (uint32_t)a_bytes; p.b_bytes = (uint32_t)b_bytes;
-    return igemm_run<true>(p, 1, WANT_PIPE, (hipStream_t)stream, probe);
-  }
-  return igemm_run<true>(p, 1, WANT_DIRECT_VEC, (hipStream_t)stream, probe);
+  const int K = KH * KW * Cin;
+  IgemmParams p = igemm_params(x, 0, wt, K, out, Cout, (int)M64, Cout, K, ep);
+  p.H = H; p.W = W; p.Cin = Cin; p.OH = OH; p.OW = OW; p.KW = KW; p.stride = stride; p.pad = pad;
+  if (serves != PIPE_YES) return igemm_run<true>(p, 1, WANT_DIRECT_VEC, (hipStream_t)stream, probe);
+  p.a_bytes = (uint32_t)extent_bytes((int64_t)B * H * W, Cin, Cin); p.b_bytes = (uint32_t)extent_bytes(Cout, K, K);
+  return igemm_run<true>(p, 1, WANT_PIPE, (hipStream_t)stream, probe);
 }
 }  // namespace
 
@@ -1387,24 +1359,21 @@ IDIFF_API const char *idiff_conv2d_route(const void *x, const void *wt, const vo
 
 // Number of workgroup row-tiles per sample when `rows_per_sample` consecutive output rows form one sample, i.e. the
 // `nsplit` of the [samples, nsplit, N, 2] fp64 layout idiff_epilogue.colstats is written in -- or 0 when the fused
-// statistics are not available for this problem (then the consumer runs idiff_groupnorm_stats_f32 as usual).
+// statistics are not available for this problem (then the consumer runs idiff_groupnorm_stats_f32 as usual).  "Available": the
+// front end's own rule (pipe_serves_linear / pipe_serves_conv) and whole tiles of the front end's own tile (igemm_tile) per sample.
 IDIFF_API int idiff_gemm_colstats_split(int M, int N, int K, int64_t lda, int64_t ldb, int rows_per_sample) {
-  if (M <= 0 || N <= 0 || K <= 0 || rows_per_sample <= 0 || M % rows_per_sample) return 0;
-  if (idiff::option(idiff::OPT_NO_PIPE) || idiff::option(idiff::OPT_NO_COLSTATS)) return 0;
-  if (K % 4 || lda % 4 || ldb % 4) return 0;
-  if (((int64_t)(M - 1) * lda + K) * 4 >= BUF_LIMIT || ((int64_t)(N - 1) * ldb + K) * 4 >= BUF_LIMIT) return 0;
-  const int bm = pipe_tile_rows(M, N, 1);
+  if (M <= 0 || N <= 0 || K <= 0 || rows_per_sample <= 0 || M % rows_per_sample || idiff::option(idiff::OPT_NO_COLSTATS)) return 0;
+  if (pipe_serves_linear(M, N, K, lda, ldb) != PIPE_YES) return 0;
+  const int bm = igemm_tile(M, N, 1, WANT_PIPE).bm;
   return rows_per_sample % bm == 0 ? rows_per_sample / bm : 0;
 }
 
 IDIFF_API int idiff_conv2d_colstats_split(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad_lo,
                                           int pad_hi) {
-  if (B <= 0 || (Cin % BK && Cin != 4) || KH * KW > 32 || idiff::option(idiff::OPT_NO_PIPE) || idiff::option(idiff::OPT_NO_COLSTATS)) return 0;
+  if (B <= 0 || idiff::option(idiff::OPT_NO_COLSTATS) || pipe_serves_conv(B, H, W, Cin, Cout, KH, KW) != PIPE_YES) return 0;
   const int OH = (H + pad_lo + pad_hi - KH) / stride + 1, OW = (W + pad_lo + pad_hi - KW) / stride + 1;
-  if (OH <= 0 || OW <= 0) return 0;
-  if ((int64_t)B * H * W * Cin * 4 >= BUF_LIMIT || (int64_t)Cout * KH * KW * Cin * 4 >= BUF_LIMIT) return 0;
   const int64_t M = (int64_t)B * OH * OW;
-  if (M > 0x7fffffff) return 0;
-  const int bm = pipe_tile_rows((int)M, Cout, 1), rps = OH * OW;
+  if (OH <= 0 || OW <= 0 || M > 0x7fffffff) return 0;
+  const int bm = igemm_tile((int)M, Cout, 1, WANT_PIPE).bm, rps = OH * OW;
   return rps % bm == 0 ? rps / bm : 0;
 }

@@ -838,21 +838,11 @@ int conv2d_winograd_impl(const float *x, const float *u, float *out, int B, int 
   if (x_bytes >= X_LIMIT || out_bytes >= X_LIMIT || res_bytes >= X_LIMIT) {
     if (ep && ep->colstats) return fail("conv2d_winograd: colstats is not available for inputs beyond one buffer descriptor");
     if (B < 2) return fail("conv2d_winograd: a single image exceeds one buffer descriptor");
-    const int rpg = (ep && ep->rows_per_group > 0) ? ep->rows_per_group : 1;
-    const int b_lo = B / 2;
-    const int64_t m_lo = (int64_t)b_lo * H * W;
-    if (m_lo % rpg) return fail("conv2d_winograd: cannot split the batch inside an epilogue row group");
-    idiff_epilogue lo, hi;
-    if (ep) {
-      lo = *ep; hi = *ep;
-      const int64_t g0 = m_lo / rpg;
-      if (hi.rowbias) hi.rowbias += g0 * ep->ld_rowbias;
-      if (hi.residual) hi.residual += m_lo * ep->ld_residual;
-      if (hi.rowscale) hi.rowscale += g0;
-    }
-    int rc = conv2d_winograd_impl(x, u, out, b_lo, H, W, Cin, Cout, ep ? &lo : nullptr, stream, split);
-    if (rc) return rc;
-    return conv2d_winograd_impl(x + m_lo * Cin, u, out + m_lo * Cout, B - b_lo, H, W, Cin, Cout, ep ? &hi : nullptr, stream, split);
+    const int64_t cut = host_cut_row(B, H * W, ep);
+    if (!cut) return fail("conv2d_winograd: cannot split the batch inside an epilogue row group");
+    return run_cut((int64_t)B * H * W, cut, ep, false, [&](int64_t r0, int64_t r1, const idiff_epilogue *e) {
+      return conv2d_winograd_impl(x + r0 * Cin, u, out + r0 * Cout, (int)((r1 - r0) / (H * W)), H, W, Cin, Cout, e, stream, split);
+    });
   }
   WinoParams p = {};
   // two output-channel tiles per scheduling group: the workgroups of an XCD then stream two filter slabs instead of

@@ -232,7 +232,11 @@ const char *idiff_conv2d_route(const void *x, const void *wt, const void *out, i
 
 /* Fused GroupNorm statistics: when `rows_per_sample` consecutive output rows form one sample, these return the number of
  * workgroup row-tiles per sample (`nsplit`: epilogue.colstats is then laid out [samples, nsplit, N, 2]) or 0 when the
- * fused statistics are unavailable for the problem (general kernel, operands beyond 4 GiB, tiles straddling samples). */
+ * fused statistics are unavailable for the problem (general kernel, operands beyond 4 GiB, tiles straddling samples).  The rule is the
+ * launchers' own: "the pipelined kernel takes this shape" (csrc/igemm.hip: pipe_serves_linear / pipe_serves_conv, which the front ends
+ * of idiff_gemm_f32 / idiff_conv2d_nhwc_f32 ask too, adding pointer alignment and batch strides) and whole tiles of the chooser's tile
+ * (igemm_tile) per sample.  nsplit > 0 therefore implies that a call with 16-byte aligned operands takes tiles of rows_per_sample /
+ * nsplit rows; the launchers accept some calls these decline (samples of 96 rows in tiles of 64). */
 int idiff_gemm_colstats_split(int M, int N, int K, int64_t lda, int64_t ldb, int rows_per_sample);
 int idiff_conv2d_colstats_split(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad_lo,
                                 int pad_hi);

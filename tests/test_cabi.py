@@ -298,3 +298,159 @@ def test_refusal_table_is_complete():
     assert sorted(_REFUSALS) == sorted(c[0] for c in _refusal_cases())
     for ident, (rc, text) in _REFUSALS.items():
         assert (rc, text) == (0, "") if ident.endswith("zero_batch") else rc == 1001 and text
+
+
+# ---- what the five contraction entry points of csrc/igemm.hip refuse before any device call
+_A, _A2, _BT, _C, _WS, _AS, _STATS = 0x10000, 0x18000, 0x20000, 0x30000, 0x40000, 0x50000, 0x60000     # fabricated, 16-byte aligned
+
+
+def _igemm_refusal_cases():
+    """(id, symbol, arguments, switches).  One violated condition per call; `zero_*` are the calls with nothing to do."""
+    cases = []
+
+    def gemm(tag, A=_A, lda=None, Bt=_BT, ldb=None, C=_C, ldc=None, M=256, N=64, K=64, batch=1, ep=None, switches=()):
+        lda, ldb, ldc = K if lda is None else lda, K if ldb is None else ldb, N if ldc is None else ldc
+        cases.append((f"gemm-{tag}", "idiff_gemm_f32", [A, lda, M * lda, Bt, ldb, N * ldb, C, ldc, M * ldc, M, N, K, batch, ep], switches))
+
+    def pairs(tag, A=_A, lda=None, Bt=_BT, ldb=None, ws=_WS, C=_C, ldc=None, M=32768, N=128, K=64, batch=1, ep=None):
+        lda, ldb, ldc = K if lda is None else lda, K if ldb is None else ldb, N if ldc is None else ldc
+        cases.append((f"pairs-{tag}", "idiff_gemm_pairs_f32",
+                      [A, lda, M * lda, Bt, ldb, N * ldb, ws, 0, _AS, C, ldc, M * ldc, M, N, K, batch, ep], ()))
+
+    def two(tag, pair=False, A2=_A2, lda=None, K1=64, ldb=None, ldc=None, M=None, N=None, K=128, ep=None, switches=()):
+        M, N = M or (32768 if pair else 256), N or (128 if pair else 64)
+        lda, ldb, ldc = max(K1, K - K1) if lda is None else lda, K if ldb is None else ldb, N if ldc is None else ldc
+        if pair:
+            cases.append((f"pairs_2src-{tag}", "idiff_gemm_pairs_2src_f32", [_A, A2, lda, K1, _AS, _BT, ldb, _WS, _C, ldc, M, N, K, ep], switches))
+        else:
+            cases.append((f"2src-{tag}", "idiff_gemm_2src_f32", [_A, A2, lda, K1, _BT, ldb, _C, ldc, M, N, K, ep], switches))
+
+    def conv(tag, x=_A, wt=_BT, out=_C, B=2, H=8, W=8, Cin=32, Cout=64, k=3, stride=1, pad=1, ep=None):
+        cases.append((f"conv-{tag}", "idiff_conv2d_nhwc_f32", [x, wt, out, B, H, W, Cin, Cout, k, k, stride, pad, pad, ep], ()))
+
+    for f in (gemm, pairs):
+        f("negative_m", M=-1); f("k_zero", K=0); f("negative_batch", batch=-1)
+        f("null_a", A=0); f("null_bt", Bt=0); f("null_c", C=0)
+        f("lda_below_k", lda=60); f("ldb_below_k", ldb=60); f("ldc_below_n", ldc=60)
+        f("zero_m", M=0)
+    gemm("batch_above_grid", batch=65536)
+    gemm("colstats_beyond_4gib", M=1_200_000, K=1024, ep=dict(colstats=_STATS, rows_per_group=128))
+    gemm("colstats_general_kernel", K=101, ep=dict(colstats=_STATS, rows_per_group=64))
+    gemm("colstats_partial_tile", M=300, N=72, ep=dict(colstats=_STATS, rows_per_group=100))
+    pairs("not_served", M=300)
+    pairs("misaligned_a", A=_A + 4)
+    pairs("pitch_not_4", lda=66)
+    pairs("slice_beyond_4gib", lda=40000)
+    pairs("colstats_batched", batch=2, ep=dict(colstats=_STATS, rows_per_group=128))
+    pairs("null_w_scale", ws=0)
+    for pair in (False, True):
+        two("k1_zero", pair, K1=0, lda=128); two("k1_equals_k", pair, K1=128, lda=128); two("k1_not_32", pair, K1=48, lda=80)
+        two("lda_below_k1", pair, K1=64, K=96, lda=48); two("lda_below_k_minus_k1", pair, K1=32, K=128, lda=64)
+        two("misaligned_a2", pair, A2=_A2 + 8)
+    two("no_pipe", switches=("IDIFF_NO_PIPE",))
+    two("colstats_beyond_4gib", M=1_200_000, lda=1024, ep=dict(colstats=_STATS, rows_per_group=128))
+    # both sources beyond one descriptor by their pitch, one row group of an odd number of rows: no row to cut at
+    two("cut_inside_row_group", M=2049, lda=1 << 20, ep=dict(rowscale=_STATS, rows_per_group=2049))
+    two("not_served", True, M=300)
+    conv("bad_stride", stride=0); conv("negative_pad", pad=-1)
+    conv("cin_not_4", Cin=30)
+    conv("null_x", x=0); conv("null_wt", wt=0); conv("null_out", out=0)
+    conv("misaligned_x", x=_A + 4); conv("misaligned_wt", wt=_BT + 8)
+    conv("empty_output", H=1, W=1, pad=0)
+    conv("rows_beyond_int32", B=40000, H=256, W=256, Cin=4, k=1, pad=0)
+    conv("colstats_not_pipelined", Cin=8, ep=dict(colstats=_STATS, rows_per_group=64))
+    conv("zero_batch", B=0)
+    return cases
+
+
+# Return code and idiff_last_error() of every case, recorded from the library of the commit before the five entry points got one front end.
+# idiff_gemm_pairs_2src_f32 now reports an unserved shape and unfit operands in the words of idiff_gemm_pairs_f32; for those two cases the
+# words both texts share are what is pinned (_IGEMM_UNIFIED; the old text stands above each).
+_IGEMM_REFUSALS = {
+    'gemm-negative_m': (1001, 'gemm: bad sizes M=-1 N=64 K=64 batch=1'),
+    'gemm-k_zero': (1001, 'gemm: bad sizes M=256 N=64 K=0 batch=1'),
+    'gemm-negative_batch': (1001, 'gemm: bad sizes M=256 N=64 K=64 batch=-1'),
+    'gemm-null_a': (1001, 'gemm: null pointer'),
+    'gemm-null_bt': (1001, 'gemm: null pointer'),
+    'gemm-null_c': (1001, 'gemm: null pointer'),
+    'gemm-lda_below_k': (1001, 'gemm: leading dimension smaller than the row length'),
+    'gemm-ldb_below_k': (1001, 'gemm: leading dimension smaller than the row length'),
+    'gemm-ldc_below_n': (1001, 'gemm: leading dimension smaller than the row length'),
+    'gemm-zero_m': (0, ''),
+    'pairs-negative_m': (1001, 'gemm_pairs: bad sizes M=-1 N=128 K=64 batch=1'),
+    'pairs-k_zero': (1001, 'gemm_pairs: bad sizes M=32768 N=128 K=0 batch=1'),
+    'pairs-negative_batch': (1001, 'gemm_pairs: bad sizes M=32768 N=128 K=64 batch=-1'),
+    'pairs-null_a': (1001, 'gemm_pairs: null pointer'),
+    'pairs-null_bt': (1001, 'gemm_pairs: null pointer'),
+    'pairs-null_c': (1001, 'gemm_pairs: null pointer'),
+    'pairs-lda_below_k': (1001, 'gemm_pairs: leading dimension smaller than the row length'),
+    'pairs-ldb_below_k': (1001, 'gemm_pairs: leading dimension smaller than the row length'),
+    'pairs-ldc_below_n': (1001, 'gemm_pairs: leading dimension smaller than the row length'),
+    'pairs-zero_m': (0, ''),
+    'gemm-batch_above_grid': (1001, 'gemm: batch 65536 exceeds grid.y'),
+    'gemm-colstats_beyond_4gib': (1001, 'gemm: colstats is not available for operands beyond 4 GiB'),
+    'gemm-colstats_general_kernel': (1001, 'gemm: colstats requested for a problem the pipelined kernel does not take (ask idiff_gemm_colstats_split first)'),
+    'gemm-colstats_partial_tile': (1001, 'gemm: colstats with M = 300 rows in tiles of 64: no whole tiles (ask idiff_gemm_colstats_split first)'),
+    'pairs-not_served': (1001, 'gemm_pairs: M=300 N=128 K=64 batch=1 not served (ask idiff_gemm_pairs_ok)'),
+    'pairs-misaligned_a': (1001, 'gemm_pairs: operands must be 16-byte aligned with row pitches and batch strides that are multiples of 4, one batch slice inside 4 GiB'),
+    'pairs-pitch_not_4': (1001, 'gemm_pairs: operands must be 16-byte aligned with row pitches and batch strides that are multiples of 4, one batch slice inside 4 GiB'),
+    'pairs-slice_beyond_4gib': (1001, 'gemm_pairs: operands must be 16-byte aligned with row pitches and batch strides that are multiples of 4, one batch slice inside 4 GiB'),
+    'pairs-colstats_batched': (1001, 'gemm_pairs: colstats only for unbatched problems'),
+    'pairs-null_w_scale': (1001, 'gemm_pairs: null pointer'),
+    '2src-k1_zero': (1001, 'gemm_2src: bad sizes M=256 N=64 K=128 K1=0'),
+    '2src-k1_equals_k': (1001, 'gemm_2src: bad sizes M=256 N=64 K=128 K1=128'),
+    '2src-k1_not_32': (1001, 'gemm_2src: the split column K1 = 48 must be a multiple of 32'),
+    '2src-lda_below_k1': (1001, 'gemm_2src: leading dimension smaller than the row length'),
+    '2src-lda_below_k_minus_k1': (1001, 'gemm_2src: leading dimension smaller than the row length'),
+    '2src-misaligned_a2': (1001, 'gemm_2src: operands must be 16-byte aligned with K % 4 == 0 and lda % 4 == 0 (use two idiff_gemm_f32 calls)'),
+    'pairs_2src-k1_zero': (1001, 'gemm_pairs_2src: bad sizes M=32768 N=128 K=128 K1=0'),
+    'pairs_2src-k1_equals_k': (1001, 'gemm_pairs_2src: bad sizes M=32768 N=128 K=128 K1=128'),
+    'pairs_2src-k1_not_32': (1001, 'gemm_pairs_2src: the split column K1 = 48 must be a multiple of 32'),
+    'pairs_2src-lda_below_k1': (1001, 'gemm_pairs_2src: leading dimension smaller than the row length'),
+    'pairs_2src-lda_below_k_minus_k1': (1001, 'gemm_pairs_2src: leading dimension smaller than the row length'),
+    # was: gemm_pairs_2src: operands must be 16-byte aligned with row pitches that are multiples of 4 and lie inside 4 GiB
+    'pairs_2src-misaligned_a2': (1001, 'operands must be 16-byte aligned with row pitches'),
+    '2src-no_pipe': (1001, 'gemm_2src: operands must be 16-byte aligned with K % 4 == 0 and lda % 4 == 0 (use two idiff_gemm_f32 calls)'),
+    '2src-colstats_beyond_4gib': (1001, 'gemm_2src: colstats is not available for operands beyond 4 GiB'),
+    '2src-cut_inside_row_group': (1001, 'gemm_2src: cannot split 2049 rows inside an epilogue row group of 2049'),
+    # was: gemm_pairs_2src: M=300 N=128 K=128 not served (ask idiff_gemm_pairs_ok)
+    'pairs_2src-not_served': (1001, 'not served (ask idiff_gemm_pairs_ok)'),
+    'conv-bad_stride': (1001, 'conv2d: bad geometry'),
+    'conv-negative_pad': (1001, 'conv2d: bad geometry'),
+    'conv-cin_not_4': (1001, 'conv2d: Cin must be a multiple of 4 (pad the channels), got 30'),
+    'conv-null_x': (1001, 'conv2d: null pointer'),
+    'conv-null_wt': (1001, 'conv2d: null pointer'),
+    'conv-null_out': (1001, 'conv2d: null pointer'),
+    'conv-misaligned_x': (1001, 'conv2d: x and wt must be 16-byte aligned'),
+    'conv-misaligned_wt': (1001, 'conv2d: x and wt must be 16-byte aligned'),
+    'conv-empty_output': (1001, 'conv2d: empty output'),
+    'conv-rows_beyond_int32': (1001, 'conv2d: B*OH*OW overflows int32'),
+    'conv-colstats_not_pipelined': (1001, 'conv2d: colstats requested for a problem the pipelined kernel does not take (ask idiff_conv2d_colstats_split first)'),
+    'conv-zero_batch': (0, ''),
+}
+_IGEMM_UNIFIED = ("pairs_2src-misaligned_a2", "pairs_2src-not_served")
+
+
+@pytest.mark.parametrize("case", _igemm_refusal_cases(), ids=lambda c: c[0])
+def test_igemm_entry_points_refuse_before_any_device_call(case):
+    """As the Winograd table above, for idiff_gemm_f32, idiff_gemm_pairs_f32, idiff_gemm_2src_f32, idiff_gemm_pairs_2src_f32 and
+    idiff_conv2d_nhwc_f32: sizes, null pointers, pitches, alignment, operands beyond one buffer descriptor and column sums the
+    pipelined kernel cannot give are turned away by the host front end."""
+    import contextlib
+    ident, symbol, args, switches = case
+    want_rc, want_text = _IGEMM_REFUSALS[ident]
+    with contextlib.ExitStack() as stack:
+        for s in switches:
+            stack.enter_context(_lib.thread_option(s, 1))
+        rc, text = _call_refusal(_lib.lib(), symbol, args)
+    assert rc == want_rc
+    if ident in _IGEMM_UNIFIED:
+        assert text.startswith(symbol[len("idiff_"):-len("_f32")] + ": ") and want_text in text
+    else:
+        assert text == want_text
+
+
+def test_igemm_refusal_table_is_complete():
+    assert sorted(_IGEMM_REFUSALS) == sorted(c[0] for c in _igemm_refusal_cases())
+    for ident, (rc, text) in _IGEMM_REFUSALS.items():
+        assert (rc, text) == (0, "") if ident.split("-")[1].startswith("zero_") else rc == 1001 and text

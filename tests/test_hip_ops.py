@@ -696,7 +696,7 @@ def test_gemm_two_sources_beyond_4gib():
 
 def test_operands_beyond_4gib_are_split_on_the_host():
     """The fast kernel addresses operands through 32-bit-offset buffer descriptors; larger problems are cut into
-    row / image ranges (igemm.hip: shift_epilogue).  Checked on the rows / images around the cut."""
+    row / image ranges (common.h: shift_epilogue).  Checked on the rows / images around the cut."""
     g = torch.Generator(device=DEV).manual_seed(0)
     M, K, N, grp = 1_200_000, 1024, 64, 1000           # A = 4.9 GB
     a = torch.randn(M, K, device=DEV, generator=g)

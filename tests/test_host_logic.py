@@ -587,6 +587,14 @@ _IGEMM_ROUTES = [
     ((), "conv", (0, 8, 8, 32, 64, 3, 1, 1, 1), None, "none"),
     ((), "conv", (3, 8, 8, 30, 64, 3, 1, 1, 1), None, None),                                    # Cin % 4
     ((), "conv", (5, 4, 4, 64, 32, 1, 1, 0, 0), dict(colstats=_P, rows_per_group=16), None),     # 80 rows: no whole tiles of 64
+    # A beyond one buffer descriptor: the rows are cut in two on the host and the query answers for the first half
+    ((), "gemm", dict(M=1_200_000, N=64, K=1024), None, "pipe 128x64 split buf-row"),
+    ((), "gemm", dict(M=1_200_000, N=64, K=1024), dict(rowscale=_P, rows_per_group=1_000_000), "direct-vec 128x64 fp32 scalar"),   # no row to cut at
+    ((), "conv", (2100, 32, 32, 512, 32, 3, 1, 1, 1), None, "pipe 128x32 split buf-row"),
+    ((), "conv", (2101, 32, 32, 512, 32, 3, 1, 1, 1), dict(rowscale=_P, rows_per_group=2048), "pipe 128x32 split buf-block"),
+    ((), "conv", (2100, 32, 32, 512, 32, 3, 1, 1, 1), dict(rowscale=_P, rows_per_group=4096), "direct-vec 128x64 fp32 scalar"),   # 1050 images end inside a group
+    (("IDIFF_NO_PIPE",), "gemm", dict(M=1_200_000, N=64, K=1024), None, "direct-vec 128x64 fp32 scalar"),
+    ((), "gemm", dict(M=1_200_000, N=64, K=1024, batch=2), None, "direct-vec 128x64 fp32 scalar"),   # batched: no cut
 ]
 
 
@@ -616,3 +624,43 @@ def test_igemm_route_table(switches, kind, geom, ep, want):
                                   stride_a=M * K, stride_b=N * K, stride_c=M * N, pairs=kind == "pairs")
             assert not g
     assert got == want
+
+
+@pytest.mark.parametrize("switch", [None, "IDIFF_NO_SPLIT"])
+def test_colstats_queries_agree_with_the_launchers(switch):
+    """idiff_gemm_colstats_split / idiff_conv2d_colstats_split decide whether the executor allocates column sums at all.  Wherever one
+    answers nsplit > 0, the launcher (asked through its route query: same shape, aligned pointers, colstats set, one sample per row
+    group) takes the pipelined kernel with tiles of rows_per_sample / nsplit rows.  Only this direction is a contract: the launcher
+    accepts calls the queries decline (samples of 96 rows in tiles of 64).  The yes counts are those of the library before query and
+    launcher shared their rule (342 of 1296, 576 of 1280, with and without the split-precision arithmetic): the property cannot hold by
+    the queries answering no everywhere."""
+    import contextlib
+    import itertools
+    import os
+    from id_diff_amd import _lib
+    if not os.path.exists(_lib.library_path()):
+        pytest.skip("libidiff_hip.so is not built")
+
+    def holds(route, nsplit, rows_per_sample):
+        return route is not None and route.startswith("pipe ") and int(route.split()[1].split("x")[0]) * nsplit == rows_per_sample
+
+    with _lib.thread_option(switch, 1) if switch else contextlib.nullcontext():
+        yes = 0
+        for M, N, K, rps in itertools.product((64, 128, 192, 256, 300, 4096, 8192, 16384, 32768), (3, 32, 64, 72, 128, 256), (4, 64, 101, 128),
+                                              (16, 64, 96, 128, 256, 1024)):
+            nsplit = _lib.gemm_colstats_split(M, N, K, K, K, rps)
+            if nsplit > 0:
+                yes += 1
+                e = _lib.Epilogue(rows_per_group=rps, out_scale=1.0, colstats=_P)
+                assert holds(_lib.gemm_route(_P, _P, _P, M, N, K, K, K, N, epilogue=e), nsplit, rps), (M, N, K, rps, nsplit)
+        assert yes >= 342
+        yes = 0
+        for B, HW, Cin, Cout, k, stride in itertools.product((1, 2, 5, 64), (4, 8, 16, 32), (4, 8, 32, 64, 128), (3, 32, 64, 128), (1, 3), (1, 2)):
+            nsplit = _lib.conv2d_colstats_split(B, HW, HW, Cin, Cout, k, k, stride, k // 2)
+            if nsplit > 0:
+                yes += 1
+                rps = ((HW + 2 * (k // 2) - k) // stride + 1) ** 2
+                e = _lib.Epilogue(rows_per_group=rps, out_scale=1.0, colstats=_P)
+                assert holds(_lib.conv2d_route(_P, _P, _P, B, HW, HW, Cin, Cout, k, k, stride, k // 2, epilogue=e), nsplit, rps), \
+                    (B, HW, Cin, Cout, k, stride, nsplit)
+        assert yes >= 576
