@@ -143,6 +143,9 @@ _SIGNATURES = {
     "idiff_render_gaussians_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
     "idiff_ksphere_union_ok": (c_i, [c_i, c_i, c_i]),
     "idiff_ksphere_union_score_f32": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
+    "idiff_local_pca_ok": (c_i, [c_i, c_i, c_i, c_i]),
+    "idiff_local_pca_chunk": (c_i, []),
+    "idiff_local_pca_f64": (c_i, [c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -1093,12 +1096,45 @@ def knn(X, k, workspace=None):
     return dist, idx, n_exact
 
 
+# ------------------------------------------------------------------------------------------- local PCA
+def local_pca(X, centre, idx, n_vectors=0):
+    """Spectrum and leading eigenvectors of the sample covariance of every neighbourhood {centre[q]} + idx[q, :] of X [N, D]
+    (CUDA fp32, contiguous; centre [Q] and idx [Q, k] int64, 2 <= k <= 64): ``(eig, basis)`` with eig [Q, min(k, D)] fp64
+    descending and basis [Q, n_vectors, D] fp64 (unit rows, largest component positive, NaN where the eigenvalue is zero to
+    rounding), or None for n_vectors = 0 (idiff_local_pca_f64, one launch).  The kernel checks every index against [0, N)
+    before it reads a row.  One host sync: the per-query status, read back to raise ``RuntimeError`` naming how many queries
+    did not converge, held an index out of range or met a NaN or Inf in their rows."""
+    _dev(X, "X"); _dev(centre, "centre", dtype=torch.int64); _dev(idx, "idx", dtype=torch.int64)
+    if X.ndim != 2 or centre.ndim != 1 or idx.ndim != 2 or idx.shape[0] != centre.shape[0]:
+        raise RuntimeError(f"local_pca: X must be [N, D], centre [Q] and idx [Q, k], got {tuple(X.shape)}, {tuple(centre.shape)} "
+                           f"and {tuple(idx.shape)}")
+    (N, D), (Q, k), nv = X.shape, idx.shape, int(n_vectors)
+    r = min(k, D)
+    eig = torch.empty(Q, r, dtype=torch.float64, device=X.device)
+    basis = torch.empty(Q, nv, D, dtype=torch.float64, device=X.device) if nv > 0 else None
+    status = torch.empty(Q, dtype=torch.int32, device=X.device)
+    if Q == 0:                        # nothing to launch (and no pointers to pass); the sizes are still the library's to refuse
+        if not lib().idiff_local_pca_ok(N, D, k, nv):
+            raise RuntimeError(f"local_pca: N = {N}, D = {D}, k = {k}, n_vectors = {nv} not served (idiff_local_pca_ok)")
+        return eig, basis
+    _check(lib().idiff_local_pca_f64(X.data_ptr(), N, D, centre.data_ptr(), idx.data_ptr(), Q, k, nv, eig.data_ptr(), _ptr(basis),
+                                     status.data_ptr(), _stream()), "idiff_local_pca_f64")
+    st = status.cpu()
+    stalled, outside, nonfinite = int((st == 1).sum()), int((st == 2).sum()), int((st == 3).sum())
+    if stalled or outside or nonfinite:
+        raise RuntimeError(f"local_pca: {stalled} of {Q} queries reached the Jacobi sweep cap without converging, "
+                           f"{outside} hold an index outside [0, {N}), {nonfinite} have a neighbourhood that is not finite (NaN or Inf in X)")
+    return eig, basis
+
+
 # ------------------------------------------------------------------------------------------- geodesic distances (Isomap)
 def __getattr__(name):
     """``_lib.APSP_TILE``: the tile of the blocked Floyd-Warshall, asked of the library (idiff_apsp_tile; the edge cases of the
-    tests sit around it)."""
+    tests sit around it).  ``_lib.LOCAL_PCA_CHUNK``: the columns of X one step of local_pca gathers (idiff_local_pca_chunk)."""
     if name == "APSP_TILE":
         return lib().idiff_apsp_tile()
+    if name == "LOCAL_PCA_CHUNK":
+        return lib().idiff_local_pca_chunk()
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -5,6 +5,7 @@ The reference fills a CSV (index ``method``: mle_5, mle_20, lpca, ppca; one colu
 (benchmark.py:57-68).  Here the estimators are module functions on the MI355X: the neighbour search of the ML
 estimators is one exact kNN (``_lib.knn``), the PCA estimators read the covariance eigenvalues of the fp64 spectrum
 kernels (``_lib.spectrum(X, return_eig=True)``); what remains is O(N k) or O(D^2) host arithmetic in fp64.
+An opt-in fifth kind of name, ``lpca_knn_<k>``, is the per-point form of lpca (``lpca.py``).
 """
 import math
 import os
@@ -168,6 +169,14 @@ def pca_fo_count(eigenvalues, alpha=0.05):
     return int(np.count_nonzero(lam > alpha * lam.max()))
 
 
+def lpca_knn_k(name):
+    """k of an estimator name ``lpca_knn_<k>`` (local PCA over the k nearest neighbours of every point, Fukunaga-Olsen per
+    point, the mean over the points: ``lpca.local_dims``), or None for any other name.  Not in the default list: a user opts
+    in with ``benchmark.estimators.append('lpca_knn_20')``."""
+    head, _, tail = str(name).rpartition('_')
+    return int(tail) if head == 'lpca_knn' and tail.isdigit() and tail.isascii() else None
+
+
 # ------------------------------------------------------------------------------------------- the benchmark
 class Benchmark():
     """benchmark.py:21-91 of the reference: same constructor, CSV layout, skip-if-filled and error-tolerant loop."""
@@ -182,7 +191,19 @@ class Benchmark():
         # load what is already saved
         if os.path.exists(self.file_name):
             exisiting_results = pd.read_csv(self.file_name, index_col='method')
+            # opt-in rows a run before this one saved: update() fills only labels the frame has, and to_csv writes only the frame
+            self._add_rows(name for name in exisiting_results.index if lpca_knn_k(name) is not None)
             self.results.update(exisiting_results)
+
+    def _add_rows(self, names):
+        for name in names:
+            if name not in self.results.index:
+                self.results.loc[name] = np.nan
+
+    def _add_opt_in_rows(self):
+        """The rows of the ``lpca_knn_<k>`` names in ``self.estimators`` (appended after the constructor built the frame of the four
+        defaults), so that the filled-already tests below see them."""
+        self._add_rows(name for name in self.estimators if lpca_knn_k(name) is not None)
 
     def run(self):
         print('--------- STARTING BENCHMARK -----------')
@@ -203,6 +224,9 @@ class Benchmark():
             print(f'------ Benchmarking on dataset {dataset_name} completed --------')
 
     def evaluate_estimator(self, data, estimator_type, dataset_name):
+        knn_k = lpca_knn_k(estimator_type)
+        if knn_k is not None:
+            self._add_rows([estimator_type])                    # an opt-in name: its row is not in the frame of the defaults
         if pd.isna(self.results[dataset_name].loc[estimator_type]):
             print(f'{estimator_type} on {dataset_name} START')
             if estimator_type == 'mle_5':
@@ -213,6 +237,9 @@ class Benchmark():
                 estimated_dim = pca_fo_dim(data)
             elif estimator_type == 'ppca':
                 estimated_dim = ppca_dim(data)
+            elif knn_k is not None:
+                from . import lpca
+                estimated_dim = float(lpca.local_dims(data, knn_k).mean())
             else:
                 raise ValueError(f"unknown estimator {estimator_type!r}")
             self.results.loc[estimator_type, dataset_name] = estimated_dim
@@ -223,6 +250,7 @@ class Benchmark():
 
     def create_dataset(self, dataset_name, config):
         """The train split of the dataset as one [N, D] fp32 tensor on the GPU (moved once per dataset)."""
+        self._add_opt_in_rows()
         if pd.isna(self.results[dataset_name]).any():
             print(f'------ Creating dataset: {dataset_name} --------')
             DataModule = create_lightning_datamodule(config)

@@ -654,6 +654,33 @@ int idiff_ksphere_union_ok(int n, int J, int P);
 int idiff_ksphere_union_score_f32(const float *x, const double *Qcat, const double *comp, const float *sigma, const float *mult,
                                   float *out, int *refused, int B, int n, int J, int P, void *stream);
 
+/* ------------------------------------------------------------------ local PCA: per-point spectrum and tangent basis */
+
+/* Fukunaga-Olsen's estimator in its original, per-point form (the reference reaches it through R's pcaLocalDimEst; no reference
+ * counterpart in code).  Query q has a centre row centre[q] and k neighbour rows idx[q, :] of X [N, D] fp32 (row-major, contiguous);
+ * with m = k + 1 rows in the neighbourhood (the centre and its neighbours), y_j = x_j - x_centre formed in fp64 before any product,
+ * G = Y Y^T (m x m, v_mfma_f64_16x16x4_f64, D streamed through LDS in chunks of idiff_local_pca_chunk() columns) and
+ * B = J G J / (m - 1), J = I - 1 1^T / m, whose non-zero eigenvalues are those of the neighbourhood's sample covariance.  One
+ * workgroup per query solves B by cyclic Jacobi in LDS; nothing [m, D] or [D, D] is written to HBM.  One launch, no host
+ * synchronisation, no allocation, no workspace.
+ *
+ * eig [Q, r] fp64, r = min(k, D): the r largest eigenvalues, descending, clamped at 0 (the others are zero by construction).
+ * basis [Q, n_vec, D] fp64 (NULL allowed only for n_vec = 0; 0 <= n_vec <= r): row v = Y^T J u_v / sqrt((m - 1) lambda_v), the unit
+ * eigenvector of the covariance, its component of largest magnitude positive (lowest index on ties); a row whose eigenvalue is
+ * <= m 2^-52 lambda_1, and every row when lambda_1 = 0, is NaN.
+ * status [Q] int32: 0 converged; 1 the sweep cap was reached with the off-diagonal norm above m 2^-52 ||B||_F (the results are
+ * what the last sweep left); 2 an index of the query lies outside [0, N): THE KERNEL CHECKS every index before it reads a row of X,
+ * so the caller need not; such a query's eig and basis rows are NaN; 3 ||B||_F is not finite (a NaN or Inf among the query's rows, or
+ * an overflow): no sweep is run and eig and basis are NaN or Inf as they fall, never a spectrum to read a dimension from.
+ *
+ * Needs 1 <= N, 1 <= D, 2 <= k <= 64, 0 <= n_vec <= min(k, D), 0 <= Q and non-null pointers (IDIFF_EINVAL otherwise, nothing
+ * launched; Q = 0 is a no-op).  idiff_local_pca_ok (host only) = 1 where the sizes are served.  centre [Q] and idx [Q, k] are
+ * int64, as idiff_knn_f32 writes them. */
+int idiff_local_pca_ok(int N, int D, int k, int n_vec);
+int idiff_local_pca_chunk(void);
+int idiff_local_pca_f64(const float *X, int N, int D, const int64_t *centre, const int64_t *idx, int Q, int k, int n_vec,
+                        double *eig, double *basis, int *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
