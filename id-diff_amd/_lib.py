@@ -146,6 +146,8 @@ _SIGNATURES = {
     "idiff_local_pca_ok": (c_i, [c_i, c_i, c_i, c_i]),
     "idiff_local_pca_chunk": (c_i, []),
     "idiff_local_pca_f64": (c_i, [c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
+    "idiff_empirical_score_ok": (c_i, [c_i64, c_i]),
+    "idiff_empirical_score_f32": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i64, c_i, c_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -1432,3 +1434,64 @@ def ksphere_union_score(x, qcat, comp, sigma, mult=None, out=None, refused=None)
     _check(lib().idiff_ksphere_union_score_f32(x.data_ptr(), qcat.data_ptr(), tab.ctypes.data, sigma.data_ptr(), _ptr(mult), out.data_ptr(),
                                                refused.data_ptr(), B, n, J, P, _stream()), "idiff_ksphere_union_score_f32")
     return out, refused
+
+
+# ------------------------------------------------------------------------------------------- empirical score of a point cloud
+def empirical_score_ok(N, D):
+    """True where empirical_score serves a cloud of N points in R^D (idiff_empirical_score_ok: host only; D <= 192)."""
+    return bool(lib().idiff_empirical_score_ok(int(N), int(D)))
+
+
+def empirical_pack(X):
+    """The cloud X [N, D] (CUDA fp32) as the kernel reads it: ``{"Y", "h", "c", "N", "D"}`` with c [D] the fp64 column mean,
+    Y [N, D4] = X - c in fp64, rows padded with zeros to D4 = 4 ceil(D / 4), and h [N] = |y_i|^2 / 2.  Plain torch fp64 ops on the
+    device, once per cloud; no host sync."""
+    _dev(X, "X")
+    if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+        raise RuntimeError(f"empirical_pack: X must be [N >= 1, D >= 1], got {tuple(X.shape)}")
+    N, D = X.shape
+    Xd = X.double()
+    c = Xd.mean(dim=0).contiguous()
+    Y = torch.zeros(N, (D + 3) // 4 * 4, dtype=torch.float64, device=X.device)
+    Y[:, :D] = Xd - c
+    h = (0.5 * (Y * Y).sum(dim=1)).contiguous()
+    return {"Y": Y, "h": h, "c": c, "N": N, "D": D}
+
+
+def empirical_score(x, pack, sigma, mult=None, out=None, ess=None):
+    """out [B, D] = mult[b] (sum_i w_bi x_i - x_b), w_b = softmax_i(-|x_b - x_i|^2 / (2 sigma_b^2)) over the packed cloud: the score
+    of the cloud's empirical distribution at noise level sigma_b times mult sigma^2, one launch (idiff_empirical_score_f32), fp64
+    throughout, no [B, N] buffer.  x [B, D], sigma [B] and mult [B] (or None) fp32 on the device; ``pack`` from ``empirical_pack``.
+    Returns (out, ess): ess [B] fp32 = 1 / sum_i w_bi^2 (made here when not given).  A row whose x or sigma is not finite, or whose
+    sigma <= 0, is NaN in both.  A shape the kernel does not serve is a RuntimeError before any launch.  No host sync."""
+    _dev(x, "x"); _dev(sigma, "sigma")
+    Y, h, c = _dev(pack["Y"], "pack Y", dtype=torch.float64), _dev(pack["h"], "pack h", dtype=torch.float64), \
+        _dev(pack["c"], "pack c", dtype=torch.float64)
+    N, D = int(pack["N"]), int(pack["D"])
+    if x.ndim != 2 or x.shape[1] != D or sigma.numel() != x.shape[0] or tuple(Y.shape) != (N, (D + 3) // 4 * 4) or h.numel() != N \
+            or c.numel() != D:
+        raise RuntimeError(f"empirical_score: x {tuple(x.shape)}, sigma {tuple(sigma.shape)}, a cloud of {N} points in R^{D} packed as "
+                           f"Y {tuple(Y.shape)}, h {tuple(h.shape)}, c {tuple(c.shape)}")
+    B = x.shape[0]
+    if not empirical_score_ok(N, D):
+        raise RuntimeError(f"empirical_score: N = {N}, D = {D} is not served (idiff_empirical_score_ok): the kernel keeps a row's fp64 "
+                           "output in registers, D <= 192")
+    if mult is not None:
+        _dev(mult, "mult")
+        if mult.numel() != B:
+            raise RuntimeError(f"empirical_score: mult holds {mult.numel()} values for {B} rows")
+    if out is None:
+        out = torch.empty_like(x)
+    _dev(out, "out")
+    if out.shape != x.shape:
+        raise RuntimeError(f"empirical_score: out {tuple(out.shape)} for x {tuple(x.shape)}")
+    if ess is None:
+        ess = torch.empty(B, device=x.device, dtype=torch.float32)
+    _dev(ess, "ess")
+    if ess.numel() != B:
+        raise RuntimeError(f"empirical_score: ess holds {ess.numel()} values for {B} rows")
+    if B == 0:
+        return out, ess
+    _check(lib().idiff_empirical_score_f32(x.data_ptr(), Y.data_ptr(), h.data_ptr(), c.data_ptr(), sigma.data_ptr(), _ptr(mult),
+                                           out.data_ptr(), ess.data_ptr(), B, N, D, _stream()), "idiff_empirical_score_f32")
+    return out, ess

@@ -681,6 +681,26 @@ int idiff_local_pca_chunk(void);
 int idiff_local_pca_f64(const float *X, int N, int D, const int64_t *centre, const int64_t *idx, int Q, int k, int n_vec,
                         double *eig, double *basis, int *status, void *stream);
 
+/* ------------------------------------------------------------------ score of the empirical distribution of a point cloud */
+
+/* The N points x_i of a cloud, each with weight 1 / N, convolved with N(0, sigma^2 I) -- exact for any finite data set, no training:
+ *   w_bi = softmax_i(-|x_b - x_i|^2 / (2 sigma_b^2)),   out[b, :] = mult[b] (sum_i w_bi x_i - x_b),   ess[b] = 1 / sum_i w_bi^2
+ * i.e. mult[b] sigma[b]^2 times the score, and the effective number of points the row's estimate rests on.  The cloud is passed
+ * centred (_lib.empirical_pack): c [D] its fp64 column mean, Y [N, D4] fp64 row-major with D4 = 4 ceil(D / 4) and zero padding,
+ * y_i = x_i - c, and h [N] = |y_i|^2 / 2.  The kernel forms q_b = x_b - c in fp64, the logits (q_b . y_i - h_i) / sigma_b^2 and both
+ * products on v_mfma_f64_16x16x4_f64 with a streamed softmax (csrc/empirical_score.hip); logits and weights stay in registers, there
+ * is no [B, N] buffer and no workspace, and the result is rounded to fp32 once.  One launch, no atomics: the same inputs give the same
+ * bits, and a row's result does not depend on which other rows are in the launch.
+ *
+ * x, out [B, D] fp32; sigma [B] fp32; mult [B] fp32 or NULL (= 1); ess [B] fp32 or NULL; all device pointers, Y 16-byte aligned.
+ * A row whose x is not finite or whose sigma is not a positive finite number is written as NaN (out and ess); no other row is
+ * affected.  IDIFF_EINVAL before any device call for a null pointer (mult and ess excepted), B < 0, N < 1, D < 1 or a shape
+ * idiff_empirical_score_ok (host only) denies: it serves 1 <= D <= 192 (a wave keeps its [16, D] fp64 output and its q tile in
+ * registers) and 1 <= N < 2^31 - 32.  B = 0 is a no-op. */
+int idiff_empirical_score_ok(int64_t N, int D);
+int idiff_empirical_score_f32(const float *x, const double *Y, const double *h, const double *c, const float *sigma, const float *mult,
+                              float *out, float *ess, int B, int64_t N, int D, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
