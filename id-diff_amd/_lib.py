@@ -148,6 +148,8 @@ _SIGNATURES = {
     "idiff_local_pca_f64": (c_i, [c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
     "idiff_empirical_score_ok": (c_i, [c_i64, c_i]),
     "idiff_empirical_score_f32": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i64, c_i, c_p]),
+    "idiff_empirical_jacobian_ok": (c_i, [c_i64, c_i]),
+    "idiff_empirical_jacobian_f64": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i64, c_i, c_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -1495,3 +1497,67 @@ def empirical_score(x, pack, sigma, mult=None, out=None, ess=None):
     _check(lib().idiff_empirical_score_f32(x.data_ptr(), Y.data_ptr(), h.data_ptr(), c.data_ptr(), sigma.data_ptr(), _ptr(mult),
                                            out.data_ptr(), ess.data_ptr(), B, N, D, _stream()), "idiff_empirical_score_f32")
     return out, ess
+
+
+# ------------------------------------------------------------------------------------------- Jacobian of the empirical score
+JACOBIAN_D_MAX = 192          # idiff_empirical_jacobian_ok: the upper blocks of one query's C live in a workgroup's registers
+EIGVALS_BATCH_MAX = 65535     # matrices idiff_tridiag_eigvals_f64 takes per call
+
+
+def empirical_jacobian_ok(N, D):
+    """True where empirical_jacobian serves a cloud of N points in R^D (idiff_empirical_jacobian_ok: host only; D <= 192)."""
+    return bool(lib().idiff_empirical_jacobian_ok(int(N), int(D)))
+
+
+def empirical_jacobian(x, X, sigma, C=None, mean=None, ess=None):
+    """``(C [B, D, D] fp64, mean [B, D] fp64, ess [B] fp32)`` for the queries (x_b, sigma_b) against the RAW cloud X [N, D] (CUDA
+    fp32, not the pack): with d_i = x_i - x_b and w_b = softmax_i(-|d_i|^2 / (2 sigma_b^2)), mean = sum_i w_i d_i (the score times
+    sigma^2), C = sum_i w_i (d_i - mean)(d_i - mean)^T / sigma_b^2 = I + sigma_b^2 times the Jacobian of the score (symmetric to the
+    bit) and ess = 1 / sum_i w_i^2.  One launch (idiff_empirical_jacobian_f64), fp64 throughout, no workspace.  x [B, D] and sigma [B]
+    fp32 on the device; the outputs are made here when not given.  A query whose x or sigma is not finite, or whose sigma <= 0, is
+    NaN in all three.  A shape the kernel does not serve is a RuntimeError before any launch.  No host sync."""
+    _dev(x, "x"); _dev(X, "X"); _dev(sigma, "sigma")
+    if X.ndim != 2 or x.ndim != 2 or x.shape[1] != X.shape[1] or sigma.numel() != x.shape[0]:
+        raise RuntimeError(f"empirical_jacobian: x {tuple(x.shape)}, sigma {tuple(sigma.shape)}, X {tuple(X.shape)}")
+    (B, D), N = x.shape, X.shape[0]
+    if not empirical_jacobian_ok(N, D):
+        raise RuntimeError(f"empirical_jacobian: N = {N}, D = {D} is not served (idiff_empirical_jacobian_ok): a workgroup keeps the "
+                           f"upper triangle of a query's fp64 C in registers, 1 <= D <= {JACOBIAN_D_MAX}, 1 <= N")
+    if C is None:
+        C = torch.empty(B, D, D, device=x.device, dtype=torch.float64)
+    if mean is None:
+        mean = torch.empty(B, D, device=x.device, dtype=torch.float64)
+    if ess is None:
+        ess = torch.empty(B, device=x.device, dtype=torch.float32)
+    _dev(C, "C", dtype=torch.float64); _dev(mean, "mean", dtype=torch.float64); _dev(ess, "ess")
+    if tuple(C.shape) != (B, D, D) or tuple(mean.shape) != (B, D) or ess.numel() != B:
+        raise RuntimeError(f"empirical_jacobian: C {tuple(C.shape)}, mean {tuple(mean.shape)}, ess {tuple(ess.shape)} for x {tuple(x.shape)}")
+    if B == 0:
+        return C, mean, ess
+    _check(lib().idiff_empirical_jacobian_f64(x.data_ptr(), X.data_ptr(), sigma.data_ptr(), C.data_ptr(), mean.data_ptr(), ess.data_ptr(),
+                                              B, N, D, _stream()), "idiff_empirical_jacobian_f64")
+    return C, mean, ess
+
+
+def sym_eigvals_batched(G):
+    """Eigenvalues [P, D] (ascending, fp64) of P symmetric fp64 matrices G [P, D, D]; G is overwritten.  ``sym_eigvals`` with the P
+    argument of idiff_symtridiag_f64 / idiff_tridiag_eigvals_f64: for D <= 128 one workgroup per matrix in one launch, above that
+    the C side takes the matrices in turn over one scratch.  At most 65535 matrices a call, so more go in chunks.  No host sync."""
+    _dev(G, "G", dtype=torch.float64)
+    if G.ndim != 3 or G.shape[1] != G.shape[2] or G.shape[1] < 1:
+        raise RuntimeError(f"sym_eigvals_batched: G must be [P, D >= 1, D], got {tuple(G.shape)}")
+    P, D = G.shape[0], G.shape[1]
+    eig = torch.empty(P, D, dtype=torch.float64, device=G.device)
+    if P == 0:
+        return eig
+    chunk = min(P, EIGVALS_BATCH_MAX)
+    diag = torch.empty(chunk, D, dtype=torch.float64, device=G.device)
+    offd = torch.empty(chunk, D, dtype=torch.float64, device=G.device)
+    scratch = torch.empty(max(1, lib().idiff_symtridiag_scratch_doubles(D)), dtype=torch.float64, device=G.device)
+    for lo in range(0, P, chunk):
+        n = min(chunk, P - lo)
+        _check(lib().idiff_symtridiag_f64(G[lo:lo + n].data_ptr(), n, D, diag.data_ptr(), offd.data_ptr(), scratch.data_ptr(), _stream()),
+               "idiff_symtridiag_f64")
+        _check(lib().idiff_tridiag_eigvals_f64(diag.data_ptr(), offd.data_ptr(), n, D, eig[lo:lo + n].data_ptr(), _stream()),
+               "idiff_tridiag_eigvals_f64")
+    return eig

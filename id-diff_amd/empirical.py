@@ -8,6 +8,13 @@ kernel (csrc/empirical_score.hip) many points a launch, ``_lib.spectrum`` gives 
 reads the dimension off the largest gap.  ``sigma`` is the kernel bandwidth (``model.sigma_min`` of a config): the estimate means
 something only where the effective sample size of the rows is well above 1, so the median ESS of every point is returned beside its
 dimension.  A sample-based score needs N to grow exponentially in the intrinsic dimension; see the model's docstring.
+
+The second half of the module needs no sampling: the Jacobian of the empirical score has a closed form, I + sigma^2 grad s(x) = C(x,
+sigma), the softmax-weighted covariance of the cloud seen from x in units of sigma^2 (csrc/empirical_jacobian.hip).  The driver's
+centred score matrix estimates |1 - eig(C)| with Monte-Carlo noise; ``jacobian_spectra`` gives eig(C) itself for many points at many
+bandwidths a launch, ``dims_from_jacobian`` reads the dimension off it (tangent eigenvalues are near 1, normal ones near 0), and
+``scale_curve`` / ``stable_dims`` find the range of bandwidths over which that dimension holds -- the range ``sigma_from_knn`` only
+asks the user to look for.
 """
 import os
 import pickle
@@ -46,6 +53,11 @@ def _setup(X, sigma, points):
     sde, eps = sde_lib.configure_sde(cfg)
     score_fn = mutils.get_score_fn(sde, model, conditional=False, train=False, continuous=True)
     builder = dim_reduction.ScoreMatrixBuilder(score_fn, sde, eps, Xd.device)
+    return model, builder, _select(Xd, points)
+
+
+def _select(Xd, points):
+    """xs [P, D] on the device: the first 100 rows of the cloud (None), its rows ``points`` (integers) or ``points`` themselves."""
     if points is None:
         xs = Xd[:100]
     else:
@@ -58,7 +70,7 @@ def _setup(X, sigma, points):
             xs = _points(pts.reshape(-1, Xd.shape[1]) if pts.ndim >= 1 else pts)
             if xs.shape[1] != Xd.shape[1]:
                 raise ValueError(f"points {tuple(pts.shape)} for a cloud in R^{Xd.shape[1]}")
-    return model, builder, xs.contiguous()
+    return xs.contiguous()
 
 
 def _groups(model, builder, xs, batchsize, seed):
@@ -117,12 +129,162 @@ def sigma_from_knn(X, k=20):
     return sigma_rule(dist[:, k - 1].cpu().numpy())
 
 
+# ------------------------------------------------------------------------------------------- the Jacobian in closed form
+ESS_MIN = 32.0                 # a HEURISTIC: the largest ESS of a wrong fp64 reading on the test clouds is 19.8
+JACOBIAN_RULES = ('half', 'gap')
+C_BYTES_PER_LAUNCH = 256 << 20
+
+
+def _sigmas(sigmas):
+    sg = np.atleast_1d(np.asarray(sigmas, dtype=np.float64)).ravel()
+    if not sg.size or not (np.isfinite(sg).all() and (sg > 0.0).all()):
+        raise ValueError(f"sigmas must be positive and finite, got {sg.tolist()}")
+    return sg
+
+
+def _jacobians(Xd, xs, sg):
+    """Yields (first query, C [Q', D, D], mean [Q', D], ess [Q']) launch by launch; query p S + s is point p at bandwidth sg[s], and a
+    launch's C stays under C_BYTES_PER_LAUNCH."""
+    P, D, S = xs.shape[0], xs.shape[1], len(sg)
+    xq = xs.repeat_interleave(S, dim=0)
+    sq = torch.from_numpy(sg.astype(np.float32)).to(xs.device).repeat(P)
+    step = max(1, C_BYTES_PER_LAUNCH // (8 * D * D))
+    for lo in range(0, P * S, step):
+        yield (lo,) + _lib.empirical_jacobian(xq[lo:lo + step].contiguous(), Xd, sq[lo:lo + step].contiguous())
+
+
+def jacobian_spectra(X, sigmas, points=None):
+    """``(eig [P, S, D] fp64, ess [P, S] fp64)`` numpy: the eigenvalues, DESCENDING, of C(x, sigma) = I + sigma^2 grad s(x) of the
+    cloud X [N, D] at every listed point (``points`` as in ``local_dims``) and every bandwidth of ``sigmas`` [S], and the effective
+    sample size of each.  No sampling: ``_lib.empirical_jacobian`` forms C in fp64 from the raw cloud, many (point, sigma) queries a
+    launch, and ``_lib.sym_eigvals_batched`` takes its eigenvalues.  The cloud goes to the device once."""
+    sg = _sigmas(sigmas)
+    Xd = _points(X)
+    xs = _select(Xd, points)
+    P, D, S = xs.shape[0], xs.shape[1], len(sg)
+    eig = torch.empty(P * S, D, dtype=torch.float64, device=Xd.device)
+    ess = torch.empty(P * S, dtype=torch.float32, device=Xd.device)
+    for lo, C, _, e in _jacobians(Xd, xs, sg):
+        eig[lo:lo + C.shape[0]] = _lib.sym_eigvals_batched(C)
+        ess[lo:lo + C.shape[0]] = e
+    return eig.flip(1).cpu().numpy().reshape(P, S, D), ess.double().cpu().numpy().reshape(P, S)
+
+
+def dims_from_jacobian(eig, rule='half'):
+    """int64 [...] from eig [..., D] (descending eigenvalues of C): 'half' the number of eigenvalues above 0.5, the midpoint between
+    a tangent direction (1) and a normal one (0); 'gap' 1 + argmax(lambda_j - lambda_(j+1)).  (``plot_utils.estimate_dim`` divides
+    by the second gap, which is exactly zero for a cloud that does not span R^D.)  A spectrum that is not finite raises
+    ``ValueError``."""
+    eig = np.asarray(eig, dtype=np.float64)
+    if eig.ndim < 1 or eig.shape[-1] < 1:
+        raise ValueError(f"eig must be [..., D >= 1], got {eig.shape}")
+    if rule not in JACOBIAN_RULES:
+        raise ValueError(f"unknown rule {rule!r} {JACOBIAN_RULES}")
+    if not np.isfinite(eig).all():
+        raise ValueError(f"{int((~np.isfinite(eig)).any(axis=-1).sum())} of {eig[..., 0].size} spectra are not finite")
+    if rule == 'half':
+        return (eig > 0.5).sum(axis=-1).astype(np.int64)
+    if eig.shape[-1] < 2:
+        return np.ones(eig.shape[:-1], dtype=np.int64)
+    return (1 + np.argmax(eig[..., :-1] - eig[..., 1:], axis=-1)).astype(np.int64)
+
+
+def sigma_grid(X, k=20, lo=-2.0, hi=3.0, per_octave=2):
+    """``sigma_from_knn(X, k) 2^(j / per_octave)`` for the integers j with lo <= j / per_octave <= hi, ascending: 11 bandwidths from
+    a quarter of the heuristic value to eight times it by default."""
+    j = np.arange(int(np.ceil(lo * per_octave - 1e-9)), int(np.floor(hi * per_octave + 1e-9)) + 1)
+    return sigma_from_knn(X, k) * 2.0 ** (j / float(per_octave))
+
+
+def stable_dims(dims, ess, sigmas, ess_min=ESS_MIN):
+    """``(dim [P] int64, range [P, 2])`` from dims [P, S], ess [P, S] and the grid sigmas [S] (host only): of the bandwidths with
+    ess >= ess_min, the longest run of consecutive grid positions with one and the same dimension -- a tie goes to the run at the
+    smaller sigma -- gives the point's dimension and the run's (first, last) sigma.  -1 and (nan, nan) where no bandwidth qualifies."""
+    dims, ess, sg = np.asarray(dims), np.asarray(ess, dtype=np.float64), np.asarray(sigmas, dtype=np.float64).ravel()
+    if dims.ndim != 2 or dims.shape != ess.shape or dims.shape[1] != sg.size:
+        raise ValueError(f"dims {dims.shape}, ess {ess.shape}, sigmas {sg.shape}")
+    out = np.full(dims.shape[0], -1, dtype=np.int64)
+    rng = np.full((dims.shape[0], 2), np.nan)
+    for p in range(dims.shape[0]):
+        best, s = None, 0                                                 # (length, first, last)
+        while s < sg.size:
+            if not ess[p, s] >= ess_min:
+                s += 1
+                continue
+            e = s
+            while e + 1 < sg.size and ess[p, e + 1] >= ess_min and dims[p, e + 1] == dims[p, s]:
+                e += 1
+            if best is None or e - s + 1 > best[0] or (e - s + 1 == best[0] and sg[s] < sg[best[1]]):
+                best = (e - s + 1, s, e)
+            s = e + 1
+        if best is not None:
+            out[p], rng[p] = dims[p, best[1]], (sg[best[1]], sg[best[2]])
+    return out, rng
+
+
+def scale_curve(X, sigmas=None, points=None, rule='half'):
+    """The dimension of every listed point at every bandwidth (default: ``sigma_grid(X)``) and where it is stable:
+    {'sigmas' [S], 'dims' [P, S], 'ess' [P, S], 'eigenvalues' [P, S, D], 'stable_dims' [P], 'stable_range' [P, 2]}."""
+    Xd = _points(X)
+    sg = sigma_grid(Xd) if sigmas is None else _sigmas(sigmas)
+    eig, ess = jacobian_spectra(Xd, sg, points=points)
+    dims = dims_from_jacobian(eig, rule)
+    stable, rng = stable_dims(dims, ess, sg)
+    return {'sigmas': sg, 'dims': dims, 'ess': ess, 'eigenvalues': eig, 'stable_dims': stable, 'stable_range': rng}
+
+
+def jacobian_tangent(X, sigma, points=None, rule='half', dtype=np.float32):
+    """One float32 numpy array [D, d] per listed point, in the layout of ``local_tangent``: the d leading eigenvectors of C(x, sigma),
+    d the point's dimension by ``rule``; None where d < 1, d > ``_lib.TANGENT_MAX`` or d >= D.  (``dtype=np.float64`` keeps the vectors
+    as computed: rounding an exact basis to float32 alone turns it by about 3e-8.)  C comes from the kernel; the vectors
+    from ``numpy.linalg.eigh`` on the host, a matter of milliseconds for a hundred matrices of D <= 192.  The device eigenvector
+    kernels do not fit: ``_lib.sym_lowvecs`` wants the eigenvalues it returns at the BOTTOM of a positive definite matrix (here they
+    are at the top, and I - C is not definite), and ``_lib.sym_topvecs`` is planned for kernel matrices of thousands of rows."""
+    sg = _sigmas(sigma)
+    if sg.size != 1:
+        raise ValueError(f"one bandwidth expected, got {sg.tolist()}")
+    Xd = _points(X)
+    xs = _select(Xd, points)
+    D = xs.shape[1]
+    out = []
+    for _, C, _, _ in _jacobians(Xd, xs, sg):
+        lam, vec = np.linalg.eigh(C.cpu().numpy())                        # ascending
+        for d, V in zip(dims_from_jacobian(lam[:, ::-1], rule), vec):
+            out.append(None if d < 1 or d > _lib.TANGENT_MAX or d >= D else np.ascontiguousarray(V[:, ::-1][:, :d], dtype=dtype))
+    return out
+
+
 # ------------------------------------------------------------------------------------------- a data set from a config
-def run(config, sigma=None, points=None, out_dir='empirical'):
+def _histogram(dims):
+    for v, c in zip(*np.unique(dims, return_counts=True)):
+        print(f'  dim {int(v):3d}: {int(c)}')
+
+
+def run_sweep(X, sigmas=None, points=None, out_dir='empirical', rule='half'):
+    """``scale_curve`` of the cloud into ``out_dir/scale_curve.pkl`` (the curve's dict plus 'rule'); prints the histogram of the
+    dimensions and the median ESS at every bandwidth, then the histogram of the stable dimensions.  -> the dict."""
+    curve = scale_curve(X, sigmas=sigmas, points=points, rule=rule)
+    curve['rule'] = rule
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, 'scale_curve.pkl'), 'wb') as f:
+        pickle.dump(curve, f)
+    print(f"empirical score Jacobian (rule {rule!r}) on {curve['dims'].shape[0]} of {X.shape[0]} points, {len(curve['sigmas'])} bandwidths")
+    for s, sigma in enumerate(curve['sigmas']):
+        print(f" sigma = {sigma:.4g}: median ESS {np.median(curve['ess'][:, s]):.1f}")
+        _histogram(curve['dims'][:, s])
+    print(f" stable over the bandwidths with ESS >= {ESS_MIN:g} (-1: none qualifies):")
+    _histogram(curve['stable_dims'])
+    return curve
+
+
+def run(config, sigma=None, points=None, out_dir='empirical', sweep=False, sigmas=None):
     """The train split of the config's data set (as the driver splits it) -> the diffusion ID of its first 100 points (or
     ``points``) at bandwidth ``sigma`` (default: ``sigma_from_knn``) into ``out_dir/local_dims.pkl`` = {'dims', 'ess_median',
-    'sigma', 'batchsize'}; prints the histogram of the dimensions.  -> dims."""
+    'sigma', 'batchsize'}; prints the histogram of the dimensions.  -> dims.  ``sweep=True`` takes the sampling-free path instead
+    (``run_sweep`` over ``sigmas``, default ``sigma_grid``): ``out_dir/scale_curve.pkl``, -> its dict."""
     X = _points(train_split(config))
+    if sweep:
+        return run_sweep(X, sigmas=sigmas, points=points, out_dir=out_dir)
     sigma = sigma_from_knn(X) if sigma is None else float(sigma)
     batchsize = int(config.training.batch_size)
     dims, ess = local_dims(X, sigma, points=points, batchsize=batchsize, seed=int(config.get('seed', 42)))
@@ -144,8 +306,11 @@ def main(argv=None):
     ap.add_argument('--config', required=True)
     ap.add_argument('--sigma', type=float, default=None)
     ap.add_argument('--out_dir', default='empirical')
+    ap.add_argument('--sweep', action='store_true', help="the sampling-free scale curve (scale_curve.pkl) instead of one bandwidth")
+    ap.add_argument('--sigmas', default=None, help="comma-separated bandwidths of --sweep (default: sigma_grid)")
     args = ap.parse_args(argv)
-    run(read_config(args.config), sigma=args.sigma, out_dir=args.out_dir)
+    sigmas = None if args.sigmas is None else [float(v) for v in args.sigmas.split(',')]
+    run(read_config(args.config), sigma=args.sigma, out_dir=args.out_dir, sweep=args.sweep, sigmas=sigmas)
 
 
 if __name__ == '__main__':

@@ -701,6 +701,25 @@ int idiff_empirical_score_ok(int64_t N, int D);
 int idiff_empirical_score_f32(const float *x, const double *Y, const double *h, const double *c, const float *sigma, const float *mult,
                               float *out, float *ess, int B, int64_t N, int D, void *stream);
 
+/* The Jacobian of that score in closed form, no sampling: with d_i = x_i - x_b, w_bi as above and m_b = sum_i w_bi d_i,
+ *   I + sigma_b^2 grad s(x_b)  =  C[b]  :=  sum_i w_bi (d_i - m_b)(d_i - m_b)^T / sigma_b^2
+ * the softmax-weighted covariance of the cloud seen from x_b in units of sigma_b^2: eigenvalues near 1 along the tangent, near 0 along
+ * the normal.  A query is a (point, sigma) pair; a launch mixes points and bandwidths freely.  X [N, D] is the RAW fp32 cloud (not the
+ * fp64 pack): d = (double)x_i - (double)x_b is one rounding and does not depend on the cloud's offset.  One workgroup per query, two
+ * passes over the cloud in one launch (the largest logit; then every logit recomputed by the same instructions, w = exp(l - max), no
+ * rescaling), sum w d d^T on v_mfma_f64_16x16x4_f64 over the 16 x 16 blocks of the upper triangle, mirrored at the store: C[b] is
+ * symmetric to the bit (csrc/empirical_jacobian.hip).  No atomics, no workspace: the same inputs give the same bits, and a query's
+ * result does not depend on which other queries share its launch.
+ *
+ * x [B, D], sigma [B] fp32; C [B, D, D] fp64, both triangles; mean [B, D] fp64 = sum_i w_bi d_i; ess [B] fp32 = 1 / sum_i w_bi^2; all
+ * device pointers, all required.  A query whose x is not finite or whose sigma is not a positive finite number is written as NaN in
+ * all three outputs; no other query is affected.  IDIFF_EINVAL before any device call for a null or misaligned pointer, B < 0, N < 1,
+ * D < 1 or a shape idiff_empirical_jacobian_ok (host only) denies: it serves 1 <= D <= 192 (the four waves of a workgroup keep the 78
+ * upper blocks of C in registers) and 1 <= N < 2^31 - 32.  B = 0 is a no-op. */
+int idiff_empirical_jacobian_ok(int64_t N, int D);
+int idiff_empirical_jacobian_f64(const float *x, const float *X, const float *sigma, double *C, double *mean, float *ess,
+                                 int B, int64_t N, int D, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
