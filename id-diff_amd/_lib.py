@@ -150,6 +150,14 @@ _SIGNATURES = {
     "idiff_empirical_score_f32": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i64, c_i, c_p]),
     "idiff_empirical_jacobian_ok": (c_i, [c_i64, c_i]),
     "idiff_empirical_jacobian_f64": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i64, c_i, c_p]),
+    "idiff_gemm_nn_ok": (c_i, [c_i, c_i, c_i]),
+    "idiff_gemm_nn_f32": (c_i, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i, c_i, c_i, c_p]),
+    "idiff_gemm_tn_ok": (c_i, [c_i, c_i, c_i]),
+    "idiff_gemm_tn_f32": (c_i, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i, c_i, c_i, c_p]),
+    "idiff_dsm_loss_grad_f32": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_i, c_i, c_i, c_p]),
+    "idiff_grad_sumsq_f32": (c_i, [c_p, c_i64, c_p, c_p, c_p]),
+    "idiff_adam_step_f32": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_p, c_d, c_d, c_d, c_d, c_d, c_d, c_i64, c_p]),
+    "idiff_fcn_train_input_f32": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -1561,3 +1569,134 @@ def sym_eigvals_batched(G):
         _check(lib().idiff_tridiag_eigvals_f64(diag.data_ptr(), offd.data_ptr(), n, D, eig[lo:lo + n].data_ptr(), _stream()),
                "idiff_tridiag_eigvals_f64")
     return eig
+
+
+# ------------------------------------------------------------------------------------------- training the fcn score network
+REDUCE_WS_DOUBLES = 1024      # IDIFF_REDUCE_WS_DOUBLES: workspace of the two fixed-order reductions
+
+
+def _ld(t, name):
+    if t.ndim != 2 or t.stride(1) != 1:
+        raise RuntimeError(f"{name}: expected a 2-D tensor with contiguous rows, got shape {tuple(t.shape)} strides {t.stride()}")
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), (t.shape[1] + 3) // 4 * 4)
+
+
+def gemm_nn(a, bm, out=None, elu_out=None, M=None, N=None, K=None, lda=None, ldb=None, ldc=None, ldp=None):
+    """out[M, N] = (a[M, K] @ bm[K, N]) * g(elu_out): the data gradient of a Linear layer through the ELU below it, with ``bm`` the
+    weight [out, in] as it lies and ``elu_out`` [M, N] (optional) that ELU's OUTPUT, g(a) = 1 if a > 0 else a + 1.  2-D tensors with
+    contiguous rows (a row stride is the leading dimension), or explicit geometry.  Exact fp32 on the matrix cores, bit-reproducible."""
+    _dev(a, "a", contiguous=False); _dev(bm, "bm", contiguous=False)
+    if M is None:
+        (M, K), N = a.shape, bm.shape[1]
+        if bm.shape[0] != K:
+            raise RuntimeError(f"gemm_nn: inner dimensions differ: {tuple(a.shape)} x {tuple(bm.shape)}")
+        lda, ldb = _ld(a, "a"), _ld(bm, "bm")
+    if out is None:
+        out = torch.empty(M, N, device=a.device, dtype=torch.float32)
+    _dev(out, "out", contiguous=False)
+    if ldc is None:
+        ldc = _ld(out, "out")
+    if elu_out is not None:
+        _dev(elu_out, "elu_out", contiguous=False)
+        if ldp is None:
+            ldp = _ld(elu_out, "elu_out")
+    _check(lib().idiff_gemm_nn_f32(a.data_ptr(), lda, bm.data_ptr(), ldb, out.data_ptr(), ldc, _ptr(elu_out), ldp or 0, M, N, K,
+                                   _stream()), "idiff_gemm_nn_f32")
+    return out
+
+
+def gemm_tn(at, bm, out=None, colsum=None, M=None, N=None, K=None, lda=None, ldb=None, ldc=None):
+    """out[M, N] = at[K, M].T @ bm[K, N] (the weight gradient: K is the batch) and, with ``colsum`` [M], colsum[m] = sum_k at[k, m] in
+    the order k = 0, 1, ... (the bias gradient).  Geometry as gemm_nn.  Exact fp32 on the matrix cores, bit-reproducible."""
+    _dev(at, "at", contiguous=False); _dev(bm, "bm", contiguous=False)
+    if M is None:
+        (K, M), N = at.shape, bm.shape[1]
+        if bm.shape[0] != K:
+            raise RuntimeError(f"gemm_tn: inner dimensions differ: {tuple(at.shape)}^T x {tuple(bm.shape)}")
+        lda, ldb = _ld(at, "at"), _ld(bm, "bm")
+    if out is None:
+        out = torch.empty(M, N, device=at.device, dtype=torch.float32)
+    _dev(out, "out", contiguous=False)
+    if ldc is None:
+        ldc = _ld(out, "out")
+    if colsum is not None:
+        _dev(colsum, "colsum")
+        if colsum.numel() != M:
+            raise RuntimeError(f"gemm_tn: colsum has {colsum.numel()} entries for M = {M}")
+    _check(lib().idiff_gemm_tn_f32(at.data_ptr(), lda, bm.data_ptr(), ldb, out.data_ptr(), ldc, _ptr(colsum), M, N, K, _stream()),
+           "idiff_gemm_tn_f32")
+    return out
+
+
+def reduce_workspace(device):
+    return torch.empty(REDUCE_WS_DOUBLES, device=device, dtype=torch.float64)
+
+
+def dsm_loss_grad(out, z, weight=None, reduce_mean=True, grad=None, loss=None, want_grad=True, workspace=None):
+    """``(loss, G)``: the denoising score matching loss mean_b weight[b] reduce_d (z - out)^2 (reduce = mean, or half the sum) as a
+    device float summed in fp64 in a fixed order, and G = dloss/dout (None with ``want_grad=False``: the evaluation loss).  A given ``grad`` may be wider than D columns (its row stride
+    is the pitch; the columns beyond D are left alone)."""
+    _dev(out, "out"); _dev(z, "z")
+    if out.ndim != 2 or out.shape != z.shape:
+        raise RuntimeError(f"dsm_loss_grad: out {tuple(out.shape)}, z {tuple(z.shape)}")
+    B, D = out.shape
+    if weight is not None:
+        _dev(weight, "weight")
+        if weight.numel() != B:
+            raise RuntimeError(f"dsm_loss_grad: weight has {weight.numel()} entries for {B} rows")
+    if want_grad and grad is None:
+        grad = torch.empty_like(out)
+    ldg = 0
+    if grad is not None:
+        _dev(grad, "grad", contiguous=False)
+        if grad.ndim != 2 or grad.shape[0] != B or grad.shape[1] < D or grad.stride(1) != 1:
+            raise RuntimeError(f"dsm_loss_grad: grad {tuple(grad.shape)} for out {tuple(out.shape)}")
+        ldg = grad.stride(0) if B > 1 else max(grad.stride(0), D)
+    if loss is None:
+        loss = torch.empty((), device=out.device, dtype=torch.float32)
+    if workspace is None:
+        workspace = reduce_workspace(out.device)
+    _dev(loss, "loss"); _dev(workspace, "workspace", dtype=torch.float64)
+    _check(lib().idiff_dsm_loss_grad_f32(out.data_ptr(), z.data_ptr(), _ptr(weight), _ptr(grad), ldg, loss.data_ptr(), workspace.data_ptr(),
+                                         B, D, int(bool(reduce_mean)), _stream()), "idiff_dsm_loss_grad_f32")
+    return loss, grad
+
+
+def grad_sumsq(x, out=None, workspace=None):
+    """Device double: sum of squares of the flat fp32 tensor ``x`` in fp64, fixed order."""
+    _dev(x, "x")
+    if out is None:
+        out = torch.empty((), device=x.device, dtype=torch.float64)
+    if workspace is None:
+        workspace = reduce_workspace(x.device)
+    _dev(out, "out", dtype=torch.float64); _dev(workspace, "workspace", dtype=torch.float64)
+    _check(lib().idiff_grad_sumsq_f32(x.data_ptr(), x.numel(), workspace.data_ptr(), out.data_ptr(), _stream()), "idiff_grad_sumsq_f32")
+    return out
+
+
+def adam_step(theta, grad, m, v, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, sumsq=None, max_norm=0.0):
+    """One torch.optim.Adam step over the flat buffers, in place in theta, m, v; ``step`` >= 1 numbers this step.  With ``sumsq`` (the
+    device double of grad_sumsq) the gradient is first scaled by min(1, max_norm / (sqrt(sumsq) + 1e-6)) as clip_grad_norm_ does."""
+    for t, name in ((theta, "theta"), (grad, "grad"), (m, "m"), (v, "v")):
+        _dev(t, name)
+        if t.numel() != theta.numel():
+            raise RuntimeError(f"adam_step: {name} has {t.numel()} entries, theta {theta.numel()}")
+    if sumsq is not None:
+        _dev(sumsq, "sumsq", dtype=torch.float64)
+    _check(lib().idiff_adam_step_f32(theta.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(), theta.numel(), _ptr(sumsq),
+                                     float(max_norm), float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
+                                     int(step), _stream()), "idiff_adam_step_f32")
+
+
+def fcn_train_input(x, z, std, mean_coeff, label, h):
+    """h[b] = [mean_coeff[b] x[b] + std[b] z[b], label[b], 0 ...]: the padded input rows [B, kpad] of the fcn for a training batch."""
+    _dev(x, "x"); _dev(z, "z"); _dev(std, "std"); _dev(label, "label"); _dev(h, "h")
+    if mean_coeff is not None:
+        _dev(mean_coeff, "mean_coeff")
+    B, D = x.shape
+    if z.shape != x.shape or h.ndim != 2 or h.shape[0] != B or std.numel() != B or label.numel() != B or \
+            (mean_coeff is not None and mean_coeff.numel() != B):
+        raise RuntimeError(f"fcn_train_input: x {tuple(x.shape)}, z {tuple(z.shape)}, std {tuple(std.shape)}, h {tuple(h.shape)}")
+    _check(lib().idiff_fcn_train_input_f32(x.data_ptr(), z.data_ptr(), std.data_ptr(), _ptr(mean_coeff), label.data_ptr(), h.data_ptr(),
+                                           B, D, h.shape[1], _stream()), "idiff_fcn_train_input_f32")
+    return h

@@ -1,6 +1,10 @@
 """CLI drop-in for ``python main.py --config <cfg.py|cfg.pkl> --mode manifold_dimension [--checkpoint_path ...]``
 (/root/reference/main.py:17-71; absl is not installable here, argparse accepts the same flags incl. ``--flag=value``).
 
+``--mode train --n_iters N`` trains the ``fcn`` score network of a Euclidean config on one GPU (train.py) and writes
+``<log_path>/<log_name>/checkpoints/last.ckpt``, which ``--mode manifold_dimension --checkpoint_path`` then reads;
+``--checkpoint_path`` with ``--mode train`` resumes.
+
 Run it from the repo root as ``python id-diff_amd/main.py ...`` or, for several GPUs of one node,
 ``python -m torch.distributed.run --nproc-per-node N id-diff_amd/main.py ...``.
 
@@ -40,7 +44,25 @@ def parse(argv=None):
                          "equal WORLD_SIZE")
     ap.add_argument("--allow_random_init", action="store_true",
                     help="run on freshly initialised weights when no checkpoint is given (timing / plumbing only)")
+    ap.add_argument("--n_iters", type=float, default=None,
+                    help="(--mode train) train until this many optimiser steps have been taken in total (the configs say 1e20)")
+    ap.add_argument("--log_every", type=int, default=0, help="(--mode train) fetch and print the loss every this many steps")
+    ap.add_argument("--checkpoint_every", type=int, default=0, help="(--mode train) also write last.ckpt every this many steps")
     return ap.parse_args(argv)
+
+
+def run_train(flags, config):
+    from id_diff_amd import train as _train
+    _train.check_scope(config)           # before anything touches the GPU: another network exits with the scope message
+    if flags.gpus is not None and flags.gpus > 1:
+        raise SystemExit("--mode train runs on one GPU: --gpus must be 1 (or left out)")
+    if flags.n_iters is None:
+        raise SystemExit("--mode train needs --n_iters (the reference's configs train for 1e20 steps)")
+    if flags.n_iters < 0 or flags.log_every < 0 or flags.checkpoint_every < 0:
+        raise SystemExit("--n_iters, --log_every and --checkpoint_every must not be negative")
+    log_path = flags.log_path if flags.log_path != "./" or not config.logging.get("log_path") else config.logging.log_path
+    return run_lib.train(config, log_path=log_path, checkpoint_path=config.model.get("checkpoint_path"), n_iters=flags.n_iters,
+                         log_every=flags.log_every, checkpoint_every=flags.checkpoint_every, log_name=flags.log_name)
 
 
 def main(argv=None):
@@ -55,9 +77,13 @@ def main(argv=None):
         config.model.checkpoint_path = flags.checkpoint_path
     if flags.allow_random_init:
         config.model.allow_random_init = True
+    if flags.mode == 'train':
+        run_train(flags, config)
+        return
     if flags.mode not in _HOT_MODES:
         raise SystemExit(f"mode {flags.mode!r} is outside the scope of id-diff_amd (the MI355X build covers "
-                         f"{', '.join(_HOT_MODES)}); use the reference for training / sampling / evaluation")
+                         f"{', '.join(_HOT_MODES)}, and train for the fcn score network); use the reference for "
+                         "sampling / evaluation and for training any other network")
     if flags.gpus is not None:
         need_devices = not str(getattr(config, "device", "cuda")).startswith("cpu")     # the same answer in the launcher and in the ranks
         if flags.gpus > 1 and not parallel.launched():

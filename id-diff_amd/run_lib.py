@@ -1,4 +1,5 @@
-"""Dispatch layer (the two lines of /root/reference/run_lib.py:324-328 that are on the hot path)."""
+"""Dispatch layer (the two lines of /root/reference/run_lib.py:324-328 that are on the hot path, and ``train`` of :37-71 for the
+fcn score network)."""
 from . import dim_reduction
 
 
@@ -8,3 +9,11 @@ def get_manifold_dimension(config, name=None):
 
 def get_conditional_manifold_dimension(config, name=None):
     dim_reduction.get_conditional_manifold_dimension(config, name)
+
+
+def train(config, log_path=None, checkpoint_path=None, n_iters=None, log_every=0, checkpoint_every=0, log_name=None):
+    """Train the fcn score network (train.py); resumes when ``checkpoint_path`` or ``config.model.checkpoint_path`` is set and writes
+    ``<log_path>/<log_name>/checkpoints/last.ckpt``."""
+    from . import train as _train
+    return _train.train(config, log_path=log_path, checkpoint_path=checkpoint_path, n_iters=n_iters, log_every=log_every,
+                        checkpoint_every=checkpoint_every, log_name=log_name)

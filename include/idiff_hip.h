@@ -720,6 +720,53 @@ int idiff_empirical_jacobian_ok(int64_t N, int D);
 int idiff_empirical_jacobian_f64(const float *x, const float *X, const float *sigma, double *C, double *mean, float *ess,
                                  int B, int64_t N, int D, void *stream);
 
+/* ------------------------------------------------------------------ training the fcn score network (csrc/fcn_train.hip) */
+
+/* The two contractions the backward pass of a Linear + ELU layer needs beside idiff_gemm_f32, on v_mfma_f32_32x32x2_f32 (a k-ordered
+ * chain of fp32 fmas: |C - exact| <= K 2^-24 sum_k |a_k b_k|).  No split of K, no atomics, no workspace: the same bits on every run.
+ *
+ *   gemm_nn:  C[M, N] = (A[M, K] . Bm[K, N]) (*) g(P),  A rows K-contiguous (lda), Bm rows N-contiguous (ldb) -- an nn.Linear weight
+ *             [out, in] as it lies gives the data gradient dH = dA . W.  P [M, N] (ldp) or NULL: the ELU OUTPUT the gradient flows
+ *             back through, g(a) = a > 0 ? 1 : a + 1 (= ELU' written in terms of the output), applied as one fma.
+ *   gemm_tn:  C[M, N] = At[K, M]^T . Bm[K, N], both operands with K as the row index (lda, ldb): dW = dA^T . H with the batch as K.
+ *             colsum [M] or NULL: sum_k At[k, m] added in the order k = 0, 1, ... (the bias gradient).
+ *
+ * Any M, N, K >= 1.  Matrices 16-byte aligned, leading dimensions multiples of 4 floats and at least the row length; IDIFF_EINVAL
+ * before any device call otherwise, with a message that starts "gemm_nn: " / "gemm_tn: ".  *_ok (host only): 1 for the sizes served. */
+int idiff_gemm_nn_ok(int M, int N, int K);
+int idiff_gemm_nn_f32(const float *A, int64_t lda, const float *Bm, int64_t ldb, float *C, int64_t ldc, const float *P, int64_t ldp,
+                      int M, int N, int K, void *stream);
+int idiff_gemm_tn_ok(int M, int N, int K);
+int idiff_gemm_tn_f32(const float *At, int64_t lda, const float *Bm, int64_t ldb, float *C, int64_t ldc, float *colsum,
+                      int M, int N, int K, void *stream);
+
+/* Doubles of workspace the two fixed-order reductions below take (per-workgroup partials, indexed by workgroup). */
+#define IDIFF_REDUCE_WS_DOUBLES 1024
+
+/* Denoising score matching loss of losses.py:164-188 and its gradient with respect to the network output.  With score = -out / std both
+ * weightings are  mean_b weight[b] r_b,  r_b = reduce_d (z - out)^2:  weight NULL (= 1) or [B] (g(t)^2 / std^2 under likelihood
+ * weighting), reduce = mean_d (reduce_mean != 0) or (1/2) sum_d.  G [B, D] (row pitch ldg >= D floats) or NULL = s weight[b] (out - z), s = 2 / (B D) or 1 / B;
+ * *loss (device float) = the loss, summed in fp64 over fixed ranges in a fixed order and rounded once.  ws: IDIFF_REDUCE_WS_DOUBLES
+ * doubles.  G is evaluated in fp64 and rounded once.  Two launches. */
+int idiff_dsm_loss_grad_f32(const float *out, const float *z, const float *weight, float *G, int64_t ldg, float *loss, double *ws,
+                            int B, int D, int reduce_mean, void *stream);
+
+/* *sumsq (device double) = sum_i x[i]^2 in fp64, fixed ranges, fixed order (two launches); ws as above. */
+int idiff_grad_sumsq_f32(const float *x, int64_t n, double *ws, double *sumsq, void *stream);
+
+/* One torch.optim.Adam step (L2 weight_decay added to the gradient, bias corrections with `step` >= 1 the number of this step,
+ * denom = sqrt(v) / sqrt(1 - beta2^step) + eps, step size lr / (1 - beta1^step)) over ONE flat parameter buffer, behind
+ * torch.nn.utils.clip_grad_norm_: with sumsq (device double, from idiff_grad_sumsq_f32) the gradient is first multiplied by
+ * min(1, max_norm / (sqrt(*sumsq) + 1e-6)), read on the device; sumsq NULL: no clipping.  Evaluated in fp64 from the fp32 state, each
+ * of theta, m, v rounded once.  grad is not modified. */
+int idiff_adam_step_f32(float *theta, const float *grad, float *m, float *v, int64_t n, const double *sumsq, double max_norm, double lr,
+                        double beta1, double beta2, double eps, double weight_decay, int64_t step, void *stream);
+
+/* The network's input rows for a training batch: h[b, :D] = mean_coeff[b] x[b, :] + std[b] z[b, :] (mean_coeff NULL = 1),
+ * h[b, D] = label[b], h[b, D + 1 : kpad] = 0; x, z [B, D], h [B, kpad]. */
+int idiff_fcn_train_input_f32(const float *x, const float *z, const float *std_, const float *mean_coeff, const float *label, float *h,
+                              int64_t B, int D, int kpad, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
