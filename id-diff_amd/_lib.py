@@ -158,6 +158,9 @@ _SIGNATURES = {
     "idiff_grad_sumsq_f32": (c_i, [c_p, c_i64, c_p, c_p, c_p]),
     "idiff_adam_step_f32": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_p, c_d, c_d, c_d, c_d, c_d, c_d, c_i64, c_p]),
     "idiff_fcn_train_input_f32": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_p]),
+    "idiff_sampler_step_f32": (c_i, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64, c_i, c_d, c_d, c_d, c_p, c_d, c_d,
+                                     ctypes.c_uint64, c_i64, c_i, c_f, c_p]),
+    "idiff_sampler_noise_norm_f32": (c_i, [c_p, c_i64, c_i64, c_i, ctypes.c_uint64, c_i64, c_p, c_p, c_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -1700,3 +1703,57 @@ def fcn_train_input(x, z, std, mean_coeff, label, h):
     _check(lib().idiff_fcn_train_input_f32(x.data_ptr(), z.data_ptr(), std.data_ptr(), _ptr(mean_coeff), label.data_ptr(), h.data_ptr(),
                                            B, D, h.shape[1], _stream()), "idiff_fcn_train_input_f32")
     return h
+
+
+def _pitch(t, name, B, D):
+    """Row pitch of a [B, >= D] fp32 tensor with contiguous rows (a view of wider rows keeps their pitch)."""
+    _dev(t, name, contiguous=False)
+    if t.ndim != 2 or t.shape[0] != B or t.shape[1] < D or t.stride(1) != 1:
+        raise RuntimeError(f"{name}: expected [{B}, >= {D}] with contiguous rows, got shape {tuple(t.shape)} strides {t.stride()}")
+    return t.stride(0) if B > 1 else max(t.stride(0), t.shape[1])
+
+
+def sampler_step(x, s, a, b, c, z=None, out=None, mean_out=None, D=None, seed=0, row0=0, noise_norm=None, lang_scale=0.0,
+                 score_scale=1.0, label_col=-1, label_value=0.0):
+    """``(out, mean_out)``: mean_out = a x + b score_scale s and out = mean_out + c z over the first ``D`` columns (default: all of x) of
+    2-D tensors with contiguous rows, in fp64 from the fp32 inputs, each output rounded once.  ``z`` None: the noise is drawn in the
+    kernel from the stream (seed, row0); ``out`` None: in place in x.  ``noise_norm`` (device double of sampler_noise_norm) selects the
+    Langevin form a = 1, b = lang_scale nn^2 score_scale, c = sqrt(2 lang_scale nn^2).  ``label_col`` >= D: ``label_value`` is written
+    into that column of every row of out."""
+    if x.ndim != 2:
+        raise RuntimeError(f"sampler_step: x must be [B, D], got {tuple(x.shape)}")
+    B = x.shape[0]
+    D = x.shape[1] if D is None else int(D)
+    if out is None:
+        out = x
+    ldx, lds, ldo = _pitch(x, "x", B, D), _pitch(s, "s", B, D), _pitch(out, "out", B, D)
+    ldz = _pitch(z, "z", B, D) if z is not None else 0
+    ldm = _pitch(mean_out, "mean_out", B, D) if mean_out is not None else 0
+    if noise_norm is not None:
+        _dev(noise_norm, "noise_norm", dtype=torch.float64)
+    _check(lib().idiff_sampler_step_f32(x.data_ptr(), ldx, s.data_ptr(), lds, _ptr(z), ldz, out.data_ptr(), ldo, _ptr(mean_out), ldm, B, D,
+                                        float(a), float(b), float(c), _ptr(noise_norm), float(lang_scale), float(score_scale),
+                                        int(seed) & 0xFFFFFFFFFFFFFFFF, int(row0), int(label_col), float(label_value), _stream()),
+           "idiff_sampler_step_f32")
+    return out, mean_out
+
+
+def sampler_noise_norm(z=None, B=None, D=None, seed=0, row0=0, out=None, workspace=None, device=None):
+    """Device double: mean_r |z_r| of the explicit noise ``z`` [B, >= D], or (z None) of the stream (seed, row0) that sampler_step draws
+    for B rows of D columns; fp64, fixed order."""
+    if z is not None:
+        B = z.shape[0] if B is None else int(B)
+        D = z.shape[1] if D is None else int(D)
+        ldz, device = _pitch(z, "z", B, D), z.device
+    else:
+        if B is None or D is None or device is None:
+            raise RuntimeError("sampler_noise_norm: without z pass B, D and device")
+        ldz = 0
+    if out is None:
+        out = torch.empty((), device=device, dtype=torch.float64)
+    if workspace is None:
+        workspace = reduce_workspace(device)
+    _dev(out, "out", dtype=torch.float64); _dev(workspace, "workspace", dtype=torch.float64)
+    _check(lib().idiff_sampler_noise_norm_f32(_ptr(z), ldz, int(B), int(D), int(seed) & 0xFFFFFFFFFFFFFFFF, int(row0), workspace.data_ptr(),
+                                              out.data_ptr(), _stream()), "idiff_sampler_noise_norm_f32")
+    return out

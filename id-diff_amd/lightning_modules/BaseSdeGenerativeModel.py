@@ -23,6 +23,20 @@ class BaseSdeGenerativeModel(nn.Module):
     def configure_sde(self, config):
         self.sde, self.sampling_eps = sde_lib.configure_sde(config)
 
+    def sample(self, show_evolution=False, num_samples=None, ode=False, seed=None):
+        """BaseSdeGenerativeModel.py:70-84 of the reference: ``(samples, sampling_info)`` from the config's sampler (sampling.py; a
+        config without a ``sampling`` section gets the Euclidean configs' values).  ``seed`` (not in the reference) keys the noise
+        streams and defaults to ``config.seed``; ``ode=True`` is not built."""
+        from .. import sampling
+        if ode:
+            raise NotImplementedError("sample(ode=True): the probability-flow ODE sampler is not built")
+        if not hasattr(self, 'sde'):
+            self.configure_sde(self.config)
+        shape = self.default_sampling_shape if num_samples is None else [int(num_samples)] + list(self.config.data.shape)
+        sampling_fn = sampling.get_sampling_fn(self.config, self.sde, shape, self.sampling_eps)
+        seed = int(self.config.get('seed', 42)) if seed is None else int(seed)
+        return sampling_fn(self.score_model, show_evolution=show_evolution, seed=seed)
+
     def load_from_checkpoint(self, checkpoint_path, **kwargs):
         """Lightning ``.ckpt`` = torch.save({'state_dict': {'score_model.<k>': tensor}, 'hyper_parameters': ...}).
 

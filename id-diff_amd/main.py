@@ -3,7 +3,12 @@
 
 ``--mode train --n_iters N`` trains the ``fcn`` score network of a Euclidean config on one GPU (train.py) and writes
 ``<log_path>/<log_name>/checkpoints/last.ckpt``, which ``--mode manifold_dimension --checkpoint_path`` then reads;
-``--checkpoint_path`` with ``--mode train`` resumes.
+``--checkpoint_path`` with ``--mode train`` resumes; ``--eval_every K`` also logs, every K steps and at the end, the norms of 1000 samples
+drawn from the current weights and the mean estimated dimension of the checkpoint just written.
+
+``--mode generate [--checkpoint_path ...] [--num_samples M] [--seed S]`` draws samples from the config's score model with the
+predictor-corrector sampler (sampling.py) on one GPU, writes ``<log_path>/<log_name>/samples/samples.pkl`` and prints the minimum,
+maximum and mean of the samples' norms.
 
 Run it from the repo root as ``python id-diff_amd/main.py ...`` or, for several GPUs of one node,
 ``python -m torch.distributed.run --nproc-per-node N id-diff_amd/main.py ...``.
@@ -48,6 +53,11 @@ def parse(argv=None):
                     help="(--mode train) train until this many optimiser steps have been taken in total (the configs say 1e20)")
     ap.add_argument("--log_every", type=int, default=0, help="(--mode train) fetch and print the loss every this many steps")
     ap.add_argument("--checkpoint_every", type=int, default=0, help="(--mode train) also write last.ckpt every this many steps")
+    ap.add_argument("--eval_every", type=int, default=0,
+                    help="(--mode train) every this many steps, and at the end, sample from the current weights and log the norms and the "
+                         "estimated dimension (0: never)")
+    ap.add_argument("--num_samples", type=int, default=None, help="(--mode generate) number of samples to draw (default 1000)")
+    ap.add_argument("--seed", type=int, default=None, help="(--mode generate) seed of the noise streams (default: config.seed)")
     return ap.parse_args(argv)
 
 
@@ -58,11 +68,22 @@ def run_train(flags, config):
         raise SystemExit("--mode train runs on one GPU: --gpus must be 1 (or left out)")
     if flags.n_iters is None:
         raise SystemExit("--mode train needs --n_iters (the reference's configs train for 1e20 steps)")
-    if flags.n_iters < 0 or flags.log_every < 0 or flags.checkpoint_every < 0:
-        raise SystemExit("--n_iters, --log_every and --checkpoint_every must not be negative")
+    if flags.n_iters < 0 or flags.log_every < 0 or flags.checkpoint_every < 0 or flags.eval_every < 0:
+        raise SystemExit("--n_iters, --log_every, --checkpoint_every and --eval_every must not be negative")
     log_path = flags.log_path if flags.log_path != "./" or not config.logging.get("log_path") else config.logging.log_path
     return run_lib.train(config, log_path=log_path, checkpoint_path=config.model.get("checkpoint_path"), n_iters=flags.n_iters,
-                         log_every=flags.log_every, checkpoint_every=flags.checkpoint_every, log_name=flags.log_name)
+                         log_every=flags.log_every, checkpoint_every=flags.checkpoint_every, log_name=flags.log_name,
+                         **({"eval_every": flags.eval_every} if flags.eval_every else {}))
+
+
+def run_generate(flags, config):
+    if flags.gpus is not None and flags.gpus > 1:
+        raise SystemExit("--mode generate runs on one GPU: --gpus must be 1 (or left out)")
+    if flags.num_samples is not None and flags.num_samples < 1:
+        raise SystemExit("--num_samples must be positive")
+    log_path = flags.log_path if flags.log_path != "./" or not config.logging.get("log_path") else config.logging.log_path
+    return run_lib.generate(config, checkpoint_path=config.model.get("checkpoint_path"), num_samples=flags.num_samples, seed=flags.seed,
+                            log_path=log_path, log_name=flags.log_name)
 
 
 def main(argv=None):
@@ -79,6 +100,9 @@ def main(argv=None):
         config.model.allow_random_init = True
     if flags.mode == 'train':
         run_train(flags, config)
+        return
+    if flags.mode == 'generate':
+        run_generate(flags, config)
         return
     if flags.mode not in _HOT_MODES:
         raise SystemExit(f"mode {flags.mode!r} is outside the scope of id-diff_amd (the MI355X build covers "

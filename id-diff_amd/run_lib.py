@@ -11,9 +11,16 @@ def get_conditional_manifold_dimension(config, name=None):
     dim_reduction.get_conditional_manifold_dimension(config, name)
 
 
-def train(config, log_path=None, checkpoint_path=None, n_iters=None, log_every=0, checkpoint_every=0, log_name=None):
+def train(config, log_path=None, checkpoint_path=None, n_iters=None, log_every=0, checkpoint_every=0, log_name=None, eval_every=0):
     """Train the fcn score network (train.py); resumes when ``checkpoint_path`` or ``config.model.checkpoint_path`` is set and writes
     ``<log_path>/<log_name>/checkpoints/last.ckpt``."""
     from . import train as _train
     return _train.train(config, log_path=log_path, checkpoint_path=checkpoint_path, n_iters=n_iters, log_every=log_every,
-                        checkpoint_every=checkpoint_every, log_name=log_name)
+                        checkpoint_every=checkpoint_every, log_name=log_name, eval_every=eval_every)
+
+
+def generate(config, checkpoint_path=None, num_samples=None, seed=None, log_path=None, log_name=None):
+    """Draw samples from the config's score model (sampling.py) and write ``<log_path>/<log_name>/samples/samples.pkl``."""
+    from . import sampling
+    return sampling.generate(config, checkpoint_path=checkpoint_path, num_samples=num_samples, seed=seed, log_path=log_path,
+                             log_name=log_name)

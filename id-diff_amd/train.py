@@ -204,6 +204,7 @@ class FcnTrainer:
         self.sumsq = torch.zeros((), device=self.device, dtype=torch.float64)
         self.loss = torch.zeros((), device=self.device, dtype=torch.float32)
         self._gen = torch.Generator(device=self.device)
+        self.evaluations = []         # [(global_step, {min_norm, max_norm, mean_norm, dim})] of fit(eval_every=)
 
     # ---------------------------------------------------------------------------------------- state
     def state_dict(self):
@@ -331,10 +332,39 @@ class FcnTrainer:
         idx = self._perm[1][self._pos * self.batch_size:(self._pos + 1) * self.batch_size]
         return data.index_select(0, idx)
 
-    def fit(self, n_iters, log_every=0, checkpoint_every=0, checkpoint_path=None, log=print):
+    def evaluate(self, checkpoint_path, num_samples=1000, log=print):
+        """The two callbacks the Euclidean configs name, as numbers: min / max / mean norm of ``num_samples`` samples drawn from the
+        current weights (KSphereEvaluation) and ``dim``, the mean estimated dimension over ``logging.svd_points`` points (default 5) of
+        the checkpoint written to ``checkpoint_path`` (ScoreSpectrumVisualization).  The sampler draws from streams of its own
+        (sampling.SALT_*), so training goes on exactly as it would have."""
+        import copy
+        from . import dim_reduction, sampling
+        _, eps = sde_lib.configure_sde(self.config)
+        shape = [int(num_samples)] + list(self.config.data.shape)
+        samples, _ = sampling.get_sampling_fn(self.config, self.sde, shape, eps)(self.model, seed=stream_key(self.seed, self.global_step, 5))
+        out = sampling.ksphere_evaluation(samples)
+        self.save_checkpoint(checkpoint_path)
+        config = copy.deepcopy(self.config)
+        config.model.checkpoint_path = checkpoint_path
+        config.device = str(self.device)
+        if config.get('dim_estimation.num_datapoints') is None and config.get('logging.svd_points') is None:
+            config.logging.svd_points = 5
+        _, dims = dim_reduction.get_manifold_dimension(config, return_svd=True, return_dims=True)
+        dims = [int(d) for d in dims if int(d) >= 0]
+        out['dim'] = float(sum(dims)) / len(dims) if dims else float('nan')
+        self.evaluations.append((self.global_step, out))
+        if log is not None:
+            log(f"step {self.global_step} min_norm {out['min_norm']:.6g} max_norm {out['max_norm']:.6g} mean_norm {out['mean_norm']:.6g} "
+                f"dim {out['dim']:.3g}")
+        return out
+
+    def fit(self, n_iters, log_every=0, checkpoint_every=0, checkpoint_path=None, log=print, eval_every=0, num_samples=1000):
         """Steps until ``global_step == n_iters``.  The loss is fetched every ``log_every`` steps (0: only at the end) and a checkpoint
         written every ``checkpoint_every`` steps (0: never here).  Returns [(step, loss)] of the fetched losses; the first entry is the
-        loss of the first step taken and the last that of the last."""
+        loss of the first step taken and the last that of the last.  ``eval_every`` K > 0 (needs ``checkpoint_path``): every K steps
+        and at the end ``evaluate`` logs the sample norms and the estimated dimension; its results collect in ``self.evaluations``."""
+        if eval_every and not checkpoint_path:
+            raise ValueError("fit: eval_every needs checkpoint_path (the dimension is read from the checkpoint just written)")
         history, first = [], self.global_step
         while self.global_step < n_iters:
             at = self.global_step
@@ -347,6 +377,8 @@ class FcnTrainer:
                     log(f"step {at + 1}/{n_iters} epoch {self.epoch} lr {warmup_lr(self.optim['lr'], at, self.optim['warmup']):.3e} loss {value:.6g}")
             if checkpoint_every and checkpoint_path and self.global_step % checkpoint_every == 0 and self.global_step < n_iters:
                 self.save_checkpoint(checkpoint_path)
+            if eval_every and (self.global_step % eval_every == 0 or self.global_step == n_iters):
+                self.evaluate(checkpoint_path, num_samples=num_samples, log=log)
         return history
 
     def eval_loss(self, split='val', max_batches=None):
@@ -394,7 +426,8 @@ def last_checkpoint_path(config, log_path=None, log_name=None):
     return os.path.join(log_path, log_name, 'checkpoints', 'last.ckpt')
 
 
-def train(config, log_path=None, checkpoint_path=None, n_iters=None, log_every=0, checkpoint_every=0, log_name=None, log=print):
+def train(config, log_path=None, checkpoint_path=None, n_iters=None, log_every=0, checkpoint_every=0, log_name=None, log=print,
+          eval_every=0):
     """``--mode train``: resume from ``checkpoint_path`` (or ``config.model.checkpoint_path``) when given, train to ``n_iters`` steps,
     write ``<log_path>/<log_name>/checkpoints/last.ckpt`` every ``checkpoint_every`` steps and at the end.  Returns (trainer, history)."""
     check_scope(config)
@@ -408,7 +441,8 @@ def train(config, log_path=None, checkpoint_path=None, n_iters=None, log_every=0
         raise ValueError("train: pass --n_iters (the configs carry no usable step count)")
     n_iters = int(min(float(n_iters), 2 ** 62))
     out = last_checkpoint_path(config, log_path, log_name)
-    history = trainer.fit(n_iters, log_every=log_every, checkpoint_every=checkpoint_every, checkpoint_path=out, log=log)
+    history = trainer.fit(n_iters, log_every=log_every, checkpoint_every=checkpoint_every, checkpoint_path=out, log=log,
+                          eval_every=eval_every)
     trainer.save_checkpoint(out)
     if log is not None:
         log(f"wrote {out} at global_step {trainer.global_step}")

@@ -767,6 +767,29 @@ int idiff_adam_step_f32(float *theta, const float *grad, float *m, float *v, int
 int idiff_fcn_train_input_f32(const float *x, const float *z, const float *std_, const float *mean_coeff, const float *label, float *h,
                               int64_t B, int D, int kpad, void *stream);
 
+/* One update of a predictor or corrector of the sampler over the state rows [B, D] (sampling.py):
+ *     mean_out = a x + b score_scale s,      x_out = mean_out + c z
+ * evaluated in fp64 from the fp32 inputs, x_out from the unrounded mean, each output rounded to fp32 once.  Row pitches in floats, each
+ * >= D.  x_out may be x (in place); mean_out may be NULL.
+ * Noise: z given = explicit noise [B, D]; z NULL = drawn here, Philox4x32-10 keyed by `seed` with counter ((row0 + r) D4 + col) >> 2,
+ * D4 = D rounded up to 4: element (r, col) has the bits idiff_perturb_randn_f32 writes to z_out for a [rows, D4] matrix and the same
+ * seed and row0, however rows are cut into launches.  With c == 0 and no noise_norm nothing is drawn and z is not read.
+ * Langevin form: noise_norm (device double, from idiff_sampler_noise_norm_f32) given = the kernel uses a = 1,
+ * b = lang_scale (*noise_norm)^2 score_scale, c = sqrt(2 lang_scale (*noise_norm)^2) and ignores the a, b, c passed.
+ * label_col >= 0 (D <= label_col < ldo): label_value is also written into that column of every row of x_out (the time feature of the
+ * fcn's padded input rows).  16-byte accesses when every pointer is 16-byte aligned and every pitch a multiple of 4; any D and pitch
+ * otherwise.  No atomics, no workspace.  B == 0 returns 0. */
+int idiff_sampler_step_f32(const float *x, int64_t ldx, const float *s, int64_t lds, const float *z, int64_t ldz, float *x_out, int64_t ldo,
+                           float *mean_out, int64_t ldm, int64_t B, int D, double a, double b, double c, const double *noise_norm,
+                           double lang_scale, double score_scale, uint64_t seed, int64_t row0, int label_col, float label_value,
+                           void *stream);
+
+/* *out (device double) = mean_r sqrt(sum_col z[r, col]^2) over the explicit z [B, D] (pitch ldz), or, z NULL, over the generated stream
+ * of (seed, row0, B, D) above -- no noise buffer exists on that path.  fp64, fixed order: per-row sums, rows added in index order
+ * (two launches); ws: IDIFF_REDUCE_WS_DOUBLES doubles. */
+int idiff_sampler_noise_norm_f32(const float *z, int64_t ldz, int64_t B, int D, uint64_t seed, int64_t row0, double *ws, double *out,
+                                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif
