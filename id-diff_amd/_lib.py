@@ -92,13 +92,19 @@ _SIGNATURES = {
     "idiff_groupnorm_apply_f32": (c_i, [c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i64, c_i, c_p, c_p]),
     "idiff_groupnorm_apply_colstats_f32": (c_i, [c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_i, c_f, c_p, c_p, c_p, c_i64,
                                                  c_i, c_p, c_p]),
+    "idiff_groupnorm_apply_route": (ctypes.c_char_p, [c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
+    "idiff_groupnorm_apply_colstats_route": (ctypes.c_char_p, [c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p]),
     "idiff_softmax_rows_f32": (c_i, [c_p, c_p, c_i64, c_i, c_f, c_p]),
+    "idiff_softmax_rows_route": (ctypes.c_char_p, [c_p, c_p, c_i64, c_i, c_f]),
     "idiff_attention256_ok": (c_i, [c_i, c_i, c_i]),
     "idiff_attention256_f32": (c_i, [c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_p]),
     "idiff_attention_heads_ok": (c_i, [c_i, c_i, c_i, c_i]),
     "idiff_attention_heads_f32": (c_i, [c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p]),
     "idiff_affine_act_f32": (c_i, [c_p, c_p, c_i64, c_f, c_f, c_i, c_p, c_i64, c_p]),
     "idiff_add_scale_f32": (c_i, [c_p, c_p, c_p, c_i64, c_f, c_p]),
+    "idiff_affine_act_route": (ctypes.c_char_p, [c_p, c_p, c_i64, c_p, c_i64]),
+    "idiff_add_scale_route": (ctypes.c_char_p, [c_p, c_p, c_p, c_i64]),
+    "idiff_concat_cols_route": (ctypes.c_char_p, [c_p, c_i, c_p, c_i, c_p, c_i64]),
     "idiff_fourier_embed_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_p]),
     "idiff_positional_embed_f32": (c_i, [c_p, c_p, c_i, c_i, c_f, c_i, c_p]),
     "idiff_concat_cols_f32": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i64, c_p]),
@@ -707,9 +713,37 @@ def groupnorm_apply_colstats(x, C, x2, C2, B, HW, G, ws1, ns1, ws2, ns2, eps, ga
            "idiff_groupnorm_apply_colstats_f32")
 
 
+def _route(name):
+    return None if name is None else name.decode()
+
+
+def _addr0(t):
+    """Address of a tensor, a raw address, or 0 for None: the route queries look at null and 16-byte alignment only."""
+    return 0 if t is None else _addr(t)
+
+
+def groupnorm_apply_route(x, C, x2, C2, B, HW, G, stats, gamma, beta, y):
+    """"rows" or "flat": the kernel ``groupnorm_apply`` would launch for these arguments (idiff_groupnorm_apply_route), None if it
+    refuses them.  Tensors or raw addresses; nothing is launched."""
+    return _route(lib().idiff_groupnorm_apply_route(_addr0(x), C, _addr0(x2), C2, B, HW, G, _addr0(stats), _addr0(gamma), _addr0(beta),
+                                                    _addr0(y)))
+
+
+def groupnorm_apply_colstats_route(x, C, x2, C2, B, HW, G, ws1, ns1, ws2, ns2, gamma, beta, y):
+    """The same for ``groupnorm_apply_colstats`` (idiff_groupnorm_apply_colstats_route): "rows", or None."""
+    return _route(lib().idiff_groupnorm_apply_colstats_route(_addr0(x), C, _addr0(x2), C2, B, HW, G, _addr0(ws1), ns1, _addr0(ws2), ns2,
+                                                             _addr0(gamma), _addr0(beta), _addr0(y)))
+
+
 def softmax_rows(x, y, rows, cols, scale):
     _check(lib().idiff_softmax_rows_f32(x.data_ptr(), y.data_ptr(), rows, cols, scale, _stream()),
            "idiff_softmax_rows_f32")
+
+
+def softmax_rows_route(x, y, rows, cols, scale):
+    """"vec<1>" / "vec<2>" / "vec<4>" / "regs" / "stream" ("none" for rows == 0): the kernel, and for the general kernel the branch,
+    that ``softmax_rows`` would run (idiff_softmax_rows_route); None if it refuses the arguments.  Nothing is launched."""
+    return _route(lib().idiff_softmax_rows_route(_addr0(x), _addr0(y), rows, cols, scale))
 
 
 def attention256_ok(B, tokens, C):
@@ -766,9 +800,19 @@ def affine_act(a, y, n, alpha=1.0, beta=0.0, act=None, rowscale=None, inner=0):
                                       _stream()), "idiff_affine_act_f32")
 
 
+def affine_act_route(a, y, n, rowscale=None, inner=0):
+    """"vec4" or "scalar" ("none" for n == 0): the kernel ``affine_act`` would launch (idiff_affine_act_route), None if it refuses."""
+    return _route(lib().idiff_affine_act_route(_addr0(a), _addr0(y), n, _addr0(rowscale), inner))
+
+
 def add_scale(a, b, y, n, scale):
     _check(lib().idiff_add_scale_f32(a.data_ptr(), b.data_ptr(), y.data_ptr(), n, scale, _stream()),
            "idiff_add_scale_f32")
+
+
+def add_scale_route(a, b, y, n):
+    """The same for ``add_scale`` (idiff_add_scale_route)."""
+    return _route(lib().idiff_add_scale_route(_addr0(a), _addr0(b), _addr0(y), n))
 
 
 def fourier_embed(t, W, out, B, half):
@@ -784,6 +828,11 @@ def positional_embed(t, out, B, dim, max_positions=10000.0, mode=0):
 def concat_cols(a, Ca, b, Cb, out, rows):
     _check(lib().idiff_concat_cols_f32(a.data_ptr(), Ca, b.data_ptr(), Cb, out.data_ptr(), rows, _stream()),
            "idiff_concat_cols_f32")
+
+
+def concat_cols_route(a, Ca, b, Cb, out, rows):
+    """The same for ``concat_cols`` (idiff_concat_cols_route; "none" for rows == 0)."""
+    return _route(lib().idiff_concat_cols_route(_addr0(a), Ca, _addr0(b), Cb, _addr0(out), rows))
 
 
 def nchw_to_nhwc(x, y, B, C, HW, Cpad, alpha=1.0, beta=0.0):

@@ -280,6 +280,8 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+constexpr int kSoftmaxRegCols = 1024;   // softmax_rows_kernel keeps a row of up to this many columns in registers ("regs"), streams a longer one
+
 __global__ void __launch_bounds__(256)
 softmax_rows_kernel(const float *__restrict__ x, float *__restrict__ y, int64_t rows, int cols, float scale) {
   const int lane = threadIdx.x & 63;
@@ -287,7 +289,7 @@ softmax_rows_kernel(const float *__restrict__ x, float *__restrict__ y, int64_t 
   if (row >= rows) return;
   const float *xr = x + row * cols;
   float *yr = y + row * cols;
-  constexpr int PL = 16;
+  constexpr int PL = kSoftmaxRegCols / 64;
   if (cols <= 64 * PL) {
     float v[PL];
     float m = -INFINITY;
@@ -536,6 +538,85 @@ perturb_kernel(const float *__restrict__ x, const float *__restrict__ z, const f
 
 bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
+// ------------------------------------------------------------------------------------------------
+// Which kernel serves a call.  One small function per launcher holds its admission checks and its choice; the launcher
+// switches on the result and the exported idiff_*_route query reports it, so a test can name the kernel it reached.
+// Each returns 0 and sets `r`, or the error code of arguments the launcher refuses (idiff_last_error says why).
+// ------------------------------------------------------------------------------------------------
+enum NaRoute { NA_NONE /* nothing to launch */, NA_ROWS, NA_FLAT, NA_VEC1, NA_VEC2, NA_VEC4R, NA_REGS, NA_STREAM, NA_VEC4, NA_SCALAR };
+const char *const kNaRouteNames[] = {"none", "rows", "flat", "vec<1>", "vec<2>", "vec<4>", "regs", "stream", "vec4", "scalar"};
+
+using idiff::fail;
+
+// what both GroupNorm applies check, and the row-structured kernel or the flat one
+int gn_apply_choose(const void *x, int C, const void *x2, int &C2, int B, int HW, int G, const void *gamma, const void *beta,
+                    const void *y, NaRoute &r) {
+  if (!x || !gamma || !beta || !y) return fail("groupnorm_apply: null pointer");
+  if (!x2) C2 = 0;
+  const int Ctot = C + C2;
+  if (B <= 0 || HW <= 0 || C <= 0 || G <= 0 || Ctot % G != 0 || C % 4 || C2 % 4) return fail("groupnorm_apply: bad shape");
+  if (!al16(x) || (x2 && !al16(x2)) || !al16(y) || !al16(gamma) || !al16(beta))
+    return fail("groupnorm_apply: pointers must be 16-byte aligned");
+  r = (Ctot / 4 <= 256 && B <= 65535) ? NA_ROWS : NA_FLAT;   // a thread per float4 channel column, grid.y = sample
+  return 0;
+}
+
+int gn_apply_stats_choose(const void *x, int C, const void *x2, int &C2, int B, int HW, int G, const void *stats, const void *gamma,
+                          const void *beta, const void *y, NaRoute &r) {
+  if (!stats) return fail("groupnorm_apply: null pointer");
+  return gn_apply_choose(x, C, x2, C2, B, HW, G, gamma, beta, y, r);
+}
+
+int gn_apply_colstats_choose(const void *x, int C, const void *x2, int &C2, int B, int HW, int G, const void *ws1, int nsplit1,
+                             const double *&ws2, int &nsplit2, const void *gamma, const void *beta, const void *y, NaRoute &r) {
+  if (!ws1 || nsplit1 <= 0) return fail("groupnorm_apply_colstats: the first source's column sums are required");
+  if (!x2) { ws2 = nullptr; nsplit2 = 0; }
+  if (x2 && (!ws2 || nsplit2 <= 0)) return fail("groupnorm_apply_colstats: the second source needs its column sums too");
+  if ((C + (x2 ? C2 : 0)) / 4 > 256 || B > 65535)
+    return fail("groupnorm_apply_colstats: more than 1024 channels or 65535 samples (use idiff_groupnorm_finalize_f32 + idiff_groupnorm_apply_f32)");
+  return gn_apply_choose(x, C, x2, C2, B, HW, G, gamma, beta, y, r);
+}
+
+int softmax_choose(const void *x, const void *y, int64_t rows, int cols, float scale, NaRoute &r) {
+  if (rows < 0 || cols <= 0) return fail("softmax: bad shape");
+  r = NA_NONE;
+  if (rows == 0) return 0;
+  if (!x || !y) return fail("softmax: null pointer");
+  if (idiff::ceil_div64(rows, 4) > 0x7fffffff) return fail("softmax: too many rows");
+  if (cols % 4 == 0 && cols <= 1024 && al16(x) && al16(y) && scale > 0.f) r = cols <= 256 ? NA_VEC1 : cols <= 512 ? NA_VEC2 : NA_VEC4R;
+  else r = cols <= kSoftmaxRegCols ? NA_REGS : NA_STREAM;
+  return 0;
+}
+
+int affine_act_choose(const void *a, const void *y, int64_t n, const void *rowscale, int64_t &inner, NaRoute &r) {
+  if (n < 0) return fail("affine_act: negative size");
+  r = NA_NONE;
+  if (n == 0) return 0;
+  if (!a || !y) return fail("affine_act: null pointer");
+  if (rowscale && inner <= 0) return fail("affine_act: rowscale needs inner > 0");
+  if (!rowscale) inner = 4;
+  r = (n % 4 == 0 && inner % 4 == 0 && al16(a) && al16(y)) ? NA_VEC4 : NA_SCALAR;
+  return 0;
+}
+
+int add_scale_choose(const void *a, const void *b, const void *y, int64_t n, NaRoute &r) {
+  if (n < 0) return fail("add_scale: negative size");
+  r = NA_NONE;
+  if (n == 0) return 0;
+  if (!a || !b || !y) return fail("add_scale: null pointer");
+  r = (n % 4 == 0 && al16(a) && al16(b) && al16(y)) ? NA_VEC4 : NA_SCALAR;
+  return 0;
+}
+
+int concat_cols_choose(const void *a, int Ca, const void *b, int Cb, const void *out, int64_t rows, NaRoute &r) {
+  if (rows < 0 || Ca <= 0 || Cb <= 0) return fail("concat_cols: bad shape");
+  r = NA_NONE;
+  if (rows == 0) return 0;
+  if (!a || !b || !out) return fail("concat_cols: null pointer");
+  r = (Ca % 4 == 0 && Cb % 4 == 0 && al16(a) && al16(b) && al16(out)) ? NA_VEC4 : NA_SCALAR;
+  return 0;
+}
+
 }  // namespace
 
 using namespace idiff;
@@ -589,43 +670,14 @@ IDIFF_API int idiff_groupnorm_coef_f32(const double *ws1, int nsplit1, int C1, c
 }
 
 namespace {
-int groupnorm_apply_impl(const float *x, int C, const float *x2, int C2, int B, int HW, int G, const float *stats,
-                         const double *ws1, int ns1, const double *ws2, int ns2, float eps, const float *gamma,
-                         const float *beta, const float *mod, int64_t ld_mod, int act, float *y, void *stream);
-}
-
-IDIFF_API int idiff_groupnorm_apply_f32(const float *x, int C, const float *x2, int C2, int B, int HW, int G,
-                                        const float *stats, const float *gamma, const float *beta, const float *mod,
-                                        int64_t ld_mod, int act, float *y, void *stream) {
-  if (!stats) return fail("groupnorm_apply: null pointer");
-  return groupnorm_apply_impl(x, C, x2, C2, B, HW, G, stats, nullptr, 0, nullptr, 0, 0.f, gamma, beta, mod, ld_mod, act, y, stream);
-}
-
-IDIFF_API int idiff_groupnorm_apply_colstats_f32(const float *x, int C, const float *x2, int C2, int B, int HW, int G,
-                                                 const double *ws1, int nsplit1, const double *ws2, int nsplit2, float eps,
-                                                 const float *gamma, const float *beta, const float *mod, int64_t ld_mod,
-                                                 int act, float *y, void *stream) {
-  if (!ws1 || nsplit1 <= 0) return fail("groupnorm_apply_colstats: the first source's column sums are required");
-  if (!x2) { ws2 = nullptr; nsplit2 = 0; }
-  if (x2 && (!ws2 || nsplit2 <= 0)) return fail("groupnorm_apply_colstats: the second source needs its column sums too");
-  if ((C + (x2 ? C2 : 0)) / 4 > 256 || B > 65535)
-    return fail("groupnorm_apply_colstats: more than 1024 channels or 65535 samples (use idiff_groupnorm_finalize_f32 + idiff_groupnorm_apply_f32)");
-  return groupnorm_apply_impl(x, C, x2, C2, B, HW, G, nullptr, ws1, nsplit1, ws2, nsplit2, eps, gamma, beta, mod, ld_mod, act, y, stream);
-}
-
-namespace {
-int groupnorm_apply_impl(const float *x, int C, const float *x2, int C2, int B, int HW, int G, const float *stats,
-                         const double *ws1, int ns1, const double *ws2, int ns2, float eps, const float *gamma,
-                         const float *beta, const float *mod, int64_t ld_mod, int act, float *y, void *stream) {
-  if (!x || !gamma || !beta || !y) return fail("groupnorm_apply: null pointer");
-  if (!x2) C2 = 0;
+// The launch of either apply kernel for the route gn_apply_choose picked (stats, or the column sums ws1 / ws2 on the row-structured kernel).
+int groupnorm_apply_launch(NaRoute route, const float *x, int C, const float *x2, int C2, int B, int HW, int G, const float *stats,
+                           const double *ws1, int ns1, const double *ws2, int ns2, float eps, const float *gamma,
+                           const float *beta, const float *mod, int64_t ld_mod, int act, float *y, void *stream) {
   const int Ctot = C + C2;
-  if (B <= 0 || HW <= 0 || C <= 0 || G <= 0 || Ctot % G != 0 || C % 4 || C2 % 4) return fail("groupnorm_apply: bad shape");
-  if (!al16(x) || (x2 && !al16(x2)) || !al16(y) || !al16(gamma) || !al16(beta))
-    return fail("groupnorm_apply: pointers must be 16-byte aligned");
   const int64_t total_vec = (int64_t)B * HW * (Ctot / 4);
   const int CVt = Ctot / 4;
-  if (CVt <= 256 && B <= 65535) {
+  if (route == NA_ROWS) {
     // ~2048 workgroups in total, each a contiguous range of pixels of one sample
     const int RP = 256 / CVt;
     int xblocks = max(1, min(ceil_div(HW, RP), ceil_div(2048, B)));
@@ -641,32 +693,67 @@ int groupnorm_apply_impl(const float *x, int C, const float *x2, int C2, int B, 
 }
 }  // namespace
 
+IDIFF_API int idiff_groupnorm_apply_f32(const float *x, int C, const float *x2, int C2, int B, int HW, int G,
+                                        const float *stats, const float *gamma, const float *beta, const float *mod,
+                                        int64_t ld_mod, int act, float *y, void *stream) {
+  NaRoute r;
+  if (int rc = gn_apply_stats_choose(x, C, x2, C2, B, HW, G, stats, gamma, beta, y, r)) return rc;
+  return groupnorm_apply_launch(r, x, C, x2, C2, B, HW, G, stats, nullptr, 0, nullptr, 0, 0.f, gamma, beta, mod, ld_mod, act, y, stream);
+}
+
+IDIFF_API const char *idiff_groupnorm_apply_route(const void *x, int C, const void *x2, int C2, int B, int HW, int G, const void *stats,
+                                                  const void *gamma, const void *beta, const void *y) {
+  NaRoute r;
+  if (gn_apply_stats_choose(x, C, x2, C2, B, HW, G, stats, gamma, beta, y, r)) return nullptr;
+  return kNaRouteNames[r];
+}
+
+IDIFF_API int idiff_groupnorm_apply_colstats_f32(const float *x, int C, const float *x2, int C2, int B, int HW, int G,
+                                                 const double *ws1, int nsplit1, const double *ws2, int nsplit2, float eps,
+                                                 const float *gamma, const float *beta, const float *mod, int64_t ld_mod,
+                                                 int act, float *y, void *stream) {
+  NaRoute r;
+  if (int rc = gn_apply_colstats_choose(x, C, x2, C2, B, HW, G, ws1, nsplit1, ws2, nsplit2, gamma, beta, y, r)) return rc;
+  return groupnorm_apply_launch(r, x, C, x2, C2, B, HW, G, nullptr, ws1, nsplit1, ws2, nsplit2, eps, gamma, beta, mod, ld_mod, act, y, stream);
+}
+
+IDIFF_API const char *idiff_groupnorm_apply_colstats_route(const void *x, int C, const void *x2, int C2, int B, int HW, int G,
+                                                           const double *ws1, int nsplit1, const double *ws2, int nsplit2,
+                                                           const void *gamma, const void *beta, const void *y) {
+  NaRoute r;
+  if (gn_apply_colstats_choose(x, C, x2, C2, B, HW, G, ws1, nsplit1, ws2, nsplit2, gamma, beta, y, r)) return nullptr;
+  return kNaRouteNames[r];
+}
+
 IDIFF_API int idiff_softmax_rows_f32(const float *x, float *y, int64_t rows, int cols, float scale, void *stream) {
-  if (rows < 0 || cols <= 0) return fail("softmax: bad shape");
-  if (rows == 0) return 0;
-  if (!x || !y) return fail("softmax: null pointer");
+  NaRoute r;
+  if (int rc = softmax_choose(x, y, rows, cols, scale, r)) return rc;
+  if (r == NA_NONE) return 0;
   const int64_t blocks = ceil_div64(rows, 4);
-  if (blocks > 0x7fffffff) return fail("softmax: too many rows");
-  if (cols % 4 == 0 && cols <= 1024 && al16(x) && al16(y) && scale > 0.f) {
-    const unsigned grid = (unsigned)(blocks < 256 * 16 ? blocks : 256 * 16);       // 16 four-wave workgroups per CU walk the rows
-    if (cols <= 256) hipLaunchKernelGGL(softmax_rows_vec_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, y, rows, cols, scale);
-    else if (cols <= 512) hipLaunchKernelGGL(softmax_rows_vec_kernel<2>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, y, rows, cols, scale);
-    else hipLaunchKernelGGL(softmax_rows_vec_kernel<4>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, y, rows, cols, scale);
-    return launch_status("softmax_rows");
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = (unsigned)(blocks < 256 * 16 ? blocks : 256 * 16);         // the vec kernels: 16 four-wave workgroups per CU walk the rows
+  switch (r) {
+    case NA_VEC1: hipLaunchKernelGGL(softmax_rows_vec_kernel<1>, dim3(grid), dim3(256), 0, st, x, y, rows, cols, scale); break;
+    case NA_VEC2: hipLaunchKernelGGL(softmax_rows_vec_kernel<2>, dim3(grid), dim3(256), 0, st, x, y, rows, cols, scale); break;
+    case NA_VEC4R: hipLaunchKernelGGL(softmax_rows_vec_kernel<4>, dim3(grid), dim3(256), 0, st, x, y, rows, cols, scale); break;
+    default: hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, y, rows, cols, scale); break;   // regs / stream
   }
-  hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, y, rows, cols, scale);
   return launch_status("softmax_rows");
+}
+
+IDIFF_API const char *idiff_softmax_rows_route(const void *x, const void *y, int64_t rows, int cols, float scale) {
+  NaRoute r;
+  if (softmax_choose(x, y, rows, cols, scale, r)) return nullptr;
+  return kNaRouteNames[r];
 }
 
 IDIFF_API int idiff_affine_act_f32(const float *a, float *y, int64_t n, float alpha, float beta_const, int act,
                                    const float *rowscale, int64_t inner, void *stream) {
-  if (n < 0) return fail("affine_act: negative size");
-  if (n == 0) return 0;
-  if (!a || !y) return fail("affine_act: null pointer");
-  if (rowscale && inner <= 0) return fail("affine_act: rowscale needs inner > 0");
-  if (!rowscale) inner = 4;
+  NaRoute r;
+  if (int rc = affine_act_choose(a, y, n, rowscale, inner, r)) return rc;
+  if (r == NA_NONE) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (n % 4 == 0 && inner % 4 == 0 && al16(a) && al16(y))
+  if (r == NA_VEC4)
     hipLaunchKernelGGL(affine_act_kernel<true>, dim3(streaming_grid(n / 4, 256)), dim3(256), 0, st, a, y, n, alpha,
                        beta_const, act, rowscale, inner);
   else
@@ -675,16 +762,28 @@ IDIFF_API int idiff_affine_act_f32(const float *a, float *y, int64_t n, float al
   return launch_status("affine_act");
 }
 
+IDIFF_API const char *idiff_affine_act_route(const void *a, const void *y, int64_t n, const void *rowscale, int64_t inner) {
+  NaRoute r;
+  if (affine_act_choose(a, y, n, rowscale, inner, r)) return nullptr;
+  return kNaRouteNames[r];
+}
+
 IDIFF_API int idiff_add_scale_f32(const float *a, const float *b, float *y, int64_t n, float scale, void *stream) {
-  if (n < 0) return fail("add_scale: negative size");
-  if (n == 0) return 0;
-  if (!a || !b || !y) return fail("add_scale: null pointer");
+  NaRoute r;
+  if (int rc = add_scale_choose(a, b, y, n, r)) return rc;
+  if (r == NA_NONE) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (n % 4 == 0 && al16(a) && al16(b) && al16(y))
+  if (r == NA_VEC4)
     hipLaunchKernelGGL(add_scale_kernel<true>, dim3(streaming_grid(n / 4, 256)), dim3(256), 0, st, a, b, y, n, scale);
   else
     hipLaunchKernelGGL(add_scale_kernel<false>, dim3(streaming_grid(n, 256)), dim3(256), 0, st, a, b, y, n, scale);
   return launch_status("add_scale");
+}
+
+IDIFF_API const char *idiff_add_scale_route(const void *a, const void *b, const void *y, int64_t n) {
+  NaRoute r;
+  if (add_scale_choose(a, b, y, n, r)) return nullptr;
+  return kNaRouteNames[r];
 }
 
 IDIFF_API int idiff_fourier_embed_f32(const float *t, const float *W, float *out, int B, int half, void *stream) {
@@ -706,16 +805,22 @@ IDIFF_API int idiff_positional_embed_f32(const float *t, float *out, int B, int 
 }
 
 IDIFF_API int idiff_concat_cols_f32(const float *a, int Ca, const float *b, int Cb, float *out, int64_t rows, void *stream) {
-  if (rows < 0 || Ca <= 0 || Cb <= 0) return fail("concat_cols: bad shape");
-  if (rows == 0) return 0;
-  if (!a || !b || !out) return fail("concat_cols: null pointer");
+  NaRoute r;
+  if (int rc = concat_cols_choose(a, Ca, b, Cb, out, rows, r)) return rc;
+  if (r == NA_NONE) return 0;
   hipStream_t st = (hipStream_t)stream;
   const int64_t total = rows * (Ca + Cb);
-  if (Ca % 4 == 0 && Cb % 4 == 0 && al16(a) && al16(b) && al16(out))
+  if (r == NA_VEC4)
     hipLaunchKernelGGL(concat_cols_vec4_kernel, dim3(streaming_grid(total / 4, 256)), dim3(256), 0, st, a, Ca, b, Cb, out, total / 4);
   else
     hipLaunchKernelGGL(concat_cols_kernel, dim3(streaming_grid(total, 256)), dim3(256), 0, st, a, Ca, b, Cb, out, total);
   return launch_status("concat_cols");
+}
+
+IDIFF_API const char *idiff_concat_cols_route(const void *a, int Ca, const void *b, int Cb, const void *out, int64_t rows) {
+  NaRoute r;
+  if (concat_cols_choose(a, Ca, b, Cb, out, rows, r)) return nullptr;
+  return kNaRouteNames[r];
 }
 
 IDIFF_API int idiff_nchw_to_nhwc_f32(const float *x, float *y, int B, int C, int HW, int Cpad, float alpha, float beta,

@@ -384,6 +384,15 @@ int idiff_groupnorm_apply_colstats_f32(const float *x, int C, const float *x2, i
                                        const double *ws1, int nsplit1, const double *ws2, int nsplit2, float eps,
                                        const float *gamma, const float *beta, const float *mod, int64_t ld_mod,
                                        int act, float *y, void *stream);
+/* The kernel idiff_groupnorm_apply_f32 / idiff_groupnorm_apply_colstats_f32 would launch for these arguments (same admission code; the
+ * pointers are only inspected for null and 16-byte alignment): "rows" (a thread per float4 channel column, grid.y = sample: C + C2 <= 1024
+ * and B <= 65535) or "flat" (one grid-stride loop over all float4s; never with column sums).  NULL for arguments the launcher refuses
+ * (idiff_last_error says why).  Launches nothing; no reference counterpart. */
+const char *idiff_groupnorm_apply_route(const void *x, int C, const void *x2, int C2, int B, int HW, int G, const void *stats,
+                                        const void *gamma, const void *beta, const void *y);
+const char *idiff_groupnorm_apply_colstats_route(const void *x, int C, const void *x2, int C2, int B, int HW, int G,
+                                                 const double *ws1, int nsplit1, const double *ws2, int nsplit2,
+                                                 const void *gamma, const void *beta, const void *y);
 /* The same GroupNorm as one affine pair per (sample, channel) for a consumer that applies it itself (idiff_conv2d_wino1d_normload_f32):
  * coef [B, C1 + C2, 2] = (a, b) with a = rstd * gamma[c], b = beta[c] - mean * rstd * gamma[c], so that a * x + b is the norm of x.
  * Statistics from the producers' column sums as idiff_groupnorm_finalize_f32 forms them; the pair is formed in fp64 and rounded once. */
@@ -392,6 +401,11 @@ int idiff_groupnorm_coef_f32(const double *ws1, int nsplit1, int C1, const doubl
 
 /* Row softmax of x [rows, cols] scaled by `scale` before the exponent (layerspp.py:82-84). In place allowed. */
 int idiff_softmax_rows_f32(const float *x, float *y, int64_t rows, int cols, float scale, void *stream);
+/* The kernel idiff_softmax_rows_f32 would launch (same admission code; x and y are only inspected for null and 16-byte alignment):
+ * "vec<1>" / "vec<2>" / "vec<4>" (16-byte accesses, v_exp_f32: cols a multiple of 4 up to 256 / 512 / 1024, aligned pointers, scale > 0),
+ * else the general kernel's branch "regs" (cols <= 1024, the row in registers) or "stream" (three passes over the row); "none" when
+ * rows == 0 (nothing to launch).  NULL for arguments the launcher refuses.  Launches nothing; no reference counterpart. */
+const char *idiff_softmax_rows_route(const void *x, const void *y, int64_t rows, int cols, float scale);
 
 /* Single-head self-attention over 256 tokens in ONE launch, the [256, 256] logits never leaving the chip (models/layerspp.py:75-91:
  * w = einsum(q, k) * C^-1/2 -> softmax -> einsum(w, v); models/BeatGANsblocks.py:466-491, one head):
@@ -426,6 +440,13 @@ int idiff_attention_heads_f32(const float *qk, int64_t ld_qk, const float *vt, c
  * time embedding, and -out/std when `rowscale` ([n / inner]) is given: y = act(...) * rowscale[i / inner]. */
 int idiff_affine_act_f32(const float *a, float *y, int64_t n, float alpha, float beta_const, int act,
                          const float *rowscale, int64_t inner, void *stream);
+/* The kernel idiff_affine_act_f32 would launch (same admission code): "vec4" (n and inner multiples of 4, a and y 16-byte aligned) or
+ * "scalar"; "none" when n == 0.  NULL for arguments the launcher refuses.  The same for idiff_add_scale_f32 (a, b, y aligned, n % 4 == 0)
+ * and idiff_concat_cols_f32 (Ca and Cb multiples of 4, a, b, out aligned; "none" when rows == 0).  They launch nothing; no reference
+ * counterpart. */
+const char *idiff_affine_act_route(const void *a, const void *y, int64_t n, const void *rowscale, int64_t inner);
+const char *idiff_add_scale_route(const void *a, const void *b, const void *y, int64_t n);
+const char *idiff_concat_cols_route(const void *a, int Ca, const void *b, int Cb, const void *out, int64_t rows);
 /* y = (a + b) * scale (skip-rescale adds, models/ncsnpp.py:303-307). */
 int idiff_add_scale_f32(const float *a, const float *b, float *y, int64_t n, float scale, void *stream);
 /* Gaussian Fourier features: out[b] = [sin(2*pi*t[b]*W), cos(2*pi*t[b]*W)] (models/layerspp.py:39-41). */
