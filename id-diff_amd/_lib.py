@@ -100,6 +100,8 @@ _SIGNATURES = {
     "idiff_attention256_f32": (c_i, [c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_p]),
     "idiff_attention_heads_ok": (c_i, [c_i, c_i, c_i, c_i]),
     "idiff_attention_heads_f32": (c_i, [c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p]),
+    "idiff_attention256_route": (ctypes.c_char_p, [c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i]),
+    "idiff_attention_heads_route": (ctypes.c_char_p, [c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i]),
     "idiff_affine_act_f32": (c_i, [c_p, c_p, c_i64, c_f, c_f, c_i, c_p, c_i64, c_p]),
     "idiff_add_scale_f32": (c_i, [c_p, c_p, c_p, c_i64, c_f, c_p]),
     "idiff_affine_act_route": (ctypes.c_char_p, [c_p, c_p, c_i64, c_p, c_i64]),
@@ -793,6 +795,19 @@ def attention_heads(qk, vt, out, B, tokens, heads, D, s_qk, s_v, scale, bias_v=N
     _check(lib().idiff_attention_heads_f32(qk.data_ptr(), qk.stride(0), vt.data_ptr(), _ptr(bias_v), s_qk.data_ptr(), s_v.data_ptr(),
                                            out.data_ptr(), B, tokens, heads, D, float(scale), _stream()), "idiff_attention_heads_f32")
     return out
+
+
+def attention256_route(qk, ld_qk, vt, bias_v, s_qk, s_v, out, B, tokens, C):
+    """"attention256<128>" / "attention256<256>" ("none" for B == 0): the instantiation ``idiff_attention256_f32`` would launch for these
+    arguments (idiff_attention256_route), None if it refuses them.  Tensors or raw addresses; nothing is launched."""
+    return _route(lib().idiff_attention256_route(_addr0(qk), ld_qk, _addr0(vt), _addr0(bias_v), _addr0(s_qk), _addr0(s_v), _addr0(out),
+                                                 B, tokens, C))
+
+
+def attention_heads_route(qk, ld_qk, vt, bias_v, s_qk, s_v, out, B, tokens, heads, D):
+    """"heads<D,NW>" ("none" for B == 0): the same for ``idiff_attention_heads_f32`` (idiff_attention_heads_route)."""
+    return _route(lib().idiff_attention_heads_route(_addr0(qk), ld_qk, _addr0(vt), _addr0(bias_v), _addr0(s_qk), _addr0(s_v), _addr0(out),
+                                                    B, tokens, heads, D))
 
 
 def affine_act(a, y, n, alpha=1.0, beta=0.0, act=None, rowscale=None, inner=0):

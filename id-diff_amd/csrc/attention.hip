@@ -517,6 +517,49 @@ bool attention_heads_shape_ok(int B, int tokens, int H, int D) {
          (int64_t)B * H <= (1 << 20);
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// Which kernel serves a call.  One small function per entry point holds its admission checks and its choice of instantiation; the
+// launcher switches on the result and the exported idiff_attention*_route query reports it, so a test can name the form it reached.
+// Each returns 0 and sets `r`, or the error code of arguments the launcher refuses (idiff_last_error says why).
+enum AtRoute { AT_NONE /* nothing to launch */, AT_C128, AT_C256, AH_32_4, AH_32_8, AH_64_4, AH_64_8, AH_128_4, AH_128_8 };
+const char *const kAtRouteNames[] = {"none", "attention256<128>", "attention256<256>", "heads<32,4>", "heads<32,8>", "heads<64,4>", "heads<64,8>",
+                                     "heads<128,4>", "heads<128,8>"};
+
+bool at_al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+int attention256_choose(const void *qk, int64_t ld_qk, const void *vt, const void *bias_v, const void *s_qk, const void *s_v, const void *out,
+                        int B, int tokens, int C, AtRoute &r) {
+  using idiff::fail;
+  r = AT_NONE;
+  if (B == 0) return 0;
+  if (tokens != AT_T || (C != 128 && C != 256) || B < 0 || B > (1 << 20))
+    return fail("attention256: tokens must be 256 and channels 128 or 256 (got %d tokens, %d channels, batch %d)", tokens, C, B);
+  if (!qk || !vt || !out || !s_qk || !s_v) return fail("attention256: null pointer");
+  if (ld_qk < 2 * C || ld_qk % 4) return fail("attention256: the q|k row pitch must be >= 2 C and a multiple of 4 (got %lld)", (long long)ld_qk);
+  if (!at_al16(qk) || !at_al16(vt) || !at_al16(out) || (bias_v && !at_al16(bias_v)))
+    return fail("attention256: qk, vt, bias_v and out must be 16-byte aligned");
+  r = C == 256 ? AT_C256 : AT_C128;
+  return 0;
+}
+
+int attention_heads_choose(const void *qk, int64_t ld_qk, const void *vt, const void *bias_v, const void *s_qk, const void *s_v, const void *out,
+                           int B, int tokens, int H, int D, AtRoute &r) {
+  using idiff::fail;
+  r = AT_NONE;
+  if (B == 0) return 0;
+  if (!attention_heads_shape_ok(B, tokens, H, D))
+    return fail("attention_heads: heads of 32, 64 or 128 channels, H D <= 1024, tokens a multiple of 64 in [64, 4096], B H <= 2^20 "
+                "(got batch %d, %d tokens, %d heads of %d)", B, tokens, H, D);
+  const int C = H * D;
+  if (!qk || !vt || !out || !s_qk || !s_v) return fail("attention_heads: null pointer");
+  if (ld_qk < 2 * C || ld_qk % 4) return fail("attention_heads: the q|k row pitch must be >= 2 C and a multiple of 4 (got %lld)", (long long)ld_qk);
+  if (!at_al16(qk) || !at_al16(vt) || !at_al16(out) || (bias_v && !at_al16(bias_v)))
+    return fail("attention_heads: qk, vt, bias_v and out must be 16-byte aligned");
+  const bool wide = tokens % 128 == 0;           // eight waves of 16 queries; four where the token count is an odd multiple of 64
+  r = D == 32 ? (wide ? AH_32_8 : AH_32_4) : D == 64 ? (wide ? AH_64_8 : AH_64_4) : (wide ? AH_128_8 : AH_128_4);
+  return 0;
+}
+
 }  // namespace
 
 IDIFF_API int idiff_attention256_ok(int B, int tokens, int C) {
@@ -526,16 +569,18 @@ IDIFF_API int idiff_attention256_ok(int B, int tokens, int C) {
 
 IDIFF_API int idiff_attention256_f32(const float *qk, int64_t ld_qk, const float *vt, const float *bias_v, const float *s_qk, const float *s_v,
                                      float *out, int B, int tokens, int C, float scale, void *stream) {
-  using namespace idiff;
-  if (B == 0) return 0;
-  if (tokens != AT_T || (C != 128 && C != 256) || B < 0 || B > (1 << 20))
-    return fail("attention256: tokens must be 256 and channels 128 or 256 (got %d tokens, %d channels, batch %d)", tokens, C, B);
-  if (!qk || !vt || !out || !s_qk || !s_v) return fail("attention256: null pointer");
-  if (ld_qk < 2 * C || ld_qk % 4) return fail("attention256: the q|k row pitch must be >= 2 C and a multiple of 4 (got %lld)", (long long)ld_qk);
-  if (((uintptr_t)qk & 15) || ((uintptr_t)vt & 15) || ((uintptr_t)out & 15) || (bias_v && ((uintptr_t)bias_v & 15)))
-    return fail("attention256: qk, vt, bias_v and out must be 16-byte aligned");
+  AtRoute r;
+  if (int rc = attention256_choose(qk, ld_qk, vt, bias_v, s_qk, s_v, out, B, tokens, C, r)) return rc;
+  if (r == AT_NONE) return 0;
   AttnParams p = {qk, vt, bias_v, s_qk, s_v, out, ld_qk, B, scale};
-  return C == 256 ? launch_attention<256>(p, (hipStream_t)stream) : launch_attention<128>(p, (hipStream_t)stream);
+  return r == AT_C256 ? launch_attention<256>(p, (hipStream_t)stream) : launch_attention<128>(p, (hipStream_t)stream);
+}
+
+IDIFF_API const char *idiff_attention256_route(const void *qk, int64_t ld_qk, const void *vt, const void *bias_v, const void *s_qk, const void *s_v,
+                                               const void *out, int B, int tokens, int C) {
+  AtRoute r;
+  if (attention256_choose(qk, ld_qk, vt, bias_v, s_qk, s_v, out, B, tokens, C, r)) return nullptr;
+  return kAtRouteNames[r];
 }
 
 IDIFF_API int idiff_attention_heads_ok(int B, int tokens, int H, int D) {
@@ -546,22 +591,24 @@ IDIFF_API int idiff_attention_heads_ok(int B, int tokens, int H, int D) {
 
 IDIFF_API int idiff_attention_heads_f32(const float *qk, int64_t ld_qk, const float *vt, const float *bias_v, const float *s_qk, const float *s_v,
                                         float *out, int B, int tokens, int H, int D, float scale, void *stream) {
-  using namespace idiff;
-  if (B == 0) return 0;
-  if (!attention_heads_shape_ok(B, tokens, H, D))
-    return fail("attention_heads: heads of 32, 64 or 128 channels, H D <= 1024, tokens a multiple of 64 in [64, 4096], B H <= 2^20 "
-                "(got batch %d, %d tokens, %d heads of %d)", B, tokens, H, D);
-  const int C = H * D;
-  if (!qk || !vt || !out || !s_qk || !s_v) return fail("attention_heads: null pointer");
-  if (ld_qk < 2 * C || ld_qk % 4) return fail("attention_heads: the q|k row pitch must be >= 2 C and a multiple of 4 (got %lld)", (long long)ld_qk);
-  if (((uintptr_t)qk & 15) || ((uintptr_t)vt & 15) || ((uintptr_t)out & 15) || (bias_v && ((uintptr_t)bias_v & 15)))
-    return fail("attention_heads: qk, vt, bias_v and out must be 16-byte aligned");
+  AtRoute r;
+  if (int rc = attention_heads_choose(qk, ld_qk, vt, bias_v, s_qk, s_v, out, B, tokens, H, D, r)) return rc;
+  if (r == AT_NONE) return 0;
   HeadsParams p = {qk, vt, bias_v, s_qk, s_v, out, ld_qk, B, tokens, H, scale};
   hipStream_t st = (hipStream_t)stream;
-  const bool wide = tokens % 128 == 0;           // eight waves of 16 queries; four where the token count is an odd multiple of 64
-  switch (D) {
-    case 32: return wide ? launch_attention_heads<32, 8>(p, st) : launch_attention_heads<32, 4>(p, st);
-    case 64: return wide ? launch_attention_heads<64, 8>(p, st) : launch_attention_heads<64, 4>(p, st);
-    default: return wide ? launch_attention_heads<128, 8>(p, st) : launch_attention_heads<128, 4>(p, st);
+  switch (r) {
+    case AH_32_4: return launch_attention_heads<32, 4>(p, st);
+    case AH_32_8: return launch_attention_heads<32, 8>(p, st);
+    case AH_64_4: return launch_attention_heads<64, 4>(p, st);
+    case AH_64_8: return launch_attention_heads<64, 8>(p, st);
+    case AH_128_4: return launch_attention_heads<128, 4>(p, st);
+    default: return launch_attention_heads<128, 8>(p, st);
   }
+}
+
+IDIFF_API const char *idiff_attention_heads_route(const void *qk, int64_t ld_qk, const void *vt, const void *bias_v, const void *s_qk,
+                                                  const void *s_v, const void *out, int B, int tokens, int H, int D) {
+  AtRoute r;
+  if (attention_heads_choose(qk, ld_qk, vt, bias_v, s_qk, s_v, out, B, tokens, H, D, r)) return nullptr;
+  return kAtRouteNames[r];
 }

@@ -436,6 +436,15 @@ int idiff_attention_heads_ok(int B, int tokens, int H, int D);
 int idiff_attention_heads_f32(const float *qk, int64_t ld_qk, const float *vt, const float *bias_v, const float *s_qk, const float *s_v,
                               float *out, int B, int tokens, int H, int D, float scale, void *stream);
 
+/* The kernel instantiation idiff_attention256_f32 / idiff_attention_heads_f32 would launch (the same admission code; the pointers are only
+ * inspected for null and 16-byte alignment): "attention256<128>" / "attention256<256>"; "heads<D,NW>" with D in {32, 64, 128} and NW = 8
+ * waves of 16 queries where tokens is a multiple of 128, else 4; "none" when B == 0 (nothing to launch).  NULL for arguments the launcher
+ * refuses (idiff_last_error says why).  Launches nothing; no reference counterpart. */
+const char *idiff_attention256_route(const void *qk, int64_t ld_qk, const void *vt, const void *bias_v, const void *s_qk, const void *s_v,
+                                     const void *out, int B, int tokens, int C);
+const char *idiff_attention_heads_route(const void *qk, int64_t ld_qk, const void *vt, const void *bias_v, const void *s_qk, const void *s_v,
+                                        const void *out, int B, int tokens, int H, int D);
+
 /* y = act(a * alpha + beta_const) elementwise; covers `2*x - 1` (models/ncsnpp.py:264-266), SiLU/ELU of the
  * time embedding, and -out/std when `rowscale` ([n / inner]) is given: y = act(...) * rowscale[i / inner]. */
 int idiff_affine_act_f32(const float *a, float *y, int64_t n, float alpha, float beta_const, int act,
