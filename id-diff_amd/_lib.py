@@ -169,6 +169,9 @@ _SIGNATURES = {
     "idiff_sampler_step_f32": (c_i, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64, c_i, c_d, c_d, c_d, c_p, c_d, c_d,
                                      ctypes.c_uint64, c_i64, c_i, c_f, c_p]),
     "idiff_sampler_noise_norm_f32": (c_i, [c_p, c_i64, c_i64, c_i, ctypes.c_uint64, c_i64, c_p, c_p, c_p]),
+    "idiff_jvp_layer_ok": (c_i, [c_i, c_i, c_i]),
+    "idiff_jvp_seed_f32": (c_i, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64, c_i, c_i, c_i, c_p]),
+    "idiff_jvp_layer_f32": (c_i, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64, c_i, c_i, c_i, c_i, c_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -1767,6 +1770,76 @@ def fcn_train_input(x, z, std, mean_coeff, label, h):
     _check(lib().idiff_fcn_train_input_f32(x.data_ptr(), z.data_ptr(), std.data_ptr(), _ptr(mean_coeff), label.data_ptr(), h.data_ptr(),
                                            B, D, h.shape[1], _stream()), "idiff_fcn_train_input_f32")
     return h
+
+
+# ------------------------------------------------------------------------------------------- Jacobian of the fcn score network
+def jvp_layer_ok(R, N, K):
+    """True where jvp_layer serves R tangent rows a point, N outputs and K inputs (idiff_jvp_layer_ok: host only)."""
+    return bool(lib().idiff_jvp_layer_ok(int(R), int(N), int(K)))
+
+
+def _points3(t, name):
+    """(P, rows, cols, ld, point stride) of a [P, rows, cols] (or [rows, cols]: one point) fp32 tensor with contiguous rows."""
+    _dev(t, name, contiguous=False)
+    if t.ndim == 2:
+        t = t.unsqueeze(0)
+    if t.ndim != 3 or t.stride(2) != 1:
+        raise RuntimeError(f"{name}: expected [P, rows, cols] with contiguous rows, got shape {tuple(t.shape)} strides {t.stride()}")
+    P, rows, cols = t.shape
+    ld = t.stride(1) if rows > 1 else max(t.stride(1), (cols + 3) // 4 * 4)
+    return P, rows, cols, ld, (t.stride(0) if P > 1 else max(t.stride(0), rows * ld))
+
+
+def jvp_seed(w1, act, D=None, out=None, P=None, N=None, ldw=None, ld_act=None, ldt=None, stride_t=None):
+    """out[p][i, n] = w1[n, i] * g(act[p, n]) for i < D: the tangent rows of the D input directions behind the first Linear + ELU, with
+    ``w1`` [N, > D] that Linear's weight as it lies (its columns from D on, the time column and the pads, are never read), ``act`` [P, N]
+    the ELU OUTPUT of the P points and g(a) = 1 if a > 0 else a + 1.  Tensors with contiguous rows (``out`` [P, D, N]; a row stride is the
+    leading dimension), or explicit geometry.  One fp32 multiply per element: bit-equal to fl(w1 * fl(a + 1))."""
+    _dev(w1, "w1", contiguous=False); _dev(act, "act", contiguous=False)
+    if P is None:
+        if D is None or act.ndim != 2 or w1.ndim != 2 or w1.shape[0] != act.shape[1] or w1.shape[1] < D:
+            raise RuntimeError(f"jvp_seed: w1 {tuple(w1.shape)}, act {tuple(act.shape)}, D = {D}")
+        (P, N), ldw, ld_act = act.shape, _ld(w1, "w1"), _ld(act, "act")
+    if out is None:
+        out = torch.empty(P, D, N, device=act.device, dtype=torch.float32)
+    _dev(out, "out", contiguous=False)
+    if ldt is None:
+        Po, Do, No, ldt, stride_t = _points3(out, "out")
+        if (Po, Do, No) != (P, D, N):
+            raise RuntimeError(f"jvp_seed: out {tuple(out.shape)} for P = {P}, D = {D}, N = {N}")
+    _check(lib().idiff_jvp_seed_f32(w1.data_ptr(), ldw, act.data_ptr(), ld_act, out.data_ptr(), ldt, stride_t, P, D, N, _stream()),
+           "idiff_jvp_seed_f32")
+    return out
+
+
+def jvp_layer(a, w, act=None, out=None, P=None, R=None, N=None, K=None, lda=None, stride_a=None, ldw=None, ld_act=None, ldc=None,
+              stride_c=None):
+    """out[p] = (a[p] @ w.T) * g(act[p]) with g broadcast over the rows of point p: one layer of the forward-mode Jacobian.  ``a``
+    [P, R, K] the tangent rows, ``w`` [N, K] an nn.Linear weight as it lies, ``act`` [P, N] the layer's ELU OUTPUT (None: no factor, the
+    output layer), g(a) = 1 if a > 0 else a + 1.  Tensors with contiguous rows (row and point strides are taken from them), or explicit
+    geometry.  Exact fp32 on the matrix cores, bit-reproducible; a point's bits do not depend on the other points."""
+    _dev(a, "a", contiguous=False); _dev(w, "w", contiguous=False)
+    if P is None:
+        P, R, K, lda, stride_a = _points3(a, "a")
+        if w.ndim != 2 or w.shape[1] != K:
+            raise RuntimeError(f"jvp_layer: inner dimensions differ: {tuple(a.shape)} x {tuple(w.shape)}^T")
+        N, ldw = w.shape[0], _ld(w, "w")
+    if act is not None:
+        _dev(act, "act", contiguous=False)
+        if ld_act is None:
+            if act.ndim != 2 or tuple(act.shape) != (P, N):
+                raise RuntimeError(f"jvp_layer: act {tuple(act.shape)} for P = {P}, N = {N}")
+            ld_act = _ld(act, "act")
+    if out is None:
+        out = torch.empty(P, R, N, device=a.device, dtype=torch.float32)
+    _dev(out, "out", contiguous=False)
+    if ldc is None:
+        Po, Ro, No, ldc, stride_c = _points3(out, "out")
+        if (Po, Ro, No) != (P, R, N):
+            raise RuntimeError(f"jvp_layer: out {tuple(out.shape)} for P = {P}, R = {R}, N = {N}")
+    _check(lib().idiff_jvp_layer_f32(a.data_ptr(), lda, stride_a, w.data_ptr(), ldw, _ptr(act), ld_act or 0, out.data_ptr(), ldc, stride_c,
+                                     P, R, N, K, _stream()), "idiff_jvp_layer_f32")
+    return out
 
 
 def _pitch(t, name, B, D):

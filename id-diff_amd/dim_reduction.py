@@ -375,6 +375,43 @@ def _tangent_refused(config, world):
                                   "the exchange of variable-width bases between ranks is not implemented")
 
 
+METHODS = ('sampling', 'jacobian')
+
+
+def estimation_method(config, method=None):
+    """'sampling' (the default: the score matrix of a perturbed cloud) or 'jacobian' (jacobian.py: the score Jacobian of an fcn network in
+    closed form); the argument wins over the config key ``dim_estimation.method``.  Anything else is a ValueError."""
+    if method is None:
+        method = config.get('dim_estimation.method', None)
+    method = 'sampling' if method is None else str(method)
+    if method not in METHODS:
+        raise ValueError(f"dim_estimation.method = {method!r}: one of {METHODS}")
+    return method
+
+
+def _jacobian_refused(config, world):
+    """method = 'jacobian' is a one-rank mode: a hundred D x D Jacobians are a fraction of a second of one GPU."""
+    if world > 1 or str(config.get('dim_estimation.shard', 'points')) == 'rows':
+        raise NotImplementedError("dim_estimation.method = 'jacobian' needs a single rank and dim_estimation.shard = 'points' (got world "
+                                  f"size {world}, shard = {config.get('dim_estimation.shard', 'points')!r}): the Jacobian method has no "
+                                  "score rows to shard and its points are not distributed over ranks")
+
+
+def _points_by_jacobian(pl_module, points, device, want_tangent):
+    """The spectra, IDs and (``want_tangent``) tangent bases of ``points`` from the score Jacobian of the module's fcn network:
+    -> (info, dims, tangent or None) as ``deliver`` takes them."""
+    from . import jacobian
+    xs = torch.stack([x.reshape(-1) for x, _ in points]).to(device=device, dtype=torch.float32).contiguous()
+    J = jacobian.network_jacobians(pl_module, pl_module.sde, xs, pl_module.sampling_eps)
+    sv = checked_spectra(jacobian._spectra_from(J)).numpy()
+    tangent = None
+    if want_tangent:
+        dims, tangent = jacobian._tangents(J, sv)
+    else:
+        dims = jacobian.dims_from_spectra(sv).tolist()
+    return {'singular_values': sv.tolist()}, [int(d) for d in dims], tangent
+
+
 def _sv_count(sample_shape, batchsize):
     """torch.linalg.svd returns min(M, D) values per point (dim_reduction.py:197): a short loader batch gives a shorter list."""
     return min(batching(tuple(sample_shape), batchsize)[2], math.prod(sample_shape))
@@ -492,7 +529,7 @@ def collect_points(loader, num_datapoints):
     return pts
 
 
-def get_manifold_dimension(config, name=None, return_svd=False, return_dims=False, return_tangent=False):
+def get_manifold_dimension(config, name=None, return_svd=False, return_dims=False, return_tangent=False, method=None):
     """Drop-in for dim_reduction.py:116-215.  ``return_dims=True`` (not in the reference; needs ``return_svd``) also
     returns the integer ID of every point, computed by the reference's rule on the rank that owns the point and gathered
     as int32 in the same collective as the spectra.
@@ -508,10 +545,21 @@ def get_manifold_dimension(config, name=None, return_svd=False, return_dims=Fals
     ``{'tangent': [...], 'dims': [...]}`` beside the unchanged ``<name>.pkl``.
 
     The row-sharded mode (``dim_estimation.shard = 'rows'`` on more than one rank) does not serve ``return_dims``: it returns
-    ``info`` alone."""
+    ``info`` alone.
+
+    ``method`` (or the config key ``dim_estimation.method``; the argument wins): 'sampling', the default, is everything above.
+    'jacobian' (``model.name == 'fcn'`` without dropout, one rank, ``shard = 'points'``; NotImplementedError otherwise, before the
+    GPU is touched) takes the same points and returns or writes the same layout, but its singular values are those of the score
+    Jacobian at mean(t) x in closed form (jacobian.py), which the spectrum of the sampled score matrix estimates up to the factor
+    std(t) sqrt(M); dims and tangent bases are read off them by the same rules."""
+    method = estimation_method(config, method)
     log_path, log_name = config.logging.log_path, config.logging.log_name
     save_path = os.path.join(log_path, log_name, 'svd')
     rank, world = parallel.rank_world()
+    if method == 'jacobian':
+        from . import jacobian
+        jacobian.check_config(config)
+        _jacobian_refused(config, world)
     if return_tangent and not return_svd:
         raise ValueError("return_tangent needs return_svd=True (set dim_estimation.save_tangent to have the bases written to disk)")
     save_tangent = not return_svd and bool(config.get('dim_estimation.save_tangent', False))
@@ -539,6 +587,8 @@ def get_manifold_dimension(config, name=None, return_svd=False, return_dims=Fals
     points = collect_points(DataModule.train_dataloader(), num_datapoints)
     if not points:                       # num_datapoints <= 1: the reference's loop body never runs (:159-164)
         return deliver({'singular_values': []}, [], [])
+    if method == 'jacobian':
+        return deliver(*_points_by_jacobian(pl_module, points, device, return_tangent or save_tangent))
     builder = ScoreMatrixBuilder(score_fn, pl_module.sde, pl_module.sampling_eps, device,
                                  config.get('dim_estimation.inflight_rows', None))
     def point_seed(p):

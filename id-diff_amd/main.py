@@ -16,6 +16,10 @@ Run it from the repo root as ``python id-diff_amd/main.py ...`` or, for several 
 ``--mode manifold_dimension`` with the config key ``dim_estimation.save_tangent = True`` (not in the reference; default False, one
 GPU only) also writes ``<log_path>/<log_name>/svd/<log_name>_tangent.pkl`` = ``{'tangent': [...], 'dims': [...]}``: per point the
 [D, d] float32 basis of its estimated tangent space, or None (``dim_reduction.get_manifold_dimension``).
+
+``--mode manifold_dimension`` with the config key ``dim_estimation.method = 'jacobian'`` (or ``--dim_method jacobian``; not in the
+reference; default 'sampling') writes the same pickle for the same points from the score Jacobian of an ``fcn`` network in closed form
+instead of the score matrix of a perturbed cloud (jacobian.py): no sampling noise, one GPU, ``model.dropout == 0``.
 """
 import argparse
 import os
@@ -58,6 +62,9 @@ def parse(argv=None):
                          "estimated dimension (0: never)")
     ap.add_argument("--num_samples", type=int, default=None, help="(--mode generate) number of samples to draw (default 1000)")
     ap.add_argument("--seed", type=int, default=None, help="(--mode generate) seed of the noise streams (default: config.seed)")
+    ap.add_argument("--dim_method", default=None, choices=("sampling", "jacobian"),
+                    help="(--mode manifold_dimension) sets the config key dim_estimation.method: 'sampling' (default) or 'jacobian', the "
+                         "score Jacobian of an fcn network in closed form (one GPU)")
     return ap.parse_args(argv)
 
 
@@ -98,6 +105,8 @@ def main(argv=None):
         config.model.checkpoint_path = flags.checkpoint_path
     if flags.allow_random_init:
         config.model.allow_random_init = True
+    if flags.dim_method is not None:
+        config['dim_estimation.method'] = flags.dim_method
     if flags.mode == 'train':
         run_train(flags, config)
         return

@@ -820,6 +820,31 @@ int idiff_sampler_step_f32(const float *x, int64_t ldx, const float *s, int64_t 
 int idiff_sampler_noise_norm_f32(const float *z, int64_t ldz, int64_t B, int D, uint64_t seed, int64_t row0, double *ws, double *out,
                                  void *stream);
 
+/* ------------------------------------------------------------------ Jacobian of the fcn score network (csrc/fcn_jacobian.hip) */
+
+/* Forward-mode propagation of a point's D input directions through Linear + ELU layers: D tangent rows per point.  g(a) = a > 0 ? 1 :
+ * a + 1 is ELU' written in terms of the ELU OUTPUT a (as idiff_gemm_nn_f32 has it); here it belongs to a (point, column) pair and is
+ * broadcast over the point's rows.
+ *
+ *   jvp_seed:   T[p][i, n] = W1[n, i] g(act[p, n]),  i < D, n < N.  W1 [N, ldw] is the first Linear's weight as it lies; its columns from
+ *               D on (the time column, the pads) are never read.  act [P, ld_act]; T [P][D, ldt] with point stride strideT.  One fp32
+ *               multiply per element after the one rounding of a + 1: bit-equal to fl(W1 fl(a + 1)).
+ *   jvp_layer:  C[p][r, n] = (sum_k A[p][r, k] W[n, k]) g(act[p, n]).  A [P][R, lda] with point stride strideA, W [N, ldw] K-contiguous (an
+ *               nn.Linear weight as it lies), act [P, ld_act] or NULL (no factor: the output layer), C [P][R, ldc] with point stride
+ *               strideC.  On v_mfma_f32_32x32x2_f32, a k-ordered chain of fp32 fmas:
+ *               |C - exact| <= g (K + 2) 2^-24 sum_k |a_k w_k| + 2 2^-24 |exact| (the roundings of a + 1 and of the multiply).  No split of
+ *               K, no atomics, no workspace: the same bits on every run, and a point's bits do not depend on the other points of the launch.
+ *               Pads of C (columns N .. ldc) and rows from R on are not written.
+ *
+ * Any P >= 0 (P = 0 is a no-op) and R, D, N, K >= 1.  Pointers 16-byte aligned; leading dimensions and point strides multiples of 4 floats,
+ * leading dimensions at least the row length; IDIFF_EINVAL before any device call otherwise, with a message that starts "jvp_seed: " /
+ * "jvp_layer: ".  idiff_jvp_layer_ok (host only): 1 for the sizes served. */
+int idiff_jvp_layer_ok(int R, int N, int K);
+int idiff_jvp_seed_f32(const float *W1, int64_t ldw, const float *act, int64_t ld_act, float *T, int64_t ldt, int64_t strideT, int P, int D,
+                       int N, void *stream);
+int idiff_jvp_layer_f32(const float *A, int64_t lda, int64_t strideA, const float *W, int64_t ldw, const float *act, int64_t ld_act,
+                        float *C, int64_t ldc, int64_t strideC, int P, int R, int N, int K, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
