@@ -80,6 +80,8 @@ _SIGNATURES = {
     "idiff_conv2d_wino1d_gn_ok": (c_i, [c_i] * 6),
     "idiff_conv2d_wino1d_normload_ok": (c_i, [c_i] * 5),
     "idiff_conv2d_wino1d_normload_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(Epilogue), c_p, c_i, c_p]),
+    "idiff_conv2d_wino1d_normload_2src_ok": (c_i, [c_i] * 6),
+    "idiff_conv2d_wino1d_normload_2src_f32": (c_i, [c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_i, ctypes.POINTER(Epilogue), c_p, c_i, c_p]),
     "idiff_groupnorm_coef_f32": (c_i, [c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p]),
     "idiff_conv2d_wino1d_gn_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(Epilogue), c_i, c_p, c_p, c_f, c_i, c_p]),
     "idiff_conv2d_winograd_split_ok": (c_i, [c_i] * 5),
@@ -323,10 +325,22 @@ def with_normload(ep, coef, act):
     return ep
 
 
+def with_normload_2src(ep, coef, act, x2, C1):
+    """with_normload for a convolution of cat[x, x2] along the channels that is never made: the launch's ``x`` is the first source
+    [B, H*W, C1], ``x2`` the second [B, H*W, Cin - C1], ``coef`` [B, Cin, 2] from groupnorm_coef_2src.  A request of its own (``normload2``,
+    never ``normload``): conv2d_wino1d serves it through idiff_conv2d_wino1d_normload_2src_f32, every other wrapper refuses it."""
+    _dev(coef, "coef"); _dev(x2, "x2")
+    ep.normload2 = (coef, ACT[act], x2, int(C1))
+    return ep
+
+
 def _ep_ref(epilogue, what):
     """The epilogue argument of a launch that has no fused GroupNorm: such a request is an error, never dropped."""
     if epilogue is None:
         return None
+    if getattr(epilogue, "normload2", None) is not None:
+        raise RuntimeError(f"{what}: the epilogue asks for a GroupNorm of two sources in the loader (with_normload_2src), which only "
+                           "conv2d_wino1d serves")
     if getattr(epilogue, "normload", None) is not None:
         raise RuntimeError(f"{what}: the epilogue asks for a GroupNorm in the loader (with_normload), which only conv2d_wino1d serves")
     if getattr(epilogue, "groupnorm", None) is not None:
@@ -565,6 +579,18 @@ def _wino_conv(stem, packed_by, x, u, out, B, H, W, Cin, Cout, epilogue):
         raise RuntimeError(f"conv2d_{stem}: a filter bank of {u.numel()} floats ({want} expected): pack it with {packed_by}")
     gn = getattr(epilogue, "groupnorm", None)
     nl = getattr(epilogue, "normload", None)
+    nl2 = getattr(epilogue, "normload2", None)
+    if nl2 is not None and stem == "wino1d":
+        if gn is not None or nl is not None:
+            raise RuntimeError("conv2d_wino1d: a two-source GroupNorm in the loader (with_normload_2src) beside another GroupNorm request "
+                               "(with_normload / with_groupnorm) in one launch")
+        coef, act, x2, C1 = nl2
+        if coef.numel() != B * Cin * 2:
+            raise RuntimeError(f"conv2d_wino1d: {coef.numel()} loader coefficients for [B, Cin, 2] = [{B}, {Cin}, 2]")
+        _check(lib().idiff_conv2d_wino1d_normload_2src_f32(x.data_ptr(), C1, x2.data_ptr(), Cin - C1, u.data_ptr(), out.data_ptr(), B, H, W, Cout,
+                                                           ctypes.byref(epilogue), coef.data_ptr(), act, _stream()),
+               "idiff_conv2d_wino1d_normload_2src_f32")
+        return out
     if nl is not None and stem == "wino1d":
         if gn is not None:
             raise RuntimeError("conv2d_wino1d: a GroupNorm in the loader (with_normload) and one in the tail (with_groupnorm) in one launch")
@@ -660,6 +686,22 @@ def conv2d_wino1d_normload_ok(B, H, W, Cin, Cout):
     return bool(lib().idiff_conv2d_wino1d_normload_ok(B, H, W, Cin, Cout))
 
 
+def conv2d_wino1d_normload_2src_ok(B, H, W, C1, C2, Cout):
+    """The same for cat[x1, x2] read from its two sources (with_normload_2src): whole K steps (16 channels) from each; off under
+    IDIFF_NO_FUSED_GN_LOAD_2SRC (not under IDIFF_NO_FUSED_GN_LOAD), IDIFF_NO_PAIRS and wherever conv2d_wino1d_ok is."""
+    return bool(lib().idiff_conv2d_wino1d_normload_2src_ok(B, H, W, C1, C2, Cout))
+
+
+def groupnorm_coef_2src(ws1, ns1, C1, ws2, ns2, C2, B, HW, G, eps, gamma, beta, coef):
+    """groupnorm_coef for the two-source loader: coef [B, C1 + C2, 2] of GroupNorm(cat[x1, x2]) from both producers' column sums."""
+    _dev(coef, "coef"); _dev(gamma, "gamma"); _dev(beta, "beta")
+    if ws2 is None or coef.numel() != B * (C1 + C2) * 2:
+        raise RuntimeError(f"groupnorm_coef_2src: both sources' column sums and coef [B, C1 + C2, 2] = {B * (C1 + C2) * 2} floats are required")
+    _check(lib().idiff_groupnorm_coef_f32(ws1.data_ptr(), ns1, C1, ws2.data_ptr(), ns2, C2, B, HW, G, eps, gamma.data_ptr(), beta.data_ptr(),
+                                          coef.data_ptr(), _stream()), "idiff_groupnorm_coef_f32")
+    return coef
+
+
 def groupnorm_coef(ws1, ns1, C1, ws2, ns2, C2, B, HW, G, eps, gamma, beta, coef):
     """coef [B, C1 + C2, 2] = (rstd gamma, beta - mean rstd gamma) from the producers' column sums (one launch, no pass over the activations)."""
     _dev(coef, "coef"); _dev(gamma, "gamma"); _dev(beta, "beta")
@@ -676,7 +718,8 @@ def wino1d_pack(wt, Cin, Cout):
 
 
 def conv2d_wino1d(x, u, out, B, H, W, Cin, Cout, epilogue=None):
-    """``epilogue`` may carry a GroupNorm request (with_groupnorm): the launch then stores act(GroupNorm(conv + bias + rowbias))."""
+    """``epilogue`` may carry a GroupNorm request (with_groupnorm): the launch then stores act(GroupNorm(conv + bias + rowbias)); or one for
+    the loader (with_normload; with_normload_2src: ``x`` is then the first source, ``Cin`` the total and the second travels in the request)."""
     return _wino_conv("wino1d", "wino1d_pack", x, u, out, B, H, W, Cin, Cout, epilogue)
 
 

@@ -116,6 +116,9 @@ struct Wino1dParams {
   const float *nl_coef;                            // wino1d_nl_kernel: [B][Cin][2] = (a, b) of the GroupNorm in FRONT of this convolution, x -> act(a x + b)
   uint32_t nl_bytes;
   float c_nb2, c_na2, c_nab2, c_a, c_b;            // the transform's constants as kernel arguments (SGPR operands of plain fmas)
+  const float *x2;                                 // wino1d_nl2_kernel: input channels [c1, Cin) come from x2 [B, H W, Cin - c1], [0, c1) from x [B, H W, c1]
+  uint32_t x2_bytes;
+  int c1;
 #ifdef IDIFF_W1D_STAMP
   uint64_t *stamps;                                // diagnostic build (scripts/wino1d_stamps.py): 8 ticks of 100 MHz per workgroup
 #endif
@@ -124,9 +127,12 @@ struct Wino1dParams {
 // GN: the tail of wino1d_gn_kernel (GroupNorm + activation of the output inside the workgroup) instead of the epilogue's switches
 // NL: the loader of wino1d_nl_kernel (0: none): the GroupNorm that PRODUCES the input, as one affine pair per (image, channel), (NL = 2:) + SiLU,
 //     applied to the pixel registers in front of B^T d; W = 32 only (a block is half an image: one image's coefficients per workgroup)
-template <int W, bool GN, int NL = 0>
+// S2: the loader of wino1d_nl2_kernel: the input is cat[x, x2] along the channels, never written -- a K step (16 channels) lies in ONE source
+//     (c1 % 16 == 0), so the source of a step is a wave-uniform choice of descriptor, channel offset and pitch; everything else is the NL kernel
+template <int W, bool GN, int NL = 0, bool S2 = false>
 __device__ __forceinline__ void r1_body(const Wino1dParams &p) {
   static_assert(NL == 0 || (W == 32 && !GN), "the norm in the loader: 32-pixel rows, the plain tail");
+  static_assert(!S2 || NL != 0, "two sources: only with the norm in the loader");
   using G = R1Geo<W>;
   constexpr int TPR = G::TPR, RB = G::RB, POS = G::POS_BYTES, BRING = R1_BRING;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -154,7 +160,7 @@ __device__ __forceinline__ void r1_body(const Wino1dParams &p) {
   const int wh = wave & 1, ph = wave >> 1;
 
   const __amdgpu_buffer_rsrc_t rU = __builtin_amdgcn_make_buffer_rsrc((void *)p.u, 0, (int)p.u_bytes, 0x00020000);
-  const uint32_t cin4 = (uint32_t)p.Cin * 4u;
+  const uint32_t cin4 = (uint32_t)(S2 ? p.c1 : p.Cin) * 4u;        // bytes per pixel (S2: of the first source)
   const int roww = W * (int)cin4;                                  // bytes per image row
   const int nsteps = p.Cin / R1_KC;
 
@@ -168,8 +174,15 @@ __device__ __forceinline__ void r1_body(const Wino1dParams &p) {
   constexpr int NPX = 4 * TS + 2;                                  // its pixels, the one to the left and the one to the right included
   const int lm = tid & 7, lk = tid >> 3;
   // base one pixel to the LEFT: offset v + j * cin4 is the segment's pixel j - 1 ... (the range check covers the vector offset only)
-  const __amdgpu_buffer_rsrc_t rXm = __builtin_amdgcn_make_buffer_rsrc((void *)(p.x - p.Cin), 0, (int)(p.x_bytes + cin4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rXm = __builtin_amdgcn_make_buffer_rsrc((void *)(p.x - (S2 ? p.c1 : p.Cin)), 0, (int)(p.x_bytes + cin4), 0x00020000);
   uint32_t v_main, v_halo;
+  // S2: the second source's pitch, descriptor (the same construction, its own extent) and per-lane offsets (pixel index * pitch + lm * 8:
+  // equal to the first source's only where c1 = Cin - c1), and the first K step that reads it
+  const uint32_t cin4b = S2 ? (uint32_t)(p.Cin - p.c1) * 4u : 0u;
+  const int n1 = S2 ? p.c1 / R1_KC : 0;
+  const __amdgpu_buffer_rsrc_t rXm2 =
+      __builtin_amdgcn_make_buffer_rsrc((void *)(S2 ? p.x2 - (p.Cin - p.c1) : p.x), 0, S2 ? (int)(p.x2_bytes + cin4b) : 0, 0x00020000);
+  uint32_t v_main2 = R1_INVALID, v_halo2 = R1_INVALID;
   bool m_l, m_r, h_c0, h_c5;
   int e_halo;
   {
@@ -187,6 +200,10 @@ __device__ __forceinline__ void r1_body(const Wino1dParams &p) {
     const bool valid = part && (top ? (row0 % p.H != 0) : ((row0 + RB) % p.H != 0 && row0 + RB < p.rows_total));
     v_halo = valid ? (uint32_t)hr * (uint32_t)roww + (uint32_t)(4 * tx) * cin4 + (uint32_t)lm * 8u : R1_INVALID;
     h_c0 = tx > 0; h_c5 = tx + 1 < TPR;
+    if constexpr (S2) {
+      if (rho < p.rows_total) v_main2 = (uint32_t)rho * (uint32_t)W * cin4b + (uint32_t)xf * cin4b + (uint32_t)lm * 8u;
+      if (valid) v_halo2 = (uint32_t)hr * (uint32_t)W * cin4b + (uint32_t)(4 * tx) * cin4b + (uint32_t)lm * 8u;
+    }
     e_halo = part ? (top ? tx : (RB + 1) * TPR + tx) : G::EZ;      // threads without a halo tile transform zeros into the zero entry
   }
   // does any lane of this wave hold a halo tile that is inside the image?  (W = 32: wave 0 the row above, wave 1 the row below; else wave 0 both)
@@ -201,7 +218,23 @@ __device__ __forceinline__ void r1_body(const Wino1dParams &p) {
     for (int j = 0; j < NPX; ++j) px[g][j] = f2{0.f, 0.f};
   uint32_t invalid_s = R1_INVALID;
   // pixels [j0, j1] of segment g for K step `step` (clamped: the last stages request their own step again, nobody reads it)
+  // S2: the (clamped) step's source, chosen by the wave-uniform `second` (scalar selects; one vector select for the lane's offset): the clamp
+  // stays inside the second source, whose last step is the convolution's last
   auto fetch_px = [&](int g, int j0, int j1, int step) __attribute__((always_inline)) {
+    if constexpr (S2) {
+      const int st = min(step, nsteps - 1);
+      const bool second = st >= n1;
+      const int choff = (second ? st - n1 : st) * (R1_KC * 4);
+      const int pitch = (int)(second ? cin4b : cin4);
+      const uint32_t vm = second ? v_main2 : v_main;
+      asm volatile("" : "+s"(invalid_s));
+#pragma unroll
+      for (int j = j0; j <= j1; ++j) {
+        const uint32_t vo = j == 0 ? (m_l ? vm : invalid_s) : (j == NPX - 1 ? (m_r ? vm : invalid_s) : vm);
+        px[g][j] = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(second ? rXm2 : rXm, (int)vo, choff + j * pitch, 0));
+      }
+      return;
+    }
     const int choff = min(step, nsteps - 1) * (R1_KC * 4);
     asm volatile("" : "+s"(invalid_s));
 #pragma unroll
@@ -212,6 +245,20 @@ __device__ __forceinline__ void r1_body(const Wino1dParams &p) {
     }
   };
   auto fetch_hp = [&](int j0, int j1, int step) __attribute__((always_inline)) {
+    if constexpr (S2) {
+      const int st = min(step, nsteps - 1);
+      const bool second = st >= n1;
+      const int choff = (second ? st - n1 : st) * (R1_KC * 4);
+      const int pitch = (int)(second ? cin4b : cin4);
+      const uint32_t vh = second ? v_halo2 : v_halo;
+      asm volatile("" : "+s"(invalid_s));
+#pragma unroll
+      for (int j = j0; j <= j1; ++j) {
+        const uint32_t vo = j == 0 ? (h_c0 ? vh : invalid_s) : (j == 5 ? (h_c5 ? vh : invalid_s) : vh);
+        hp[j] = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(second ? rXm2 : rXm, (int)vo, choff + j * pitch, 0));
+      }
+      return;
+    }
     const int choff = min(step, nsteps - 1) * (R1_KC * 4);
     asm volatile("" : "+s"(invalid_s));
 #pragma unroll
@@ -823,6 +870,11 @@ template <int NL>
 __global__ void __launch_bounds__(R1_THREADS)
 wino1d_nl_kernel(const Wino1dParams p) { r1_body<32, false, NL>(p); }
 
+// the same with the input cat[x, x2] read from its two sources (GroupNorm_0 of a residual block on the up path: the concatenation is never made)
+template <int NL>
+__global__ void __launch_bounds__(R1_THREADS)
+wino1d_nl2_kernel(const Wino1dParams p) { r1_body<32, false, NL, true>(p); }
+
 // U[i][ky] = sum_kx G[i][kx] g[ky][kx] in fp64 for one (cin, cout) pair
 __device__ __forceinline__ void r1_u_of_pair(const float *wt, int Cin, int cin, int cout, double (&U)[18]) {
   double Gm[6][3];
@@ -890,13 +942,23 @@ IDIFF_API int idiff_wino1d_pack_f32(const float *wt, float *u, int Cin, int Cout
 
 namespace {
 struct R1GroupNorm { int groups; const float *gamma, *beta; float eps; int act; };
-struct R1NormLoad { const float *coef; int act; };
+struct R1NormLoad { const float *coef; int act; const float *x2; int c1; };       // x2 != nullptr: two sources, x [.., c1] and x2 [.., Cin - c1]
 
-// the three entry points: gn == nullptr and nl == nullptr is idiff_conv2d_wino1d_f32
+// the four entry points: gn == nullptr and nl == nullptr is idiff_conv2d_wino1d_f32
 int r1_run(const float *x, const float *u, float *out, int B, int H, int W, int Cin, int Cout, const idiff_epilogue *ep, const R1GroupNorm *gn,
            const R1NormLoad *nl, void *stream) {
   using namespace idiff;
   if (B == 0) return 0;
+  const bool two = nl && nl->x2;
+  if (nl && (nl->x2 || nl->c1 != Cin)) {
+    // two sources: whole K steps from each, each inside one buffer descriptor of its own
+    const int C1 = nl->c1, C2 = Cin - nl->c1;
+    if (C1 <= 0 || C2 <= 0 || C1 % R1_KC || C2 % R1_KC)
+      return fail("conv2d_wino1d_normload_2src: C1 = %d and C2 = %d must be positive multiples of %d (a K step reads one source)", C1, C2, R1_KC);
+    if (B > 0 && H > 0 && W > 0 && (int64_t)B * H * W * (C1 > C2 ? C1 : C2) * 4 >= R1_X_LIMIT - 0x4000)
+      return fail("conv2d_wino1d_normload_2src: a source of B=%d H=%d W=%d C=%d is beyond one buffer descriptor", B, H, W, C1 > C2 ? C1 : C2);
+    if (!nl->x2 || ((uintptr_t)nl->x2 & 15)) return fail("conv2d_wino1d_normload_2src: x2 is required, 16-byte aligned");
+  }
   if (nl) {
     // nothing is launched unless a block's rows are one image's (one set of coefficients per workgroup)
     if (!r1_nl_geometry_ok(B, H, W, Cin, Cout))
@@ -935,6 +997,13 @@ int r1_run(const float *x, const float *u, float *out, int B, int H, int W, int 
 #ifdef IDIFF_W1D_STAMP
   { const char *e = getenv("IDIFF_W1D_STAMP_PTR"); p.stamps = e ? reinterpret_cast<uint64_t *>(strtoull(e, nullptr, 0)) : nullptr; }
 #endif
+  if (two) {
+    p.nl_coef = nl->coef; p.nl_bytes = (uint32_t)((int64_t)B * Cin * 8);
+    p.x2 = nl->x2; p.c1 = nl->c1;
+    p.x_bytes = (uint32_t)((int64_t)B * H * W * nl->c1 * 4); p.x2_bytes = (uint32_t)((int64_t)B * H * W * (Cin - nl->c1) * 4);
+    if (nl->act == IDIFF_ACT_SILU) return r1_launch<wino1d_nl2_kernel<2>>(p, "conv2d_wino1d_normload_2src", (hipStream_t)stream);
+    return r1_launch<wino1d_nl2_kernel<1>>(p, "conv2d_wino1d_normload_2src", (hipStream_t)stream);
+  }
   if (nl) {
     p.nl_coef = nl->coef; p.nl_bytes = (uint32_t)((int64_t)B * Cin * 8);
     if (nl->act == IDIFF_ACT_SILU) return r1_launch<wino1d_nl_kernel<2>>(p, "conv2d_wino1d_normload", (hipStream_t)stream);
@@ -983,6 +1052,8 @@ IDIFF_API int idiff_conv2d_wino1d_gn_f32(const float *x, const float *u, float *
 //   256 -> 256   917 + 4129 = 5046   against  16 + 4961 = 4977   (-1.4 %: inside the repetitions' spread -- not routed)
 // The K loop is 18 - 23 % slower with the norm's 96 units in it, whatever the class; the pass it replaces costs the same per input channel
 // while the loop's time grows with the cout tiles that stage the same input: one or two tiles win, four do not.
+// In config 3 one source only ever brings 128 -> 128 here: the 256 -> 128 and 384 -> 128 classes are GroupNorm_0 of cat[h, skip] on the up
+// path and reach the loader through the two-source form (idiff_conv2d_wino1d_normload_2src_ok, at the end of this file).
 IDIFF_API int idiff_conv2d_wino1d_normload_ok(int B, int H, int W, int Cin, int Cout) {
   using namespace idiff;
   if (option(OPT_NO_WINOGRAD) || option(OPT_NO_WINO43H) || option(OPT_NO_WINO1D) || option(OPT_NO_PAIRS) || option(OPT_NO_FUSED_GN_LOAD)) return 0;
@@ -992,6 +1063,29 @@ IDIFF_API int idiff_conv2d_wino1d_normload_ok(int B, int H, int W, int Cin, int 
 
 IDIFF_API int idiff_conv2d_wino1d_normload_f32(const float *x, const float *u, float *out, int B, int H, int W, int Cin, int Cout,
                                                const idiff_epilogue *ep, const float *coef, int act, void *stream) {
-  const R1NormLoad nl = {coef, act};
+  const R1NormLoad nl = {coef, act, nullptr, Cin};
   return r1_run(x, u, out, B, H, W, Cin, Cout, ep, nullptr, &nl, stream);
+}
+
+// The two-source form: GroupNorm_0 of cat[h, skip] in the level-0 blocks of config 3's up path -- the 256 -> 128 and 384 -> 128 classes of the
+// table above reach the loader only through it (one source never has them there).  Routed class by class as the one-source form is
+// (scripts/normload2_shape_ab.py, profiles/normload2_shape_ab.txt: {two-source groupnorm_apply_colstats + conv2d_wino1d on the concatenated
+// output} against {coefficients + this}, B = 2240, 32 x 32, median us):
+//   128 + 128 -> 128   929 + 2081 = 3010   against  16 + 2607 = 2623   (-12.8 %, spread 190)
+//   256 + 128 -> 128  1371 + 2994 = 4366   against  23 + 3720 = 3743   (-14.3 %, spread 133)
+// both beyond the repetitions' spread: at most two cout tiles are routed, as for one source (four were never a gain there).
+// IDIFF_NO_FUSED_GN_LOAD_2SRC answers no, IDIFF_NO_FUSED_GN_LOAD does not bear on it.
+IDIFF_API int idiff_conv2d_wino1d_normload_2src_ok(int B, int H, int W, int C1, int C2, int Cout) {
+  using namespace idiff;
+  if (option(OPT_NO_WINOGRAD) || option(OPT_NO_WINO43H) || option(OPT_NO_WINO1D) || option(OPT_NO_PAIRS) || option(OPT_NO_FUSED_GN_LOAD_2SRC)) return 0;
+  if (C1 <= 0 || C2 <= 0 || C1 % R1_KC || C2 % R1_KC || !r1_nl_geometry_ok(B, H, W, C1 + C2, Cout)) return 0;
+  return Cout / R1_COUT <= 2 ? 1 : 0;
+}
+
+IDIFF_API int idiff_conv2d_wino1d_normload_2src_f32(const float *x1, int C1, const float *x2, int C2, const float *u, float *out, int B, int H,
+                                                    int W, int Cout, const idiff_epilogue *ep, const float *coef, int act, void *stream) {
+  if (C1 <= 0 || C2 <= 0)
+    return idiff::fail("conv2d_wino1d_normload_2src: C1 = %d and C2 = %d must be positive multiples of %d (a K step reads one source)", C1, C2, R1_KC);
+  const R1NormLoad nl = {coef, act, x2, C1};
+  return r1_run(x1, u, out, B, H, W, C1 + C2, Cout, ep, nullptr, &nl, stream);
 }

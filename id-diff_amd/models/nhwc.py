@@ -25,7 +25,8 @@ class _T:
     def __init__(self, buf, H, W, C, stats=None, norm=None, pending=None):
         self.buf, self.H, self.W, self.C, self.stats = buf, H, W, C, stats
         # set where a GroupNorm was NOT applied: ``buf`` is still the norm's raw input and the one 3x3 convolution that reads this tensor
-        # applies it in its loader: (coefficients [B, C, 2], activation, the norm's input _T, the module) -- see NhwcExecutor._gn_act
+        # applies it in its loader: (coefficients [B, C, 2], activation, the norm's input _T, the module, the second source _T of a
+        # concatenation that was not made or None) -- see NhwcExecutor._gn_act
         self.pending = pending
         # set on the output of a GroupNorm (and kept through the resamplers): (module, elements per normalised group, absolute gain of
         # what followed, modulated?) -- what HipScoreModel.pairs_admissible needs to decide whether the consumer may run on fp16 pairs
@@ -149,7 +150,9 @@ class NhwcExecutor(HipScoreModel):
         sums, admitted to the fp16 pairs by ITS OWN gamma / beta (the record below: the tensor in memory stays the raw one) and the kernel's
         query routes the class (IDIFF_NO_FUSED_GN_LOAD answers no), the pass is not made: one small launch turns the column sums into an
         affine pair per (image, channel) and the tensor is handed on ``pending``; _conv applies a x + b and the activation in its loader.
-        cat[x, x2] stays on the pass (the loader reads one base pointer)."""
+        cat[x, x2] (both with column sums) goes the same way where the two-source query routes its class (its own switch,
+        IDIFF_NO_FUSED_GN_LOAD_2SRC): neither the concatenated nor the normalised tensor is made, the pending record carries ``x2`` and the
+        tensor handed on is the first source under the concatenation's channel count."""
         B = x.buf.shape[0]
         HW = x.H * x.W
         C2 = x2.C if x2 is not None else 0
@@ -162,7 +165,17 @@ class NhwcExecutor(HipScoreModel):
             if route is not None and route.name == "wino1d":
                 coef = torch.empty(B * x.C * 2, device=x.buf.device, dtype=torch.float32)
                 _lib.groupnorm_coef(x.stats[0], x.stats[1], x.C, None, 0, 0, B, HW, G, gn.eps, gn.weight.detach(), gn.bias.detach(), coef)
-                return _T(x.buf, x.H, x.W, x.C, norm=norm, pending=(coef, act, x, gn))
+                return _T(x.buf, x.H, x.W, x.C, norm=norm, pending=(coef, act, x, gn, None))
+        if (conv_cout is not None and mod is None and x2 is not None and x.stats is not None and x2.stats is not None and x.pending is None
+                and x2.pending is None and x.W == 32 and _lib.ACT[act] in (0, 1)
+                and _lib.conv2d_wino1d_normload_2src_ok(B, x.H, x.W, x.C, C2, conv_cout)
+                and self.pairs_admissible(gn, norm[1], gain=1.0, transform=True, modulated=False)):
+            route = conv3x3_route(B, x.H, x.W, x.C + C2, conv_cout, True, True)
+            if route is not None and route.name == "wino1d":
+                coef = torch.empty(B * (x.C + C2) * 2, device=x.buf.device, dtype=torch.float32)
+                _lib.groupnorm_coef_2src(x.stats[0], x.stats[1], x.C, x2.stats[0], x2.stats[1], C2, B, HW, G, gn.eps, gn.weight.detach(),
+                                         gn.bias.detach(), coef)
+                return _T(x.buf, x.H, x.W, x.C + C2, norm=norm, pending=(coef, act, x, gn, x2))
         if x.stats is not None and (x2 is None or x2.stats is not None) and x.C + C2 <= 1024 and B <= 65535:
             # both sources carry the column sums their producing contraction wrote: no pass over the activations, and the
             # statistics are finished inside the apply kernel (one launch per GroupNorm)
@@ -213,9 +226,11 @@ class NhwcExecutor(HipScoreModel):
         if (kh, kw, stride, pad, ph) == (3, 3, 1, 1, 1):
             route = conv3x3_route(*geom, normed, ep["rows_per_group"] == OH * OW)
         pending = x.pending
-        if pending is not None and (route is None or route.name != "wino1d" or not _lib.conv2d_wino1d_normload_ok(*geom)):
+        if pending is not None and (route is None or route.name != "wino1d" or not (
+                _lib.conv2d_wino1d_normload_ok(*geom) if pending[4] is None
+                else _lib.conv2d_wino1d_normload_2src_ok(B, x.H, x.W, pending[2].C, pending[4].C, cout))):
             # not the convolution _gn_act foresaw (a switch flipped in between): the pass after all, never a raw tensor into a kernel
-            x, pending = self._gn_act(pending[2], pending[3], pending[1]), None
+            x, pending = self._gn_act(pending[2], pending[3], pending[1], pending[4]), None
         if route is None:
             if stats or fuse_gn is not None:
                 self._colstats(y, _lib.conv2d_colstats_split(*geom, kh, kw, stride, pad, pad_hi), ep)
@@ -238,7 +253,9 @@ class NhwcExecutor(HipScoreModel):
         if stats or fuse_gn is not None:
             self._colstats(y, getattr(_lib, route.split)(*geom), ep)
         epilogue = _lib.make_epilogue(bias=bias, **ep)
-        if pending is not None:
+        if pending is not None and pending[4] is not None:
+            epilogue = _lib.with_normload_2src(epilogue, pending[0], pending[1], pending[4].buf, pending[2].C)
+        elif pending is not None:
             epilogue = _lib.with_normload(epilogue, pending[0], pending[1])
         getattr(_lib, route.launch)(x.buf, bank[key][1], y.buf, *geom, epilogue=epilogue, **form)
         return (y, False) if fuse_gn is not None else y

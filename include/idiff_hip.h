@@ -52,7 +52,9 @@ const char *idiff_variant_flags(void);
  * IDIFF_NO_WINO43 (3x3 convolutions on the F(2x2,3x3) kernel instead of F(4x4,3x3)), IDIFF_NO_WINO43H (F(4x4,3x3) with its
  * contractions on the fp32 matrix cores instead of fp16 pairs), IDIFF_NO_FUSED_ATTN (idiff_attention256_ok and idiff_attention_heads_ok answer 0), IDIFF_NO_WINO1D (idiff_conv2d_wino1d_ok answers 0),
  * IDIFF_NO_FUSED_GN (idiff_conv2d_wino1d_gn_ok answers 0: the GroupNorm behind a row-wise convolution stays a launch of its own), IDIFF_NO_FUSED_GN_LOAD
- * (idiff_conv2d_wino1d_normload_ok answers 0: the GroupNorm in front of a row-wise convolution stays a pass of its own), IDIFF_NO_PAIRS (idiff_gemm_pairs_ok answers 0: the 1x1
+ * (idiff_conv2d_wino1d_normload_ok answers 0: the GroupNorm in front of a row-wise convolution stays a pass of its own),
+ * IDIFF_NO_FUSED_GN_LOAD_2SRC (idiff_conv2d_wino1d_normload_2src_ok answers 0: the GroupNorm of cat[x1, x2] in front of a row-wise
+ * convolution stays a pass of its own), IDIFF_NO_PAIRS (idiff_gemm_pairs_ok answers 0: the 1x1
  * projections behind a GroupNorm stay on idiff_gemm_f32's six-product form), IDIFF_PAIRS_MIN_TILES (tests: the number of 128 x 128
  * tiles from which idiff_gemm_pairs_ok answers 1; default 256).
  * Returns the previous value, -1 for an unknown name.  No reference counterpart. */
@@ -342,6 +344,19 @@ int idiff_conv2d_wino1d_gn_f32(const float *x, const float *u, float *out, int B
 int idiff_conv2d_wino1d_normload_ok(int B, int H, int W, int Cin, int Cout);
 int idiff_conv2d_wino1d_normload_f32(const float *x, const float *u, float *out, int B, int H, int W, int Cin, int Cout,
                                      const idiff_epilogue *ep, const float *coef, int act, void *stream);
+/* The same with the convolution's input cat[x1, x2] along the channels read from its two sources, x1 [B, H * W, C1] and x2 [B, H * W, C2], each
+ * with its own row pitch: input channels [0, C1) come from x1 and [C1, C1 + C2) from x2 (GroupNorm_0 of cat[h, skip] in a residual block of the
+ * up path: neither the concatenated nor the normalised tensor is written).  The filter bank is the one packed over Cin = C1 + C2 and coef is
+ * [B, C1 + C2, 2], indexed by the concatenated channel (idiff_groupnorm_coef_f32 with both sources' column sums).
+ *   idiff_conv2d_wino1d_normload_2src_ok   1 where this form is served (C1 % 16 == 0, C2 % 16 == 0, both > 0, and the one-source form's
+ *                                          conditions on Cin = C1 + C2) and routed (measured faster than the pass + convolution: Cout <= 128,
+ *                                          csrc/wino1d.hip); 0 under IDIFF_NO_FUSED_GN_LOAD_2SRC, IDIFF_NO_PAIRS and the switches of
+ *                                          idiff_conv2d_wino1d_ok.  IDIFF_NO_FUSED_GN_LOAD does not bear on it.
+ *   idiff_conv2d_wino1d_normload_2src_f32  x1, x2: 16-byte aligned, each inside one buffer descriptor; the rest as
+ *                                          idiff_conv2d_wino1d_normload_f32.  Anything else is refused (IDIFF_EINVAL, nothing launched). */
+int idiff_conv2d_wino1d_normload_2src_ok(int B, int H, int W, int C1, int C2, int Cout);
+int idiff_conv2d_wino1d_normload_2src_f32(const float *x1, int C1, const float *x2, int C2, const float *u, float *out, int B, int H, int W,
+                                          int Cout, const idiff_epilogue *ep, const float *coef, int act, void *stream);
 
 /* Split-precision form of the same convolution: the 16 position-wise contractions run on the bf16 matrix cores with every
  * fp32 operand cut exactly into three bf16 pieces and six of the nine partial products kept (fp32 accumulation; what is
