@@ -9,6 +9,7 @@ CPU path: a missing library or a CPU tensor is an error, never a fallback.
 import ctypes
 import os
 import subprocess
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -316,21 +317,26 @@ def with_groupnorm(ep, groups, gamma, beta, eps, act):
     return ep
 
 
-def with_normload(ep, coef, act):
+class NormLoad(NamedTuple):
+    """The loader-norm request of with_normload.  ``x2 is None``: one source."""
+    coef: torch.Tensor
+    act: int
+    x2: Optional[torch.Tensor]
+    C1: Optional[int]
+
+
+def with_normload(ep, coef, act, x2=None, C1=None):
     """Ask the convolution that consumes ``ep`` to apply the GroupNorm (+ ``act``: "silu" or None) in FRONT of it in its own loader:
-    ``coef`` [B, Cin, 2] from groupnorm_coef, the input handed to the launch is the norm's RAW input.  Rides beside the C struct as
-    with_groupnorm's request does; conv2d_wino1d serves it through idiff_conv2d_wino1d_normload_f32, every other wrapper refuses it."""
+    ``coef`` [B, Cin, 2] from groupnorm_coef, the input handed to the launch is the norm's RAW input.  With ``x2`` and ``C1`` (both or
+    neither) the convolution is one of cat[x, x2] along the channels that is never made: the launch's ``x`` is the first source
+    [B, H*W, C1], ``x2`` the second [B, H*W, Cin - C1].  Rides beside the C struct as with_groupnorm's request does (``ep.normload``);
+    conv2d_wino1d serves it through idiff_conv2d_wino1d_normload_f32 / _2src_f32, every other wrapper refuses it."""
     _dev(coef, "coef")
-    ep.normload = (coef, ACT[act])
-    return ep
-
-
-def with_normload_2src(ep, coef, act, x2, C1):
-    """with_normload for a convolution of cat[x, x2] along the channels that is never made: the launch's ``x`` is the first source
-    [B, H*W, C1], ``x2`` the second [B, H*W, Cin - C1], ``coef`` [B, Cin, 2] from groupnorm_coef_2src.  A request of its own (``normload2``,
-    never ``normload``): conv2d_wino1d serves it through idiff_conv2d_wino1d_normload_2src_f32, every other wrapper refuses it."""
-    _dev(coef, "coef"); _dev(x2, "x2")
-    ep.normload2 = (coef, ACT[act], x2, int(C1))
+    if (x2 is None) != (C1 is None):
+        raise RuntimeError("with_normload: a second source x2 and the first one's channel count C1 come together or not at all")
+    if x2 is not None:
+        _dev(x2, "x2")
+    ep.normload = NormLoad(coef, ACT[act], x2, None if C1 is None else int(C1))
     return ep
 
 
@@ -338,9 +344,6 @@ def _ep_ref(epilogue, what):
     """The epilogue argument of a launch that has no fused GroupNorm: such a request is an error, never dropped."""
     if epilogue is None:
         return None
-    if getattr(epilogue, "normload2", None) is not None:
-        raise RuntimeError(f"{what}: the epilogue asks for a GroupNorm of two sources in the loader (with_normload_2src), which only "
-                           "conv2d_wino1d serves")
     if getattr(epilogue, "normload", None) is not None:
         raise RuntimeError(f"{what}: the epilogue asks for a GroupNorm in the loader (with_normload), which only conv2d_wino1d serves")
     if getattr(epilogue, "groupnorm", None) is not None:
@@ -579,26 +582,18 @@ def _wino_conv(stem, packed_by, x, u, out, B, H, W, Cin, Cout, epilogue):
         raise RuntimeError(f"conv2d_{stem}: a filter bank of {u.numel()} floats ({want} expected): pack it with {packed_by}")
     gn = getattr(epilogue, "groupnorm", None)
     nl = getattr(epilogue, "normload", None)
-    nl2 = getattr(epilogue, "normload2", None)
-    if nl2 is not None and stem == "wino1d":
-        if gn is not None or nl is not None:
-            raise RuntimeError("conv2d_wino1d: a two-source GroupNorm in the loader (with_normload_2src) beside another GroupNorm request "
-                               "(with_normload / with_groupnorm) in one launch")
-        coef, act, x2, C1 = nl2
-        if coef.numel() != B * Cin * 2:
-            raise RuntimeError(f"conv2d_wino1d: {coef.numel()} loader coefficients for [B, Cin, 2] = [{B}, {Cin}, 2]")
-        _check(lib().idiff_conv2d_wino1d_normload_2src_f32(x.data_ptr(), C1, x2.data_ptr(), Cin - C1, u.data_ptr(), out.data_ptr(), B, H, W, Cout,
-                                                           ctypes.byref(epilogue), coef.data_ptr(), act, _stream()),
-               "idiff_conv2d_wino1d_normload_2src_f32")
-        return out
     if nl is not None and stem == "wino1d":
         if gn is not None:
             raise RuntimeError("conv2d_wino1d: a GroupNorm in the loader (with_normload) and one in the tail (with_groupnorm) in one launch")
-        coef, act = nl
-        if coef.numel() != B * Cin * 2:
-            raise RuntimeError(f"conv2d_wino1d: {coef.numel()} loader coefficients for [B, Cin, 2] = [{B}, {Cin}, 2]")
-        _check(lib().idiff_conv2d_wino1d_normload_f32(x.data_ptr(), u.data_ptr(), out.data_ptr(), B, H, W, Cin, Cout, ctypes.byref(epilogue),
-                                                      coef.data_ptr(), act, _stream()), "idiff_conv2d_wino1d_normload_f32")
+        if nl.coef.numel() != B * Cin * 2:
+            raise RuntimeError(f"conv2d_wino1d: {nl.coef.numel()} loader coefficients for [B, Cin, 2] = [{B}, {Cin}, 2]")
+        if nl.x2 is not None:
+            _check(lib().idiff_conv2d_wino1d_normload_2src_f32(x.data_ptr(), nl.C1, nl.x2.data_ptr(), Cin - nl.C1, u.data_ptr(), out.data_ptr(),
+                                                               B, H, W, Cout, ctypes.byref(epilogue), nl.coef.data_ptr(), nl.act, _stream()),
+                   "idiff_conv2d_wino1d_normload_2src_f32")
+        else:
+            _check(lib().idiff_conv2d_wino1d_normload_f32(x.data_ptr(), u.data_ptr(), out.data_ptr(), B, H, W, Cin, Cout, ctypes.byref(epilogue),
+                                                          nl.coef.data_ptr(), nl.act, _stream()), "idiff_conv2d_wino1d_normload_f32")
         return out
     if gn is not None and stem == "wino1d":
         groups, gamma, beta, eps, act = gn
@@ -687,19 +682,9 @@ def conv2d_wino1d_normload_ok(B, H, W, Cin, Cout):
 
 
 def conv2d_wino1d_normload_2src_ok(B, H, W, C1, C2, Cout):
-    """The same for cat[x1, x2] read from its two sources (with_normload_2src): whole K steps (16 channels) from each; off under
+    """The same for cat[x1, x2] read from its two sources (with_normload's x2, C1): whole K steps (16 channels) from each; off under
     IDIFF_NO_FUSED_GN_LOAD_2SRC (not under IDIFF_NO_FUSED_GN_LOAD), IDIFF_NO_PAIRS and wherever conv2d_wino1d_ok is."""
     return bool(lib().idiff_conv2d_wino1d_normload_2src_ok(B, H, W, C1, C2, Cout))
-
-
-def groupnorm_coef_2src(ws1, ns1, C1, ws2, ns2, C2, B, HW, G, eps, gamma, beta, coef):
-    """groupnorm_coef for the two-source loader: coef [B, C1 + C2, 2] of GroupNorm(cat[x1, x2]) from both producers' column sums."""
-    _dev(coef, "coef"); _dev(gamma, "gamma"); _dev(beta, "beta")
-    if ws2 is None or coef.numel() != B * (C1 + C2) * 2:
-        raise RuntimeError(f"groupnorm_coef_2src: both sources' column sums and coef [B, C1 + C2, 2] = {B * (C1 + C2) * 2} floats are required")
-    _check(lib().idiff_groupnorm_coef_f32(ws1.data_ptr(), ns1, C1, ws2.data_ptr(), ns2, C2, B, HW, G, eps, gamma.data_ptr(), beta.data_ptr(),
-                                          coef.data_ptr(), _stream()), "idiff_groupnorm_coef_f32")
-    return coef
 
 
 def groupnorm_coef(ws1, ns1, C1, ws2, ns2, C2, B, HW, G, eps, gamma, beta, coef):
@@ -719,7 +704,7 @@ def wino1d_pack(wt, Cin, Cout):
 
 def conv2d_wino1d(x, u, out, B, H, W, Cin, Cout, epilogue=None):
     """``epilogue`` may carry a GroupNorm request (with_groupnorm): the launch then stores act(GroupNorm(conv + bias + rowbias)); or one for
-    the loader (with_normload; with_normload_2src: ``x`` is then the first source, ``Cin`` the total and the second travels in the request)."""
+    the loader (with_normload; with its x2, C1 ``x`` is the first source, ``Cin`` the total and the second travels in the request)."""
     return _wino_conv("wino1d", "wino1d_pack", x, u, out, B, H, W, Cin, Cout, epilogue)
 
 

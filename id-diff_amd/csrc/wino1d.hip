@@ -997,17 +997,17 @@ int r1_run(const float *x, const float *u, float *out, int B, int H, int W, int 
 #ifdef IDIFF_W1D_STAMP
   { const char *e = getenv("IDIFF_W1D_STAMP_PTR"); p.stamps = e ? reinterpret_cast<uint64_t *>(strtoull(e, nullptr, 0)) : nullptr; }
 #endif
-  if (two) {
-    p.nl_coef = nl->coef; p.nl_bytes = (uint32_t)((int64_t)B * Cin * 8);
-    p.x2 = nl->x2; p.c1 = nl->c1;
-    p.x_bytes = (uint32_t)((int64_t)B * H * W * nl->c1 * 4); p.x2_bytes = (uint32_t)((int64_t)B * H * W * (Cin - nl->c1) * 4);
-    if (nl->act == IDIFF_ACT_SILU) return r1_launch<wino1d_nl2_kernel<2>>(p, "conv2d_wino1d_normload_2src", (hipStream_t)stream);
-    return r1_launch<wino1d_nl2_kernel<1>>(p, "conv2d_wino1d_normload_2src", (hipStream_t)stream);
-  }
   if (nl) {
     p.nl_coef = nl->coef; p.nl_bytes = (uint32_t)((int64_t)B * Cin * 8);
-    if (nl->act == IDIFF_ACT_SILU) return r1_launch<wino1d_nl_kernel<2>>(p, "conv2d_wino1d_normload", (hipStream_t)stream);
-    return r1_launch<wino1d_nl_kernel<1>>(p, "conv2d_wino1d_normload", (hipStream_t)stream);
+    if (two) {
+      p.x2 = nl->x2; p.c1 = nl->c1;
+      p.x_bytes = (uint32_t)((int64_t)B * H * W * nl->c1 * 4); p.x2_bytes = (uint32_t)((int64_t)B * H * W * (Cin - nl->c1) * 4);
+    }
+    const bool silu = nl->act == IDIFF_ACT_SILU;
+    const hipStream_t s = (hipStream_t)stream;
+    return two ? (silu ? r1_launch<wino1d_nl2_kernel<2>>(p, "conv2d_wino1d_normload_2src", s)
+                       : r1_launch<wino1d_nl2_kernel<1>>(p, "conv2d_wino1d_normload_2src", s))
+               : (silu ? r1_launch<wino1d_nl_kernel<2>>(p, "conv2d_wino1d_normload", s) : r1_launch<wino1d_nl_kernel<1>>(p, "conv2d_wino1d_normload", s));
   }
   if (gn) {
     p.gn_gamma = gn->gamma; p.gn_beta = gn->beta; p.gn_cpg = Cout / gn->groups; p.gn_act = gn->act; p.gn_eps = gn->eps;
@@ -1069,7 +1069,7 @@ IDIFF_API int idiff_conv2d_wino1d_normload_f32(const float *x, const float *u, f
 
 // The two-source form: GroupNorm_0 of cat[h, skip] in the level-0 blocks of config 3's up path -- the 256 -> 128 and 384 -> 128 classes of the
 // table above reach the loader only through it (one source never has them there).  Routed class by class as the one-source form is
-// (scripts/normload2_shape_ab.py, profiles/normload2_shape_ab.txt: {two-source groupnorm_apply_colstats + conv2d_wino1d on the concatenated
+// (scripts/normload_shape_ab.py, profiles/normload2_shape_ab.txt: {two-source groupnorm_apply_colstats + conv2d_wino1d on the concatenated
 // output} against {coefficients + this}, B = 2240, 32 x 32, median us):
 //   128 + 128 -> 128   929 + 2081 = 3010   against  16 + 2607 = 2623   (-12.8 %, spread 190)
 //   256 + 128 -> 128  1371 + 2994 = 4366   against  23 + 3720 = 3743   (-14.3 %, spread 133)

@@ -5,7 +5,7 @@ An activation is a ``_T`` ([B, H*W, C] + geometry); every step is one or a few l
 ``state_dict`` layout), the plan, the weight packing, FIR resampling.  Which kernel serves a 3x3 convolution is decided in one
 place, ``CONV3X3_ROUTES`` / ``conv3x3_route``: host logic only, testable without a GPU.
 """
-from typing import Callable, NamedTuple
+from typing import Callable, NamedTuple, Optional
 
 import torch
 
@@ -17,6 +17,21 @@ def _pad4(c):
     return (c + 3) // 4 * 4
 
 
+class PendingNorm(NamedTuple):
+    """A GroupNorm that was NOT applied (NhwcExecutor._gn_act): the one 3x3 convolution that reads the tensor applies it in its loader."""
+    coef: torch.Tensor       # [B, C, 2] from groupnorm_coef
+    act: Optional[str]
+    src: "_T"                # the norm's input
+    gn: torch.nn.Module
+    src2: Optional["_T"]     # the second source of a concatenation that was not made, or None
+
+    def served(self, B, H, W, cout):
+        """Does the loader (still) apply this norm in front of a convolution of [B, H, W] to ``cout`` channels?  The query of its source count."""
+        if self.src2 is None:
+            return _lib.conv2d_wino1d_normload_ok(B, H, W, self.src.C, cout)
+        return _lib.conv2d_wino1d_normload_2src_ok(B, H, W, self.src.C, self.src2.C, cout)
+
+
 class _T:
     """An NHWC activation: buffer [B, H*W, C] + geometry (+ the per-tile column sums [B, nsplit, C, 2] its producing
     contraction wrote through epilogue.colstats, which let the consuming GroupNorm skip its statistics pass)."""
@@ -24,9 +39,7 @@ class _T:
 
     def __init__(self, buf, H, W, C, stats=None, norm=None, pending=None):
         self.buf, self.H, self.W, self.C, self.stats = buf, H, W, C, stats
-        # set where a GroupNorm was NOT applied: ``buf`` is still the norm's raw input and the one 3x3 convolution that reads this tensor
-        # applies it in its loader: (coefficients [B, C, 2], activation, the norm's input _T, the module, the second source _T of a
-        # concatenation that was not made or None) -- see NhwcExecutor._gn_act
+        # a PendingNorm where a GroupNorm was NOT applied: ``buf`` is still the norm's raw input
         self.pending = pending
         # set on the output of a GroupNorm (and kept through the resamplers): (module, elements per normalised group, absolute gain of
         # what followed, modulated?) -- what HipScoreModel.pairs_admissible needs to decide whether the consumer may run on fp16 pairs
@@ -149,33 +162,19 @@ class NhwcExecutor(HipScoreModel):
         images.  Where that convolution takes the ``wino1d`` route on rows of 32 pixels, the norm is unmodulated, of one source with column
         sums, admitted to the fp16 pairs by ITS OWN gamma / beta (the record below: the tensor in memory stays the raw one) and the kernel's
         query routes the class (IDIFF_NO_FUSED_GN_LOAD answers no), the pass is not made: one small launch turns the column sums into an
-        affine pair per (image, channel) and the tensor is handed on ``pending``; _conv applies a x + b and the activation in its loader.
-        cat[x, x2] (both with column sums) goes the same way where the two-source query routes its class (its own switch,
-        IDIFF_NO_FUSED_GN_LOAD_2SRC): neither the concatenated nor the normalised tensor is made, the pending record carries ``x2`` and the
-        tensor handed on is the first source under the concatenation's channel count."""
+        affine pair per (image, channel) and the tensor is handed on with a PendingNorm; _conv applies a x + b and the activation in its
+        loader.  cat[x, x2] (both with column sums) goes the same way where the two-source query routes its class (its own switch,
+        IDIFF_NO_FUSED_GN_LOAD_2SRC): neither the concatenated nor the normalised tensor is made, the record carries ``x2`` as ``src2`` and
+        the tensor handed on is the first source under the concatenation's channel count (_defer_norm)."""
         B = x.buf.shape[0]
         HW = x.H * x.W
         C2 = x2.C if x2 is not None else 0
         G = gn.num_groups
         norm = (gn, ((x.C + C2) // G) * HW, 1.0, mod is not None)
-        if (conv_cout is not None and mod is None and x2 is None and x.stats is not None and x.pending is None and x.W == 32
-                and _lib.ACT[act] in (0, 1) and _lib.conv2d_wino1d_normload_ok(B, x.H, x.W, x.C, conv_cout)
-                and self.pairs_admissible(gn, norm[1], gain=1.0, transform=True, modulated=False)):
-            route = conv3x3_route(B, x.H, x.W, x.C, conv_cout, True, True)
-            if route is not None and route.name == "wino1d":
-                coef = torch.empty(B * x.C * 2, device=x.buf.device, dtype=torch.float32)
-                _lib.groupnorm_coef(x.stats[0], x.stats[1], x.C, None, 0, 0, B, HW, G, gn.eps, gn.weight.detach(), gn.bias.detach(), coef)
-                return _T(x.buf, x.H, x.W, x.C, norm=norm, pending=(coef, act, x, gn, None))
-        if (conv_cout is not None and mod is None and x2 is not None and x.stats is not None and x2.stats is not None and x.pending is None
-                and x2.pending is None and x.W == 32 and _lib.ACT[act] in (0, 1)
-                and _lib.conv2d_wino1d_normload_2src_ok(B, x.H, x.W, x.C, C2, conv_cout)
-                and self.pairs_admissible(gn, norm[1], gain=1.0, transform=True, modulated=False)):
-            route = conv3x3_route(B, x.H, x.W, x.C + C2, conv_cout, True, True)
-            if route is not None and route.name == "wino1d":
-                coef = torch.empty(B * (x.C + C2) * 2, device=x.buf.device, dtype=torch.float32)
-                _lib.groupnorm_coef_2src(x.stats[0], x.stats[1], x.C, x2.stats[0], x2.stats[1], C2, B, HW, G, gn.eps, gn.weight.detach(),
-                                         gn.bias.detach(), coef)
-                return _T(x.buf, x.H, x.W, x.C + C2, norm=norm, pending=(coef, act, x, gn, x2))
+        if conv_cout is not None and mod is None:
+            deferred = self._defer_norm(x, x2, gn, act, norm, conv_cout)
+            if deferred is not None:
+                return deferred
         if x.stats is not None and (x2 is None or x2.stats is not None) and x.C + C2 <= 1024 and B <= 65535:
             # both sources carry the column sums their producing contraction wrote: no pass over the activations, and the
             # statistics are finished inside the apply kernel (one launch per GroupNorm)
@@ -198,6 +197,25 @@ class NhwcExecutor(HipScoreModel):
                              gn.weight.detach(), gn.bias.detach(), act, y.buf, mod=mod)
         y.norm = norm
         return y
+
+    def _defer_norm(self, x, x2, gn, act, norm, conv_cout):
+        """_gn_act's unmodulated norm in front of a 3x3 convolution to ``conv_cout`` channels: the raw tensor with a PendingNorm where the
+        convolution's loader applies it (_gn_act's conditions), else None."""
+        srcs = (x,) if x2 is None else (x, x2)
+        B, C = x.buf.shape[0], sum(s.C for s in srcs)
+        pending = PendingNorm(None, act, x, gn, x2)                 # the coefficients follow once every condition holds
+        if not (all(s.stats is not None and s.pending is None for s in srcs) and x.W == 32 and _lib.ACT[act] in (0, 1)
+                and pending.served(B, x.H, x.W, conv_cout)
+                and self.pairs_admissible(gn, norm[1], gain=1.0, transform=True, modulated=False)):
+            return None
+        route = conv3x3_route(B, x.H, x.W, C, conv_cout, True, True)
+        if route is None or route.name != "wino1d":
+            return None
+        ws2, ns2, C2 = (*x2.stats, x2.C) if x2 is not None else (None, 0, 0)
+        coef = torch.empty(B * C * 2, device=x.buf.device, dtype=torch.float32)
+        _lib.groupnorm_coef(x.stats[0], x.stats[1], x.C, ws2, ns2, C2, B, x.H * x.W, gn.num_groups, gn.eps, gn.weight.detach(),
+                            gn.bias.detach(), coef)
+        return _T(x.buf, x.H, x.W, C, norm=norm, pending=pending._replace(coef=coef))
 
     def _conv(self, x, wt, bias, stride=1, pad=1, pad_hi=None, stats=False, normed=False, fuse_gn=None, **ep):
         """``stats=True``: the output feeds a GroupNorm -> ask the epilogue for its per-tile column sums.
@@ -226,11 +244,9 @@ class NhwcExecutor(HipScoreModel):
         if (kh, kw, stride, pad, ph) == (3, 3, 1, 1, 1):
             route = conv3x3_route(*geom, normed, ep["rows_per_group"] == OH * OW)
         pending = x.pending
-        if pending is not None and (route is None or route.name != "wino1d" or not (
-                _lib.conv2d_wino1d_normload_ok(*geom) if pending[4] is None
-                else _lib.conv2d_wino1d_normload_2src_ok(B, x.H, x.W, pending[2].C, pending[4].C, cout))):
+        if pending is not None and (route is None or route.name != "wino1d" or not pending.served(B, x.H, x.W, cout)):
             # not the convolution _gn_act foresaw (a switch flipped in between): the pass after all, never a raw tensor into a kernel
-            x, pending = self._gn_act(pending[2], pending[3], pending[1], pending[4]), None
+            x, pending = self._gn_act(pending.src, pending.gn, pending.act, pending.src2), None
         if route is None:
             if stats or fuse_gn is not None:
                 self._colstats(y, _lib.conv2d_colstats_split(*geom, kh, kw, stride, pad, pad_hi), ep)
@@ -253,10 +269,9 @@ class NhwcExecutor(HipScoreModel):
         if stats or fuse_gn is not None:
             self._colstats(y, getattr(_lib, route.split)(*geom), ep)
         epilogue = _lib.make_epilogue(bias=bias, **ep)
-        if pending is not None and pending[4] is not None:
-            epilogue = _lib.with_normload_2src(epilogue, pending[0], pending[1], pending[4].buf, pending[2].C)
-        elif pending is not None:
-            epilogue = _lib.with_normload(epilogue, pending[0], pending[1])
+        if pending is not None:
+            two = pending.src2 is not None
+            epilogue = _lib.with_normload(epilogue, pending.coef, pending.act, pending.src2.buf if two else None, pending.src.C if two else None)
         getattr(_lib, route.launch)(x.buf, bank[key][1], y.buf, *geom, epilogue=epilogue, **form)
         return (y, False) if fuse_gn is not None else y
 

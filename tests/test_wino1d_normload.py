@@ -8,6 +8,7 @@ import torch
 import torch.nn.functional as F
 
 import id_diff_amd
+import normload_cases
 from helpers import fill_from_seed, ncsnpp_config, rel_err
 from id_diff_amd import _lib
 from id_diff_amd.models import nhwc as hip_nhwc
@@ -46,8 +47,7 @@ def _case(Cin, Cout, act):
     ref = F.conv2d(n, w.double(), b.double(), padding=1).permute(0, 2, 3, 1).contiguous()
 
     xd = x.permute(0, 2, 3, 1).contiguous().to(DEV)                      # the raw tensor, NHWC
-    # the producers' column sums of x ([B, nsplit = 1, Cin, 2] fp64), as a contraction's epilogue would have written them
-    cs = torch.stack([xd.double().sum(dim=(1, 2)), (xd.double() ** 2).sum(dim=(1, 2))], dim=-1).contiguous().view(-1)
+    cs = normload_cases.colsums(xd.view(B, H * W, Cin))
     wt = w.permute(0, 2, 3, 1).contiguous().to(DEV)
     bd, gd, btd = b.to(DEV), gamma.to(DEV), beta.to(DEV)
     # two launches: the pass, then the 3x3 convolution on the route the executor takes for this geometry behind a GroupNorm
@@ -77,9 +77,7 @@ def _case(Cin, Cout, act):
 
 @pytest.fixture
 def small_batches(monkeypatch):
-    monkeypatch.setattr(hip_nhwc, "WINO1D_MIN_WORKGROUPS", 1)
-    monkeypatch.setattr(hip_nhwc, "WINO43_MIN_WORKGROUPS", 1)
-    monkeypatch.setattr(hip_nhwc, "WINO43_PAIRS_MIN_WORKGROUPS", 1)
+    normload_cases.small_batches(monkeypatch)
 
 
 @pytest.mark.parametrize("Cin,Cout,act", CASES)
@@ -129,32 +127,14 @@ def test_normload_query_switches_and_refusals():
 
 @pytest.fixture
 def counted(small_batches, monkeypatch):
-    calls = {"gn_apply": 0, "gn_coef": 0, "wino1d": 0, "wino1d_nl": 0}
-    orig_gn, orig_coef, orig_conv = _lib.groupnorm_apply_colstats, _lib.groupnorm_coef, _lib.conv2d_wino1d
-
-    def counted_gn(*a, **k):
-        calls["gn_apply"] += 1
-        return orig_gn(*a, **k)
-
-    def counted_coef(*a, **k):
-        calls["gn_coef"] += 1
-        return orig_coef(*a, **k)
-
-    def counted_conv(x, u, out, B, H, W, Cin, Cout, epilogue=None):
-        calls["wino1d"] += 1
-        calls["wino1d_nl"] += getattr(epilogue, "normload", None) is not None
-        return orig_conv(x, u, out, B, H, W, Cin, Cout, epilogue=epilogue)
-    monkeypatch.setattr(_lib, "groupnorm_apply_colstats", counted_gn)
-    monkeypatch.setattr(_lib, "groupnorm_coef", counted_coef)
-    monkeypatch.setattr(_lib, "conv2d_wino1d", counted_conv)
-    return calls
+    return normload_cases.counted(monkeypatch)
 
 
 def _small_model():
     """nf = 32, two levels of 64 channels, two residual blocks per level, 32 x 32 input.  At 32 x 32: two blocks down (GroupNorm_0 of one
     source and GroupNorm_1 each: 4 norms read by one 3x3 convolution only), the down block (its GroupNorm_0 is read by the FIR: the pass
-    stays; its Conv_0 and GroupNorm_1 are at 16 x 16), three blocks up on cat[h, skip] (GroupNorm_0 of two sources stays, GroupNorm_1
-    goes: 3) and the up block (GroupNorm_0 and the FIR at 16 x 16, Conv_0 -> GroupNorm_1 -> Conv_1 at 32 x 32: 1) -- 8 in all."""
+    stays; its Conv_0 and GroupNorm_1 are at 16 x 16), three blocks up on cat[h, skip] (GroupNorm_0 of two sources is the two-source form's, on
+    under this file's switch too and counted apart as wino1d_nl2 / gn_coef2; GroupNorm_1 goes: 3) and the up block (GroupNorm_0 and the FIR at 16 x 16, Conv_0 -> GroupNorm_1 -> Conv_1 at 32 x 32: 1) -- 8 in all."""
     model = mutils.create_model(ncsnpp_config(**{"model.nf": 32, "model.ch_mult": (2, 2), "model.num_res_blocks": 2, "model.init_scale": 1.0}))
     fill_from_seed(model, 5)
     model.to(DEV)
@@ -164,13 +144,7 @@ def _small_model():
 
 
 def _on_and_off(model, x, t, calls):
-    c0 = dict(calls)
-    on = model(x, t * 999)
-    c_on = {k: calls[k] - c0[k] for k in calls}
-    with _lib.thread_option("IDIFF_NO_FUSED_GN_LOAD", 1):
-        off = model(x, t * 999)
-    c_off = {k: calls[k] - c0[k] - c_on[k] for k in calls}
-    return on, off, c_on, c_off
+    return normload_cases.on_and_off(model, x, t, calls, "IDIFF_NO_FUSED_GN_LOAD")
 
 
 def test_small_ncsnpp_with_and_without_normload(counted):

@@ -10,7 +10,9 @@ import torch
 import torch.nn.functional as F
 
 import id_diff_amd
+import normload_cases
 from helpers import fill_from_seed, ncsnpp_config, rel_err
+from normload_cases import colsums as _colsums
 from id_diff_amd import _lib
 from id_diff_amd.models import nhwc as hip_nhwc
 from id_diff_amd.models import utils as mutils
@@ -54,11 +56,6 @@ def _inputs(C1, C2, Cout, act):
     return out
 
 
-def _colsums(xd):
-    """the producer's column sums of xd [B, HW, C] ([B, nsplit = 1, C, 2] fp64), as a contraction's epilogue would have written them"""
-    return torch.stack([xd.double().sum(dim=1), (xd.double() ** 2).sum(dim=1)], dim=-1).contiguous().view(-1)
-
-
 def _case(C1, C2, Cout, act):
     key = (C1, C2, Cout, act)
     if key in _cache:
@@ -85,9 +82,9 @@ def _case(C1, C2, Cout, act):
         name = route.name
     # one launch (+ the coefficients): the raw sources into the loader
     coef = torch.full((B * Cin * 2,), float("nan"), device=DEV)
-    _lib.groupnorm_coef_2src(cs1, 1, C1, cs2, 1, C2, B, H * W, G, EPS, gd, btd, coef)
+    _lib.groupnorm_coef(cs1, 1, C1, cs2, 1, C2, B, H * W, G, EPS, gd, btd, coef)
     fused = torch.full((B, H * W, Cout), float("nan"), device=DEV)       # every output must be written
-    ep = _lib.with_normload_2src(_lib.make_epilogue(bias=bd), coef, act, x2d, C1)
+    ep = _lib.with_normload(_lib.make_epilogue(bias=bd), coef, act, x2d, C1)
     _lib.conv2d_wino1d(x1d, _lib.wino1d_pack(wt, Cin, Cout), fused, B, H, W, Cin, Cout, epilogue=ep)
     torch.cuda.synchronize()
     out = (ref, two.cpu().double().view(B, H, W, Cout), fused.cpu().double().view(B, H, W, Cout), name)
@@ -97,9 +94,7 @@ def _case(C1, C2, Cout, act):
 
 @pytest.fixture
 def small_batches(monkeypatch):
-    monkeypatch.setattr(hip_nhwc, "WINO1D_MIN_WORKGROUPS", 1)
-    monkeypatch.setattr(hip_nhwc, "WINO43_MIN_WORKGROUPS", 1)
-    monkeypatch.setattr(hip_nhwc, "WINO43_PAIRS_MIN_WORKGROUPS", 1)
+    normload_cases.small_batches(monkeypatch)
 
 
 @pytest.mark.parametrize("C1,C2", SOURCES)
@@ -160,7 +155,7 @@ def test_normload_2src_query_and_switches():
 def _request(Bn, C1, C2, Cout, act="silu", x2=None):
     Cin = C1 + C2
     x2 = torch.zeros(2 * 1024 * max(C2, 16), device=DEV) if x2 is None else x2
-    return _lib.with_normload_2src(_lib.make_epilogue(), torch.zeros(Bn * Cin * 2, device=DEV), act, x2, C1)
+    return _lib.with_normload(_lib.make_epilogue(), torch.zeros(Bn * Cin * 2, device=DEV), act, x2, C1)
 
 
 @gpu
@@ -208,7 +203,7 @@ def test_normload_2src_refusals_launch_nothing():
 
 
 # ---------------------------------------------------------------------------------------------------------------- executor
-MEASURED = ((128, 128), (256, 128))      # the benchmark's classes (C1, C2) -> 128 of scripts/normload2_shape_ab.py
+MEASURED = ((128, 128), (256, 128))      # the benchmark's classes (C1, C2) -> 128 of scripts/normload_shape_ab.py
 
 
 @pytest.fixture
@@ -216,30 +211,11 @@ def counted(small_batches, monkeypatch):
     """Counts the passes, the two-source coefficient launches and the convolutions; the routing query admits every geometry the launcher
     serves with at most two cout tiles (this network's 128 + 64 -> 64 and 64 + 64 -> 64 are not classes of the benchmark) as long as the
     library's own query -- and with it every switch -- admits a measured class."""
-    calls = {"gn_apply": 0, "gn_coef2": 0, "wino1d": 0, "wino1d_nl2": 0}
-    orig_gn, orig_coef, orig_conv, orig_ok = (_lib.groupnorm_apply_colstats, _lib.groupnorm_coef_2src, _lib.conv2d_wino1d,
-                                              _lib.conv2d_wino1d_normload_2src_ok)
-
-    def counted_gn(*a, **k):
-        calls["gn_apply"] += 1
-        return orig_gn(*a, **k)
-
-    def counted_coef(*a, **k):
-        calls["gn_coef2"] += 1
-        return orig_coef(*a, **k)
-
-    def counted_conv(x, u, out, B, H, W, Cin, Cout, epilogue=None):
-        calls["wino1d"] += 1
-        calls["wino1d_nl2"] += getattr(epilogue, "normload2", None) is not None
-        assert getattr(epilogue, "normload2", None) is None or getattr(epilogue, "normload", None) is None
-        return orig_conv(x, u, out, B, H, W, Cin, Cout, epilogue=epilogue)
+    calls, orig_ok = normload_cases.counted(monkeypatch), _lib.conv2d_wino1d_normload_2src_ok
 
     def admit(B, H, W, C1, C2, Cout):
         return (any(orig_ok(B, 32, 32, c1, c2, 128) for c1, c2 in MEASURED) and W == 32 and H % 16 == 0 and C1 > 0 and C2 > 0
                 and C1 % 16 == 0 and C2 % 16 == 0 and Cout in (64, 128))
-    monkeypatch.setattr(_lib, "groupnorm_apply_colstats", counted_gn)
-    monkeypatch.setattr(_lib, "groupnorm_coef_2src", counted_coef)
-    monkeypatch.setattr(_lib, "conv2d_wino1d", counted_conv)
     monkeypatch.setattr(_lib, "conv2d_wino1d_normload_2src_ok", admit)
     return calls
 
@@ -256,13 +232,7 @@ def _small_model():
 
 
 def _on_and_off(model, x, t, calls):
-    c0 = dict(calls)
-    on = model(x, t * 999)
-    c_on = {k: calls[k] - c0[k] for k in calls}
-    with _lib.thread_option("IDIFF_NO_FUSED_GN_LOAD_2SRC", 1):
-        off = model(x, t * 999)
-    c_off = {k: calls[k] - c0[k] - c_on[k] for k in calls}
-    return on, off, c_on, c_off
+    return normload_cases.on_and_off(model, x, t, calls, "IDIFF_NO_FUSED_GN_LOAD_2SRC")
 
 
 @gpu
@@ -296,3 +266,69 @@ def test_inadmissible_gamma_leaves_the_two_source_loader_route(counted):
     assert c_off["gn_apply"] - c_on["gn_apply"] == 1, (c_on, c_off)
     assert bool(torch.isfinite(on).all())
     assert rel_err(on.cpu(), off.cpu()) < NET_RTOL
+
+
+@gpu
+@pytest.mark.parametrize("sources", (1, 2))
+def test_conv_makes_the_pass_when_the_loader_no_longer_serves(counted, sources):
+    """The deferred norm's way back: _gn_act hands a raw tensor on with a pending record, the form's switch is flipped, and _conv -- whose
+    query now answers no -- makes the pass after all, from the record's fields, before it launches.  GroupNorm(8, 32) + SiLU of one raw
+    source of 32 channels (the smallest Cin of the plain wino1d route) or of 16 + 16 (one K step each, means +1 .. 2 and -1 .. -2: swapped
+    or repeated sources are an error of order 1), B = 2, 32 x 32 -> 64 channels.  Bit-equal to the same two calls made entirely under the
+    switch (the same pass and the same convolution launch on the same data), and within the file's bar of the fp64 restatement."""
+    Bn, C, Cout = 2, 32, 64
+    switch = "IDIFF_NO_FUSED_GN_LOAD" if sources == 1 else "IDIFF_NO_FUSED_GN_LOAD_2SRC"
+    model, _, _ = _small_model()
+    g = torch.Generator().manual_seed(91 + sources)
+    sign = lambda n: torch.where(torch.rand(n, generator=g) < 0.5, -1.0, 1.0)
+    widths = (C,) if sources == 1 else (C // 2, C // 2)
+    raw = [torch.randn(Bn, c, H, W, generator=g) * 1.3 + s * (torch.rand(1, c, 1, 1, generator=g) + 1.0) for c, s in zip(widths, (1.0, -1.0))]
+    w = torch.randn(Cout, C, 3, 3, generator=g) / (C * 9) ** 0.5
+    b = torch.randn(Cout, generator=g)
+    gn = torch.nn.GroupNorm(8, C, eps=EPS).to(DEV)
+    with torch.no_grad():
+        gn.weight.copy_((torch.rand(C, generator=g) + 0.5) * sign(C) * 1.4)
+        gn.bias.copy_((torch.rand(C, generator=g) * 0.6 + 0.7) * sign(C))
+    assert float(gn.bias.detach().abs().min()) >= 0.7
+    n = F.silu(F.group_norm(torch.cat(raw, dim=1).double(), 8, gn.weight.detach().cpu().double(), gn.bias.detach().cpu().double(), EPS))
+    ref = F.conv2d(n, w.double(), b.double(), padding=1).permute(0, 2, 3, 1).contiguous()
+    wt, bd = w.permute(0, 2, 3, 1).contiguous().to(DEV), b.to(DEV)
+
+    def tensors():
+        bufs = [r.permute(0, 2, 3, 1).contiguous().view(Bn, H * W, r.shape[1]).to(DEV) for r in raw]
+        ts = [hip_nhwc._T(buf, H, W, buf.shape[2], stats=(_colsums(buf), 1)) for buf in bufs]
+        return ts[0], (ts[1] if sources == 2 else None)
+
+    with torch.no_grad():
+        x, x2 = tensors()
+        c0 = dict(counted)
+        deferred = model._gn_act(x, gn, "silu", x2, conv_cout=Cout)
+        assert deferred.pending is not None and deferred.buf is x.buf and deferred.C == C
+        assert counted["gn_apply"] == c0["gn_apply"], "the pass is deferred"
+        c1 = dict(counted)
+        with _lib.thread_option(switch, 1):
+            got = model._conv(deferred, wt, bd, normed=True, rows_per_group=H * W)
+        made = {k: counted[k] - c1[k] for k in counted}
+        # the whole of it under the switch: the pass at once, no record, the same convolution
+        with _lib.thread_option(switch, 1):
+            x, x2 = tensors()
+            c2 = dict(counted)
+            normed = model._gn_act(x, gn, "silu", x2, conv_cout=Cout)
+            assert normed.pending is None
+            want = model._conv(normed, wt, bd, normed=True, rows_per_group=H * W)
+        plain = {k: counted[k] - c2[k] for k in counted}
+    torch.cuda.synchronize()
+    print(f"rerun sources={sources}: launches of the switched _conv {made}, of both calls under the switch {plain}")
+    assert made["gn_apply"] == 1 and plain["gn_apply"] == 1, (made, plain)          # exactly the one pass that was put off
+    assert made["wino1d"] == 1 and plain["wino1d"] == 1, (made, plain)
+    assert made["wino1d_nl"] == 0 and made["wino1d_nl2"] == 0, made
+    assert got.pending is None and (got.H, got.W, got.C) == (H, W, Cout)
+    assert torch.equal(got.buf, want.buf)
+    e_two = (want.buf.cpu().double().view(Bn, H, W, Cout) - ref).abs()
+    e_got = (got.buf.cpu().double().view(Bn, H, W, Cout) - ref).abs()
+    max_two, rms_two = float(e_two.max()), float(e_two.pow(2).mean().sqrt())
+    print(f"rerun sources={sources}: two-launch max {max_two:.3e} rms {rms_two:.3e} | re-run max {float(e_got.max()):.3e} "
+          f"rms {float(e_got.pow(2).mean().sqrt()):.3e}")
+    assert max_two > 0 and max_two < 1e-4 * max(1.0, float(ref.abs().max()))
+    assert float(e_got.max()) <= FUSED_VS_TWO_LAUNCH * max_two
+    assert float(e_got.pow(2).mean().sqrt()) <= FUSED_VS_TWO_LAUNCH * rms_two
