@@ -175,6 +175,10 @@ _SIGNATURES = {
     "idiff_jvp_layer_ok": (c_i, [c_i, c_i, c_i]),
     "idiff_jvp_seed_f32": (c_i, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64, c_i, c_i, c_i, c_p]),
     "idiff_jvp_layer_f32": (c_i, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64, c_i, c_i, c_i, c_i, c_p]),
+    "idiff_rk_stage_f64": (c_i, [c_p, c_i64, c_p, c_i64, c_i64, c_p, c_i, c_p, c_i64, c_p, c_i64, c_i64, c_i, c_i, c_f, c_p]),
+    "idiff_rk_error_f64": (c_i, [c_p, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_i64, c_i64, c_i, c_d, c_d, c_p, c_p, c_p]),
+    "idiff_flow_rhs_f64": (c_i, [c_p, c_i64, c_p, c_i64, c_d, c_d, c_p, c_i64, c_i64, c_i, c_i, c_p, c_i64, c_p, c_i64, c_p, c_p]),
+    "idiff_jvp_trace_f64": (c_i, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i, c_i, c_i, c_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -1921,4 +1925,103 @@ def sampler_noise_norm(z=None, B=None, D=None, seed=0, row0=0, out=None, workspa
     _dev(out, "out", dtype=torch.float64); _dev(workspace, "workspace", dtype=torch.float64)
     _check(lib().idiff_sampler_noise_norm_f32(_ptr(z), ldz, int(B), int(D), int(seed) & 0xFFFFFFFFFFFFFFFF, int(row0), workspace.data_ptr(),
                                               out.data_ptr(), _stream()), "idiff_sampler_noise_norm_f32")
+    return out
+
+
+# ------------------------------------------------------------------------------------------- probability-flow ODE (csrc/ode.hip)
+def _pitch64(t, name, B, W):
+    """Row pitch of a [B, >= W] fp64 tensor with contiguous rows."""
+    _dev(t, name, dtype=torch.float64, contiguous=False)
+    if t.ndim != 2 or t.shape[0] != B or t.shape[1] < W or t.stride(1) != 1:
+        raise RuntimeError(f"{name}: expected [{B}, >= {W}] with contiguous rows, got shape {tuple(t.shape)} strides {t.stride()}")
+    return t.stride(0) if B > 1 else max(t.stride(0), t.shape[1])
+
+
+def _stages(K, B, W):
+    """(row pitch, stage stride) of the stage derivatives K [7, B, >= W] fp64."""
+    _dev(K, "K", dtype=torch.float64, contiguous=False)
+    if K.ndim != 3 or K.shape[0] != 7 or K.shape[1] != B or K.shape[2] < W or K.stride(2) != 1:
+        raise RuntimeError(f"K: expected [7, {B}, >= {W}] with contiguous rows, got shape {tuple(K.shape)} strides {K.stride()}")
+    ldk = K.stride(1) if B > 1 else max(K.stride(1), K.shape[2])
+    return ldk, max(K.stride(0), B * ldk)
+
+
+def rk_stage(y, K, coef, x32, D, label_value, y_out=None):
+    """v = y + sum_j coef[j] K[j] over the first W = y.shape[1] columns (``coef``: up to six host floats); ``y_out`` (optional, may be
+    y) receives v, ``x32`` [B, > D] fp32 receives fl32(v[:, :D]) and ``label_value`` in column D (its later columns are not written)."""
+    B, W = y.shape
+    aug = W - int(D)
+    coef = [float(c) for c in coef]
+    ldk, strideK = _stages(K, B, W)
+    ldy = _pitch64(y, "y", B, W)
+    ldyo = _pitch64(y_out, "y_out", B, W) if y_out is not None else 0
+    ldx = _pitch(x32, "x32", B, D + 1)
+    if len(coef) > 6:
+        raise RuntimeError(f"rk_stage: {len(coef)} coefficients (at most 6)")
+    if B == 0:                                    # an empty tensor has no address to hand over
+        return y_out
+    arr = (c_d * 6)(*(coef + [0.0] * (6 - len(coef))))
+    _check(lib().idiff_rk_stage_f64(y.data_ptr(), ldy, K.data_ptr(), ldk, strideK, arr, len(coef), _ptr(y_out), ldyo, x32.data_ptr(), ldx,
+                                    B, int(D), aug, float(label_value), _stream()), "idiff_rk_stage_f64")
+    return y_out
+
+
+def rk_error(K, coef, y, y_new, atol, rtol, out=None, workspace=None):
+    """Device double: sum over all elements of ((sum_j coef[j] K[j]) / (atol + rtol max(|y|, |y_new|)))^2, ``coef`` seven host floats;
+    fp64, fixed order."""
+    B, W = y.shape
+    coef = [float(c) for c in coef]
+    if len(coef) != 7:
+        raise RuntimeError(f"rk_error: {len(coef)} coefficients (needs 7)")
+    ldk, strideK = _stages(K, B, W)
+    ldy, ldyn = _pitch64(y, "y", B, W), _pitch64(y_new, "y_new", B, W)
+    if out is None:
+        out = torch.zeros((), device=y.device, dtype=torch.float64)
+    if workspace is None:
+        workspace = reduce_workspace(y.device)
+    _dev(out, "out", dtype=torch.float64); _dev(workspace, "workspace", dtype=torch.float64)
+    if B == 0:
+        return out
+    _check(lib().idiff_rk_error_f64(K.data_ptr(), ldk, strideK, (c_d * 7)(*coef), y.data_ptr(), ldy, y_new.data_ptr(), ldyn, B, W,
+                                    float(atol), float(rtol), workspace.data_ptr(), out.data_ptr(), _stream()), "idiff_rk_error_f64")
+    return out
+
+
+def flow_rhs(x32, v, a, b, Ks, D, aug, eps=None, u=None, q=None):
+    """Ks[:, :D] = a x32 + b v; with ``aug`` Ks[:, D] = a D + b q, q the device doubles ``q`` [B] or the row sums of eps * u."""
+    B = Ks.shape[0]
+    D, aug = int(D), int(aug)
+    ldk = _pitch64(Ks, "Ks", B, D + aug)
+    ldx, ldv = _pitch(x32, "x32", B, D), _pitch(v, "v", B, D)
+    lde = _pitch(eps, "eps", B, D) if eps is not None else 0
+    ldu = _pitch(u, "u", B, D) if u is not None else 0
+    if q is not None:
+        _dev(q, "q", dtype=torch.float64)
+        if q.numel() != B:
+            raise RuntimeError(f"flow_rhs: q has {q.numel()} entries for {B} rows")
+    if B == 0:
+        return Ks
+    _check(lib().idiff_flow_rhs_f64(x32.data_ptr(), ldx, v.data_ptr(), ldv, float(a), float(b), Ks.data_ptr(), ldk, B, D, aug, _ptr(eps), lde,
+                                    _ptr(u), ldu, _ptr(q), _stream()), "idiff_flow_rhs_f64")
+    return Ks
+
+
+def jvp_trace(T, w_out, out=None, P=None, D=None, N=None, ldt=None, stride_t=None, ldw=None):
+    """out[p] = sum_{i, n} T[p][i, n] w_out[i, n] (device doubles [P]): the trace of the network Jacobian from the tangent rows ``T``
+    [P, D, N] in front of the output layer ``w_out`` [D, >= N]; tensors with contiguous rows, or explicit geometry."""
+    _dev(T, "T", contiguous=False); _dev(w_out, "w_out", contiguous=False)
+    if P is None:
+        P, D, N, ldt, stride_t = _points3(T, "T")
+        if w_out.ndim != 2 or w_out.shape[0] != D or w_out.shape[1] < N:
+            raise RuntimeError(f"jvp_trace: w_out {tuple(w_out.shape)} for T {tuple(T.shape)}")
+        ldw = _ld(w_out, "w_out")
+    if out is None:
+        out = torch.empty(P, device=T.device, dtype=torch.float64)
+    _dev(out, "out", dtype=torch.float64)
+    if out.numel() != P:
+        raise RuntimeError(f"jvp_trace: out has {out.numel()} entries for P = {P}")
+    if P == 0:
+        return out
+    _check(lib().idiff_jvp_trace_f64(T.data_ptr(), ldt, stride_t, w_out.data_ptr(), ldw, out.data_ptr(), P, D, N, _stream()),
+           "idiff_jvp_trace_f64")
     return out

@@ -76,6 +76,41 @@ def _weights(net):
     return ws, pk["b"], pk["kpad"]
 
 
+def forward_acts(ws, bs, h, kpad, acts=None):
+    """The ELU output [P, pad4(N)] of every hidden layer for the padded input rows ``h`` [P, kpad]: FCN.forward's launches with every
+    activation kept (rows padded to 16 bytes, pads zero).  ``acts``: buffers to reuse (their pads must be zero)."""
+    P = h.shape[0]
+    out, K = [], kpad
+    for i, (w, b) in enumerate(zip(ws[:-1], bs[:-1])):
+        N = w.shape[0]
+        a = torch.zeros(P, pad4(N), device=h.device, dtype=torch.float32) if acts is None else acts[i]
+        _lib.gemm(h, w, out=a, epilogue=_lib.make_epilogue(bias=b, act="elu"), M=P, N=N, K=K, lda=h.stride(0), ldb=w.stride(0),
+                  ldc=a.stride(0))
+        out.append(a)
+        h, K = a, pad4(N)                      # the pad columns of the activations and of the weights are zero
+    return out
+
+
+def tangent_rows(ws, acts, D, n_layers):
+    """(flat buffer, ld): the tangent rows [P][D, ld] of the D input directions behind the first ``n_layers`` Linear layers (the seed and
+    ws[1:n_layers]; a layer without an activation behind it, the output layer, gets no ELU' factor), in one of two ping-pong buffers."""
+    P = acts[0].shape[0]
+    width = max(pad4(w.shape[0]) for w in ws[:n_layers])
+    bufs = [torch.empty(P * D * width, device=acts[0].device, dtype=torch.float32) for _ in range(2)]
+    N = ws[0].shape[0]
+    ld = pad4(N)
+    _lib.jvp_seed(ws[0], acts[0], out=bufs[0], P=P, D=D, N=N, ldw=ws[0].stride(0), ld_act=acts[0].stride(0), ldt=ld, stride_t=D * ld)
+    cur = 0
+    for i, w in enumerate(ws[1:n_layers], start=1):
+        act = acts[i] if i < len(acts) else None
+        N, K = w.shape[0], ws[i - 1].shape[0]
+        ldc = pad4(N)
+        _lib.jvp_layer(bufs[cur], w, act=act, out=bufs[1 - cur], P=P, R=D, N=N, K=K, lda=ld, stride_a=D * ld, ldw=w.stride(0),
+                       ld_act=None if act is None else act.stride(0), ldc=ldc, stride_c=D * ldc)
+        cur, ld = 1 - cur, ldc
+    return bufs[cur], ld
+
+
 def _chunk_jacobians(net, sde, xs, t):
     """J [P, D, D] of one chunk of points (see ``network_jacobians``)."""
     P, D = xs.shape
@@ -90,29 +125,10 @@ def _chunk_jacobians(net, sde, xs, t):
     tpad[:, 0] = labels
     h = torch.empty(P, kpad, device=dev, dtype=torch.float32)
     _lib.concat_cols(centre.contiguous(), D, tpad, kpad - D, h, P)
-    acts, K = [], kpad
-    for w, b in zip(ws[:-1], bs[:-1]):
-        N = w.shape[0]
-        a = torch.zeros(P, pad4(N), device=dev, dtype=torch.float32)
-        _lib.gemm(h, w, out=a, epilogue=_lib.make_epilogue(bias=b, act="elu"), M=P, N=N, K=K, lda=h.stride(0), ldb=w.stride(0),
-                  ldc=a.stride(0))
-        acts.append(a)
-        h, K = a, pad4(N)                      # the pad columns of the activations and of the weights are zero
+    acts = forward_acts(ws, bs, h, kpad)
     # 2.-4. seed, hidden layers, output layer: two ping-pong buffers of tangent rows
-    width = max(pad4(w.shape[0]) for w in ws)
-    bufs = [torch.empty(P * D * width, device=dev, dtype=torch.float32) for _ in range(2)]
-    N = ws[0].shape[0]
-    ld = pad4(N)
-    _lib.jvp_seed(ws[0], acts[0], out=bufs[0], P=P, D=D, N=N, ldw=ws[0].stride(0), ld_act=acts[0].stride(0), ldt=ld, stride_t=D * ld)
-    cur = 0
-    for i, w in enumerate(ws[1:], start=1):
-        act = acts[i] if i < len(acts) else None
-        N, K = w.shape[0], ws[i - 1].shape[0]
-        ldc = pad4(N)
-        _lib.jvp_layer(bufs[cur], w, act=act, out=bufs[1 - cur], P=P, R=D, N=N, K=K, lda=ld, stride_a=D * ld, ldw=w.stride(0),
-                       ld_act=None if act is None else act.stride(0), ldc=ldc, stride_c=D * ldc)
-        cur, ld = 1 - cur, ldc
-    out = bufs[cur][:P * D * ld].view(P, D, ld)[:, :, :D]
+    buf, ld = tangent_rows(ws, acts, D, len(ws))
+    out = buf[:P * D * ld].view(P, D, ld)[:, :, :D]
     # 5. get_score_fn's factor: -1 / std, rounded to fp32 once
     return out * (-1.0 / std).float().view(P, 1, 1)
 

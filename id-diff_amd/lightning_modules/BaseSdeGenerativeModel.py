@@ -37,6 +37,19 @@ class BaseSdeGenerativeModel(nn.Module):
         seed = int(self.config.get('seed', 42)) if seed is None else int(seed)
         return sampling_fn(self.score_model, show_evolution=show_evolution, seed=seed)
 
+    def ode_sample(self, num_samples=None, z=None, seed=None):
+        """``(samples, nfe)`` from the probability-flow ODE sampler (``sampling.get_ode_sampler``, integrated from T to
+        ``sampling_eps``): from the latent code ``z``, or from a draw of the prior keyed by ``seed`` (default ``config.seed``)."""
+        from .. import sampling
+        if not hasattr(self, 'sde'):
+            self.configure_sde(self.config)
+        if z is not None:
+            num_samples = len(z)
+        shape = self.default_sampling_shape if num_samples is None else [int(num_samples)] + list(self.config.data.shape)
+        sampler = sampling.get_ode_sampler(self.sde, shape, eps=self.sampling_eps)
+        seed = int(self.config.get('seed', 42)) if seed is None else int(seed)
+        return sampler(self.score_model, z=z, seed=seed)
+
     def load_from_checkpoint(self, checkpoint_path, **kwargs):
         """Lightning ``.ckpt`` = torch.save({'state_dict': {'score_model.<k>': tensor}, 'hyper_parameters': ...}).
 

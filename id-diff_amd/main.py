@@ -10,6 +10,11 @@ drawn from the current weights and the mean estimated dimension of the checkpoin
 predictor-corrector sampler (sampling.py) on one GPU, writes ``<log_path>/<log_name>/samples/samples.pkl`` and prints the minimum,
 maximum and mean of the samples' norms.
 
+``--mode generate --sampler ode`` draws them with the probability-flow ODE sampler (adaptive RK45, ode.py) instead; the pickle then
+holds ``nfe``.  ``--mode likelihood [--checkpoint_path ...] [--num_samples M] [--exact] [--seed S]`` evaluates the log-likelihood of the
+first M (default 1000) points of the config's test split under an ``fcn`` score network on one GPU (likelihood.py), writes
+``<log_path>/<log_name>/likelihood/likelihood.pkl`` = {bpd, z, nfe, exact} and prints the mean, minimum and maximum.
+
 Run it from the repo root as ``python id-diff_amd/main.py ...`` or, for several GPUs of one node,
 ``python -m torch.distributed.run --nproc-per-node N id-diff_amd/main.py ...``.
 
@@ -62,6 +67,10 @@ def parse(argv=None):
                          "estimated dimension (0: never)")
     ap.add_argument("--num_samples", type=int, default=None, help="(--mode generate) number of samples to draw (default 1000)")
     ap.add_argument("--seed", type=int, default=None, help="(--mode generate) seed of the noise streams (default: config.seed)")
+    ap.add_argument("--sampler", default=None, choices=("pc", "ode"),
+                    help="(--mode generate) 'ode': draw the samples with the probability-flow ODE sampler instead of the config's")
+    ap.add_argument("--exact", action="store_true",
+                    help="(--mode likelihood) the exact divergence instead of Hutchinson's estimator")
     ap.add_argument("--dim_method", default=None, choices=("sampling", "jacobian"),
                     help="(--mode manifold_dimension) sets the config key dim_estimation.method: 'sampling' (default) or 'jacobian', the "
                          "score Jacobian of an fcn network in closed form (one GPU)")
@@ -90,7 +99,19 @@ def run_generate(flags, config):
         raise SystemExit("--num_samples must be positive")
     log_path = flags.log_path if flags.log_path != "./" or not config.logging.get("log_path") else config.logging.log_path
     return run_lib.generate(config, checkpoint_path=config.model.get("checkpoint_path"), num_samples=flags.num_samples, seed=flags.seed,
-                            log_path=log_path, log_name=flags.log_name)
+                            log_path=log_path, log_name=flags.log_name, **({"sampler": flags.sampler} if flags.sampler else {}))
+
+
+def run_likelihood(flags, config):
+    from id_diff_amd import likelihood as _likelihood
+    _likelihood.check_config(config)     # before anything touches the GPU: another network exits with the scope message
+    if flags.gpus is not None and flags.gpus > 1:
+        raise SystemExit("--mode likelihood runs on one GPU: --gpus must be 1 (or left out)")
+    if flags.num_samples is not None and flags.num_samples < 1:
+        raise SystemExit("--num_samples must be positive")
+    log_path = flags.log_path if flags.log_path != "./" or not config.logging.get("log_path") else config.logging.log_path
+    return run_lib.likelihood(config, checkpoint_path=config.model.get("checkpoint_path"), num_samples=flags.num_samples,
+                              exact=flags.exact, seed=flags.seed, log_path=log_path, log_name=flags.log_name)
 
 
 def main(argv=None):
@@ -112,6 +133,9 @@ def main(argv=None):
         return
     if flags.mode == 'generate':
         run_generate(flags, config)
+        return
+    if flags.mode == 'likelihood':
+        run_likelihood(flags, config)
         return
     if flags.mode not in _HOT_MODES:
         raise SystemExit(f"mode {flags.mode!r} is outside the scope of id-diff_amd (the MI355X build covers "

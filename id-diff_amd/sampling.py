@@ -24,7 +24,10 @@ d x and g are drift and diffusion of the forward SDE at t (d = 0 for VE, -beta(t
 Two execution paths behind ``pc_sampler``: any model ``mutils.get_score_fn`` accepts runs ``score_fn`` + one step launch per update;
 ``models.fcn.FCN`` keeps the state in the padded input rows of its first layer and runs ``hidden_layers + 2`` idiff_gemm_f32 launches
 and one step launch that reads the raw output (score = -out / std rides in b), updates the state in place and writes the next time
-feature.  Out of scope: the ODE sampler, ``heun``, ``mala``, the conditional samplers, inpainting, EMA weights, several GPUs.
+feature.  Out of scope: ``heun``, ``mala``, the conditional samplers, inpainting, EMA weights, several GPUs.
+
+The probability-flow ODE sampler (``get_ode_sampler``) arrives through its own name and ``generate(sampler='ode')`` /
+``BaseSdeGenerativeModel.ode_sample``; ``sampling.method = 'ode'`` in ``get_sampling_fn`` and ``sample(ode=True)`` still refuse.
 """
 import math
 
@@ -386,6 +389,83 @@ def get_pc_sampler(sde, shape, predictor, corrector, snr, n_steps=1, probability
     return pc_sampler
 
 
+# ---------------------------------------------------------------------------------------------- the probability-flow ODE
+def flow_coefficients(sde, t):
+    """``(a, b, label, std)`` as fp64 host scalars: the reverse SDE's ``probability_flow=True`` drift at time t is a x + b raw with raw
+    the fcn output (score = -raw / std): a = d, b = g^2 / (2 std), with d, g and std the fp64 expressions of the schedule evaluated at
+    the fp32 value of t, the time the network's label carries (the reference's ``vec_t`` is fp32 too), and label the fp32 product
+    ``label_of`` forms.  Coefficients at the unrounded t beside a label at the rounded one cost the VE sampler of the fixture ten times
+    its deviation from the fp64 oracle."""
+    t32 = float(np.float32(t))
+    d, g = _drift_diffusion(sde, t32)
+    std = marginal_std(sde, t32)
+    return d, 0.5 * g * g / std, label_of(sde, t), std
+
+
+def get_ode_sampler(sde, shape, denoise=False, rtol=1e-5, atol=1e-5, method='RK45', eps=1e-3):
+    """unconditional.py:66-131 of the reference.  Returns ``ode_sampler(model, z=None, *, seed=None) -> (x, nfe)``: the
+    probability-flow ODE integrated from sde.T to eps by ``ode.rk45`` (scipy's RK45 step control on the host, the state in fp64 on the
+    device), from the latent code ``z`` or a draw of the prior from the stream of ``seed``.  A ``models.fcn.FCN`` with [B, D] samples runs
+    its own launches (likelihood.FcnFlow); any other model ``get_score_fn`` accepts runs through its ``score_fn``.  ``denoise``: one
+    noise-free reverse-diffusion step at eps."""
+    from . import _lib, likelihood, ode
+    from .models import utils as mutils
+    from .models.fcn import FCN
+    likelihood.check_method(method)
+    _kind(sde)
+    shape = [int(v) for v in shape]
+    B, D = shape[0], int(np.prod(shape[1:]))
+    p_std = prior_std(sde)
+    eps = float(eps)
+
+    def ode_sampler(model, z=None, *, seed=None):
+        device = model.device
+        if device.type != 'cuda':
+            raise RuntimeError(f"ode_sampler: the model is on {device}; id-diff_amd samples on the MI355X only (no CPU path)")
+        fast = isinstance(model, FCN) and len(shape) == 2
+        with torch.no_grad():
+            y = likelihood.state_buffer(B, D, device)
+            if z is None:
+                x0 = torch.zeros(B, D, device=device, dtype=torch.float32)
+                _lib.sampler_step(x0, x0, 0.0, 0.0, p_std, D=D, seed=_stream_key(42 if seed is None else int(seed), 0, SALT_PRIOR))
+            else:
+                x0 = torch.as_tensor(z, dtype=torch.float32).to(device).reshape(B, D)
+            y.copy_(x0.double())
+            if fast:
+                flow = likelihood.FcnFlow(likelihood.fcn_of(model), sde, B, aug=0)
+                x32, rhs = flow.x32, flow.rhs
+
+                def score_at_eps():
+                    return flow.forward(), -1.0 / marginal_std(sde, eps)
+            else:
+                score_fn = mutils.get_score_fn(sde, model, conditional=False, train=False, continuous=True)
+                x32 = torch.zeros(B, (D + 1 + 3) // 4 * 4, device=device, dtype=torch.float32)
+                ones = torch.ones(B, device=device, dtype=torch.float32)
+
+                def score(t):
+                    return score_fn(x32[:, :D].contiguous().view(shape), ones * float(np.float32(t))).reshape(B, D).contiguous()
+
+                def rhs(stage, t, K, v=None):
+                    d, g = _drift_diffusion(sde, float(np.float32(t)))
+                    _lib.flow_rhs(x32, score(t), d, -0.5 * g * g, K[stage], D, 0)
+
+                def score_at_eps():
+                    return score(eps), 1.0
+            K = torch.zeros(7, B, y.stride(0), device=device, dtype=torch.float64)[:, :, :D]
+            nfe, _, _, _ = ode.rk45(rhs, float(sde.T), eps, y, x32, D, lambda t: label_of(sde, t), rtol=rtol, atol=atol, K=K)
+            x = y.float()
+            if denoise:
+                _lib.rk_stage(y, K, [], x32, D, label_of(sde, eps))
+                s, scale = score_at_eps()
+                a, b, _ = predictor_coefficients(sde, 'reverse_diffusion', eps, False)
+                mean = torch.zeros_like(x)
+                _lib.sampler_step(x, s, a, b, 0.0, mean_out=mean, D=D, score_scale=scale)
+                x = mean
+            return x.reshape(shape).contiguous(), nfe
+
+    return ode_sampler
+
+
 def get_sampling_fn(config, sde, shape, eps):
     """unconditional.py:13-49; ``method == 'ode'`` (scipy's RK45 driven from the host) is not built."""
     s = sampling_config(config)
@@ -405,9 +485,11 @@ def ksphere_evaluation(samples):
     return dict(min_norm=float(norms.min()), max_norm=float(norms.max()), mean_norm=float(norms.mean()))
 
 
-def generate(config, checkpoint_path=None, num_samples=None, seed=None, log_path=None, log_name=None, log=print):
+def generate(config, checkpoint_path=None, num_samples=None, seed=None, log_path=None, log_name=None, log=print, sampler=None):
     """``--mode generate``: draw ``num_samples`` (default 1000, the callback's number) samples from the config's model on one GPU and
-    write ``<log_path>/<log_name>/samples/samples.pkl`` = {samples, times, steps, min_norm, max_norm, mean_norm}."""
+    write ``<log_path>/<log_name>/samples/samples.pkl`` = {samples, times, steps, min_norm, max_norm, mean_norm}.  ``sampler='ode'``
+    draws them with the probability-flow ODE sampler instead of the config's (``--sampler ode``); the pickle then holds
+    {samples, nfe, min_norm, max_norm, mean_norm}."""
     import os
     import pickle
     from .lightning_modules.utils import create_lightning_module
@@ -417,15 +499,21 @@ def generate(config, checkpoint_path=None, num_samples=None, seed=None, log_path
     module.configure_sde(config)
     module.to(device).eval()
     n = 1000 if num_samples is None else int(num_samples)
-    samples, info = module.sample(num_samples=n, seed=seed)
+    if sampler not in (None, 'pc', 'ode'):
+        raise ValueError(f"generate: sampler {sampler!r} unknown (have: 'pc', the config's sampler, and 'ode')")
+    if sampler == 'ode':
+        samples, nfe = module.ode_sample(num_samples=n, seed=seed)
+        info = {'nfe': int(nfe)}
+    else:
+        samples, info = module.sample(num_samples=n, seed=seed)
     norms = ksphere_evaluation(samples)
     log_path = log_path if log_path is not None else (config.logging.get('log_path') or './')
     log_name = log_name if log_name is not None else (config.logging.get('log_name') or 'generate')
     path = os.path.join(log_path, log_name, 'samples', 'samples.pkl')
     os.makedirs(os.path.dirname(path), exist_ok=True)
+    record = dict(nfe=info['nfe']) if sampler == 'ode' else dict(times=info['times'].cpu().numpy(), steps=int(info['steps']))
     with open(path, 'wb') as f:
-        pickle.dump(dict(samples=samples.cpu().numpy().astype(np.float32), times=info['times'].cpu().numpy(), steps=int(info['steps']),
-                         **norms), f)
+        pickle.dump(dict(samples=samples.cpu().numpy().astype(np.float32), **record, **norms), f)
     if log is not None:
         log(f"{n} samples: min_norm {norms['min_norm']:.6g} max_norm {norms['max_norm']:.6g} mean_norm {norms['mean_norm']:.6g}; wrote {path}")
     return samples, dict(info, **norms, path=path)

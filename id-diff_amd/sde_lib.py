@@ -1,11 +1,17 @@
 """SDE perturbation kernels used by the manifold_dimension path (host-side scalars + tiny device vectors).
 
-Mirrors /root/reference/sde_lib.py: ``VESDE`` (:316-347) and ``VPSDE`` (:222-252), ``marginal_prob`` only --
-the reverse SDE, discretisation and priors belong to sampling/training and are out of scope.
+Mirrors /root/reference/sde_lib.py: ``VESDE`` (:316-347) and ``VPSDE`` (:222-252), ``marginal_prob`` and ``prior_logp`` --
+the reverse SDE and the discretisations are host scalars in sampling.py.
 The per-sample std vector has B entries; it is produced with torch elementwise ops on the device the time
 vector lives on (plumbing, a few hundred bytes) and consumed by the fused HIP kernels.
 """
+import math
+
 import torch
+
+
+def _sumsq_rows(z):
+    return torch.sum(z.reshape(z.shape[0], -1) ** 2, dim=1)
 
 
 class SDE:
@@ -36,6 +42,11 @@ class VESDE(SDE):
         lo, hi = cached[1], cached[2]
         return x, lo * (hi / lo) ** t
 
+    def prior_logp(self, z):
+        """log N(z; 0, sigma_max^2 I) per row, summed over all non-batch dimensions (sde_lib.py:375-379 of the reference)."""
+        n = math.prod(z.shape[1:])
+        return -n / 2. * math.log(2 * math.pi * self.sigma_max ** 2) - _sumsq_rows(z) / (2 * self.sigma_max ** 2)
+
 
 class VPSDE(SDE):
     def __init__(self, beta_min=0.1, beta_max=20, N=1000):
@@ -46,6 +57,12 @@ class VPSDE(SDE):
         log_mean_coeff = -0.25 * t ** 2 * (self.beta_1 - self.beta_0) - 0.5 * t * self.beta_0
         mean = torch.exp(log_mean_coeff).reshape((-1,) + (1,) * (x.ndim - 1)) * x
         return mean, torch.sqrt(1. - torch.exp(2. * log_mean_coeff))
+
+    def prior_logp(self, z):
+        """log N(z; 0, I) per row, summed over all non-batch dimensions.  The reference's VP and subVP versions (sde_lib.py:259-263,
+        309-313) sum dim=(1, 2, 3) and raise on [B, D] data; this one serves any rank (subVPSDE inherits it)."""
+        n = math.prod(z.shape[1:])
+        return -n / 2. * math.log(2 * math.pi) - _sumsq_rows(z) / 2.
 
 
 class subVPSDE(VPSDE):

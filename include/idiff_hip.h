@@ -860,6 +860,37 @@ int idiff_jvp_seed_f32(const float *W1, int64_t ldw, const float *act, int64_t l
 int idiff_jvp_layer_f32(const float *A, int64_t lda, int64_t strideA, const float *W, int64_t ldw, const float *act, int64_t ld_act,
                         float *C, int64_t ldc, int64_t strideC, int P, int R, int N, int K, void *stream);
 
+/* ------------------------------------------------------------------ probability-flow ODE: adaptive Runge-Kutta (csrc/ode.hip) */
+
+/* The arithmetic over the batch of one adaptive Runge-Kutta step whose step-size control runs on the host (ode.py).  State y [B, W]
+ * doubles, W = D + aug (aug = 1: column D carries log p); stage derivatives K [7][B, W] doubles, stage j at K + j strideK; pitches in
+ * elements.  fp64 throughout, every output rounded once, sums over stages in index order with one fma per term, reductions over fixed
+ * ranges in a fixed order, no atomics: the same arguments give the same bits.  B == 0 (P == 0) returns 0 without a launch; a bad size,
+ * pitch or alignment returns IDIFF_EINVAL before any device call, with a message that starts with the kernel's name.
+ *
+ *   rk_stage   v = y + sum_{j < ns} c[j] K_j, 0 <= ns <= 6, c a HOST array (h a_sj, or h b_j for the solution).  y_out (or NULL) = v;
+ *              x32[r, c < D] = fl32(v[r, c]) and x32[r, D] = label_value: the padded first-layer input rows [B, ldx >= D + 1] of the
+ *              network.  Columns of x32 beyond D are never written.  y_out may be y.
+ *              |v - exact| <= (ns + 1) 2^-53 (|y| + sum_j |c_j K_j|), the fp32 rows 2^-24 |v| more.
+ *   rk_error   *out (device double) = sum_{r, c} ((sum_{j < 7} e[j] K_j[r, c]) / (atol + rtol max(|y[r, c]|, |y_new[r, c]|)))^2, e a HOST
+ *              array (h E_j).  Two launches; ws: IDIFF_REDUCE_WS_DOUBLES doubles.
+ *   flow_rhs   Ks[r, c < D] = a x32[r, c] + b v[r, c] (x32, v fp32); with aug: Ks[r, D] = a D + b q_r, where q_r = q[r] (device doubles:
+ *              the exact trace) or, q NULL, sum_c eps[r, c] u[r, c] over fp32 rows (Hutchinson: u the vector-Jacobian product of eps), one
+ *              fixed-order sum per row.  Pass q, or eps and u.
+ *   jvp_trace  tr[p] = sum_{i < D} sum_{n < N} T[p][i, n] Wout[i, n]: the trace of the network Jacobian from the tangent rows T [P][D, ldt]
+ *              (point stride strideT) in front of the output layer Wout [D, ldw].  One workgroup per point.  T and Wout 16-byte aligned,
+ *              ldt, ldw, strideT multiples of 4 floats, ldt and ldw at least N rounded up to 4 (those columns are read, not used).
+ *
+ * rk_stage and flow_rhs move 16 bytes per access when the double pointers are 16-byte aligned and their pitches even. */
+int idiff_rk_stage_f64(const double *y, int64_t ldy, const double *K, int64_t ldk, int64_t strideK, const double *c, int ns, double *y_out,
+                       int64_t ldyo, float *x32, int64_t ldx, int64_t B, int D, int aug, float label_value, void *stream);
+int idiff_rk_error_f64(const double *K, int64_t ldk, int64_t strideK, const double *e, const double *y, int64_t ldy, const double *y_new,
+                       int64_t ldyn, int64_t B, int W, double atol, double rtol, double *ws, double *out, void *stream);
+int idiff_flow_rhs_f64(const float *x32, int64_t ldx, const float *v, int64_t ldv, double a, double b, double *Ks, int64_t ldk, int64_t B,
+                       int D, int aug, const float *eps, int64_t lde, const float *u, int64_t ldu, const double *q, void *stream);
+int idiff_jvp_trace_f64(const float *T, int64_t ldt, int64_t strideT, const float *Wout, int64_t ldw, double *tr, int P, int D, int N,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif
