@@ -45,6 +45,8 @@ _SIGNATURES = {
     "idiff_set_thread_option": (c_i, [ctypes.c_char_p, c_i, c_i]),
     "idiff_upfirdn2d_f32": (c_i, [c_p, c_p, c_p] + [c_i] * 14 + [c_p]),
     "idiff_upfirdn2d_route": (ctypes.c_char_p, [c_p, c_p] + [c_i] * 14),
+    "idiff_upfirdn2d_gn_f32": (c_i, [c_p, c_p, c_p, c_i, c_p] + [c_i] * 14 + [c_p]),
+    "idiff_upfirdn2d_gn_ok": (c_i, [c_p, c_p, c_i, c_p] + [c_i] * 14),
     "idiff_fused_bias_act_f32": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_i, c_f, c_f, c_p]),
     "idiff_upfirdn2d_f16": (c_i, [c_p, c_p, c_p] + [c_i] * 14 + [c_p]),
     "idiff_upfirdn2d_f64": (c_i, [c_p, c_p, c_p] + [c_i] * 14 + [c_p]),
@@ -388,6 +390,27 @@ def upfirdn2d_route(x, out, major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x
     return None if name is None else name.decode()
 
 
+def upfirdn2d_gn(x, k, coef, act, out, major, in_h, in_w, minor, up_x, up_y, down_x, down_y, px0, px1, py0, py1):
+    """upfirdn2d_raw (fp32, NHWC) of act(a x + b): ``x`` is a GroupNorm's RAW input, ``coef`` [major, minor, 2] from
+    groupnorm_reader_coef, ``act`` "silu" or None.  Served on the two NHWC resampling kernels of the score networks
+    (upfirdn2d_gn_ok); anything else is refused, nothing launched."""
+    kh, kw = k.shape
+    for t, name in ((x, "input"), (k, "kernel"), (coef, "coef"), (out, "output")):
+        _dev(t, name)
+    if coef.numel() != major * minor * 2:
+        raise RuntimeError(f"upfirdn2d_gn: coef holds {coef.numel()} floats, [major, minor, 2] = {major * minor * 2} expected")
+    _check(lib().idiff_upfirdn2d_gn_f32(x.data_ptr(), k.data_ptr(), coef.data_ptr(), ACT[act], out.data_ptr(), major, in_h, in_w, minor,
+                                        kh, kw, up_x, up_y, down_x, down_y, px0, px1, py0, py1, _stream()), "idiff_upfirdn2d_gn_f32")
+
+
+def upfirdn2d_gn_ok(x, coef, act, out, major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, px0, px1, py0, py1):
+    """True where upfirdn2d_gn serves these arguments; x / coef / out: tensors or raw addresses (only their alignment matters).  Off
+    under IDIFF_NO_FUSED_GN_FIR.  Launches nothing."""
+    addr = lambda t: t if isinstance(t, int) else t.data_ptr()
+    return bool(lib().idiff_upfirdn2d_gn_ok(addr(x), addr(coef), ACT[act], addr(out), major, in_h, in_w, minor, kh, kw, up_x, up_y,
+                                            down_x, down_y, px0, px1, py0, py1))
+
+
 def upfirdn2d_out_size(in_size, up, down, pad0, pad1, k):
     return (in_size * up + pad0 + pad1 - k) // down + 1
 
@@ -697,6 +720,17 @@ def groupnorm_coef(ws1, ns1, C1, ws2, ns2, C2, B, HW, G, eps, gamma, beta, coef)
     if coef.numel() != B * (C1 + (C2 if ws2 is not None else 0)) * 2:
         raise RuntimeError(f"groupnorm_coef: coef holds {coef.numel()} floats, [B, C, 2] = {B * (C1 + C2) * 2} expected")
     _check(lib().idiff_groupnorm_coef_f32(ws1.data_ptr(), ns1, C1, _ptr(ws2), ns2, C2, B, HW, G, eps, gamma.data_ptr(), beta.data_ptr(),
+                                          coef.data_ptr(), _stream()), "idiff_groupnorm_coef_f32")
+    return coef
+
+
+def groupnorm_reader_coef(ws, ns, C, B, HW, G, eps, gamma, beta, coef):
+    """groupnorm_coef of one source for the readers that are not the convolution loader (upfirdn2d_gn): the same C entry, a name of its
+    own so that the launches of either kind can be told apart."""
+    _dev(coef, "coef"); _dev(gamma, "gamma"); _dev(beta, "beta")
+    if coef.numel() != B * C * 2:
+        raise RuntimeError(f"groupnorm_reader_coef: coef holds {coef.numel()} floats, [B, C, 2] = {B * C * 2} expected")
+    _check(lib().idiff_groupnorm_coef_f32(ws.data_ptr(), ns, C, 0, 0, 0, B, HW, G, eps, gamma.data_ptr(), beta.data_ptr(),
                                           coef.data_ptr(), _stream()), "idiff_groupnorm_coef_f32")
     return coef
 

@@ -575,6 +575,161 @@ upfirdn2d_nhwc_up2_block(const float *__restrict__ x, const float *__restrict__ 
   }
 }
 
+// ---------------------------------------------------------------- NHWC, GroupNorm (+ SiLU) applied to what the resampler loads
+// The two kernels above for an input that is a GroupNorm's RAW input (idiff_upfirdn2d_gn_f32): coef [major, minor, 2] holds
+// (a, b) = (rstd gamma, beta - mean rstd gamma) per (image, channel) from idiff_groupnorm_coef_f32, and every loaded sample becomes
+// act(a x + b) -- one fma where the pass rounds three times, and act_apply's SiLU, the pass's own.  A thread's channel quad and a
+// workgroup's plane are fixed: the eight coefficients are fetched once.  A tap outside the image is an exact zero, never act(b): the
+// norm is applied on the inside of the select that the plain kernels make.  The normalised tensor is never written (the pass these
+// kernels replace runs at the copy rate, and both kernels are bound by their memory traffic with vector ALU to spare).
+template <int ACT>
+__device__ __forceinline__ float4 gn_act4(const float4 s, const float4 c01, const float4 c23) {
+  return make_float4(idiff::act_apply(fmaf(c01.x, s.x, c01.y), ACT), idiff::act_apply(fmaf(c01.z, s.y, c01.w), ACT),
+                     idiff::act_apply(fmaf(c23.x, s.z, c23.y), ACT), idiff::act_apply(fmaf(c23.z, s.w, c23.w), ACT));
+}
+
+// FIR + decimation by 2 with a 4x4 kernel (downsample_2d of the score networks; the plain form is upfirdn2d_nhwc_rows<0>) on
+// act(a x + b).  With the norm in the loader the vector ALU is what binds: the row form evaluates every input sample's SiLU once per
+// output that reads it, four times each (measured: 2.0x the plain kernel's time at [2240, 32, 32, 128]).  So a thread produces a 2 x 2
+// block of outputs from its 6 x 6 window -- 9 loaded samples per output instead of 16 -- one window row at a time: six loads in
+// flight, four accumulators.  grid.x = (plane, pair of output rows); odd out_h / out_w: the last block stores what exists.
+template <int ACT>
+__global__ void __launch_bounds__(256)
+upfirdn2d_nhwc_down2_block_gn(const float *__restrict__ x, const float *__restrict__ k, const float *__restrict__ coef,
+                              float *__restrict__ out, UfdParams p, int cv, int col_step) {
+  __shared__ float taps[16];
+  if (threadIdx.x < 16) {
+    const int ky = threadIdx.x >> 2, kx = threadIdx.x & 3;
+    taps[threadIdx.x] = k[(3 - ky) * 4 + (3 - kx)];
+  }
+  __syncthreads();
+  const int bid = xcd_contiguous(blockIdx.x, gridDim.x);
+  const int brows = (p.out_h + 1) >> 1;
+  const int plane = bid / brows, Y = bid - plane * brows;
+  const int c4 = threadIdx.x % cv, col0 = threadIdx.x / cv;
+  if (col0 >= col_step) return;
+  float w[16];
+#pragma unroll
+  for (int t = 0; t < 16; ++t) w[t] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, taps[t])));
+  const float4 *cp = reinterpret_cast<const float4 *>(coef) + ((int64_t)plane * cv + c4) * 2;
+  const float4 c01 = cp[0], c23 = cp[1];
+  const int by = 4 * Y - p.pad_y0;                               // first window row: output row 2 Y reads by .. by + 3, 2 Y + 1 by + 2 .. by + 5
+  const bool row1 = 2 * Y + 1 < p.out_h;
+  const float4 *xp = reinterpret_cast<const float4 *>(x) + (int64_t)plane * p.in_h * p.in_w * cv + c4;
+  float4 *op = reinterpret_cast<float4 *>(out) + ((int64_t)plane * p.out_h + 2 * Y) * p.out_w * cv + c4;
+  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int X = col0; 2 * X < p.out_w; X += col_step) {
+    const int bx = 4 * X - p.pad_x0;
+    float4 acc[2][2] = {{zero, zero}, {zero, zero}};
+#pragma unroll
+    for (int rr = 0; rr < 6; ++rr) {
+      const int iy = by + rr;
+      const bool vy = (unsigned)iy < (unsigned)p.in_h;
+      const float4 *row = xp + (int64_t)(vy ? iy : 0) * p.in_w * cv;
+      float4 s[6];
+#pragma unroll
+      for (int cc = 0; cc < 6; ++cc) {
+        const int ix = bx + cc;
+        const bool ok = vy && (unsigned)ix < (unsigned)p.in_w;
+        const float4 v = gn_act4<ACT>(row[(int64_t)(ok ? ix : 0) * cv], c01, c23);   // an "off" tap reads a pixel that exists ...
+        s[cc] = ok ? v : zero;                                                         // ... and is an exact zero
+      }
+#pragma unroll
+      for (int a = 0; a < 2; ++a) {
+        const int ky = rr - 2 * a;
+        if (ky < 0 || ky > 3) continue;
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            const float wt = w[ky * 4 + t];
+            const float4 sv = s[t + 2 * b];
+            acc[a][b].x += sv.x * wt; acc[a][b].y += sv.y * wt; acc[a][b].z += sv.z * wt; acc[a][b].w += sv.w * wt;
+          }
+      }
+    }
+    const bool col1 = 2 * X + 1 < p.out_w;
+    op[(int64_t)(2 * X) * cv] = acc[0][0];
+    if (col1) op[(int64_t)(2 * X + 1) * cv] = acc[0][1];
+    if (row1) {
+      op[((int64_t)p.out_w + 2 * X) * cv] = acc[1][0];
+      if (col1) op[((int64_t)p.out_w + 2 * X + 1) * cv] = acc[1][1];
+    }
+  }
+}
+
+// upfirdn2d_nhwc_up2_block on act(a x + b).  A thread walks a run of neighbouring input pixels of its row and keeps the 3 x 3 window in
+// registers: three new samples (and their SiLU) per pixel instead of nine; the next column's loads are issued before the current
+// pixel's four outputs are formed and stored.
+template <int ACT>
+__global__ void __launch_bounds__(256)
+upfirdn2d_nhwc_up2_block_gn(const float *__restrict__ x, const float *__restrict__ k, const float *__restrict__ coef,
+                            float *__restrict__ out, UfdParams p, int cv, int col_step) {
+  __shared__ float taps[16];
+  if (threadIdx.x < 16) {
+    const int ky = threadIdx.x >> 2, kx = threadIdx.x & 3;
+    taps[threadIdx.x] = k[(3 - ky) * 4 + (3 - kx)];
+  }
+  __syncthreads();
+  const int bid = xcd_contiguous(blockIdx.x, gridDim.x);
+  const int plane = bid / p.in_h, i = bid - plane * p.in_h;
+  const int c4 = threadIdx.x % cv, col0 = threadIdx.x / cv;
+  if (col0 >= col_step) return;
+  float w[16];
+#pragma unroll
+  for (int t = 0; t < 16; ++t) w[t] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, taps[t])));
+  const float4 *cp = reinterpret_cast<const float4 *>(coef) + ((int64_t)plane * cv + c4) * 2;
+  const float4 c01 = cp[0], c23 = cp[1];
+  const float4 *xp = reinterpret_cast<const float4 *>(x) + (int64_t)plane * p.in_h * p.in_w * cv + c4;
+  float4 *op = reinterpret_cast<float4 *>(out) + ((int64_t)plane * p.out_h + 2 * i) * p.out_w * cv + c4;
+  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+  const int per = (p.in_w + col_step - 1) / col_step;            // this thread's pixels: [j0, j1)
+  const int j0 = col0 * per, j1 = min(j0 + per, p.in_w);
+  if (j0 >= j1) return;
+  const float4 *row[3];
+  bool vy[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const int iy = i - 1 + r;
+    vy[r] = (unsigned)iy < (unsigned)p.in_h;
+    row[r] = xp + (int64_t)(vy[r] ? iy : 0) * p.in_w * cv;
+  }
+  // column ix of the window's three rows: act(a x + b) inside the image, exact zeros outside (the load itself stays inside)
+  auto raw = [&](int r, int ix) { return row[r][(int64_t)((unsigned)ix < (unsigned)p.in_w ? ix : 0) * cv]; };
+  auto normed = [&](int r, int ix, const float4 v) { return (vy[r] && (unsigned)ix < (unsigned)p.in_w) ? gn_act4<ACT>(v, c01, c23) : zero; };
+  float4 in[3][3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    in[r][1] = normed(r, j0 - 1, raw(r, j0 - 1));
+    in[r][2] = normed(r, j0, raw(r, j0));
+  }
+  for (int j = j0; j < j1; ++j) {
+    float4 nxt[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      in[r][0] = in[r][1]; in[r][1] = in[r][2];
+      nxt[r] = raw(r, j + 1);
+    }
+#pragma unroll
+    for (int r = 0; r < 3; ++r) in[r][2] = normed(r, j + 1, nxt[r]);
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        float4 acc = zero;
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+          for (int v = 0; v < 2; ++v) {
+            const float wt = w[(a + 2 * u) * 4 + (b + 2 * v)];
+            const float4 sv = in[a + u][b + v];
+            acc.x += sv.x * wt; acc.y += sv.y * wt; acc.z += sv.z * wt; acc.w += sv.w * wt;
+          }
+        op[((int64_t)a * p.out_w + 2 * j + b) * cv] = acc;
+      }
+  }
+}
+
 // ---------------------------------------------------------------- anything else
 __global__ void __launch_bounds__(256)
 upfirdn2d_generic(const float *__restrict__ x, const float *__restrict__ k, float *__restrict__ out, UfdParams p,
@@ -882,4 +1037,68 @@ IDIFF_API const char *idiff_upfirdn2d_route(const void *x, const void *out, int 
   UfdPlan c;
   if (ufd_choose(x, out, major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1, p, c)) return nullptr;
   return kUfdRouteNames[c.route];
+}
+
+// ---------------------------------------------------------------- fp32, NHWC, a GroupNorm (+ SiLU) in the loader
+namespace {
+// The plan of idiff_upfirdn2d_gn_f32: the plain launcher's own choice, served where it is one of the two NHWC kernels that have a
+// normalising form.  Returns 0 with c.route == UFD_NONE for an empty batch.
+int ufd_gn_choose(const void *x, const void *coef, int act, const void *out, int major, int in_h, int in_w, int minor, int kh, int kw,
+                  int up_x, int up_y, int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1, UfdParams &p, UfdPlan &c) {
+  using namespace idiff;
+  if (act != IDIFF_ACT_NONE && act != IDIFF_ACT_SILU) return fail("upfirdn2d_gn: activation code %d (none or SiLU are served)", act);
+  if (major != 0 && !coef) return fail("upfirdn2d_gn: null coefficients");
+  if ((uintptr_t)coef % 16) return fail("upfirdn2d_gn: coefficients not 16-byte aligned");
+  if (int rc = ufd_choose(x, out, major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1, p, c))
+    return rc;
+  const bool down2 = c.route == UFD_NHWC_ROWS0 && down_x == 2 && down_y == 2 && kh == 4 && kw == 4;
+  if (c.route != UFD_NONE && c.route != UFD_NHWC_UP2_BLOCK && !down2)
+    return fail("upfirdn2d_gn: served where upfirdn2d takes nhwc_up2_block (up 2, 4x4 taps) or nhwc_rows<0> with down 2 and 4x4 taps "
+                "(minor %% 4 == 0), this geometry takes %s with down %dx%d and %dx%d taps", kUfdRouteNames[c.route], down_x, down_y, kh, kw);
+  if (down2) c.grid = dim3(major * ((p.out_h + 1) / 2));          // a workgroup per (plane, pair of output rows)
+  return 0;
+}
+}  // namespace
+
+IDIFF_API int idiff_upfirdn2d_gn_f32(const float *x, const float *k, const float *coef, int act, float *out, int major, int in_h,
+                                     int in_w, int minor, int kh, int kw, int up_x, int up_y, int down_x, int down_y, int pad_x0,
+                                     int pad_x1, int pad_y0, int pad_y1, void *stream) {
+  using namespace idiff;
+  if (major != 0 && !k) return fail("upfirdn2d_gn: null pointer");
+  UfdParams p;
+  UfdPlan c;
+  if (int rc = ufd_gn_choose(x, coef, act, out, major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0,
+                             pad_y1, p, c))
+    return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 blk(256);
+  const bool silu = act == IDIFF_ACT_SILU;
+  switch (c.route) {
+    case UFD_NONE: return 0;
+    case UFD_NHWC_UP2_BLOCK:
+      if (silu) hipLaunchKernelGGL(upfirdn2d_nhwc_up2_block_gn<IDIFF_ACT_SILU>, c.grid, blk, 0, st, x, k, coef, out, p, c.cv, c.col_step);
+      else hipLaunchKernelGGL(upfirdn2d_nhwc_up2_block_gn<IDIFF_ACT_NONE>, c.grid, blk, 0, st, x, k, coef, out, p, c.cv, c.col_step);
+      return launch_status("upfirdn2d_nhwc_up2_block_gn");
+    case UFD_NHWC_ROWS0:
+      if (silu) hipLaunchKernelGGL(upfirdn2d_nhwc_down2_block_gn<IDIFF_ACT_SILU>, c.grid, blk, 0, st, x, k, coef, out, p, c.cv, c.col_step);
+      else hipLaunchKernelGGL(upfirdn2d_nhwc_down2_block_gn<IDIFF_ACT_NONE>, c.grid, blk, 0, st, x, k, coef, out, p, c.cv, c.col_step);
+      return launch_status("upfirdn2d_nhwc_down2_block_gn");
+    default: break;
+  }
+  return fail("upfirdn2d_gn: no route");
+}
+
+IDIFF_API int idiff_upfirdn2d_gn_ok(const void *x, const void *coef, int act, const void *out, int major, int in_h, int in_w, int minor,
+                                    int kh, int kw, int up_x, int up_y, int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0,
+                                    int pad_y1) {
+  if (idiff::option(idiff::OPT_NO_FUSED_GN_FIR)) return 0;
+  UfdParams p;
+  UfdPlan c;
+  if (ufd_gn_choose(x, coef, act, out, major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1, p, c))
+    return 0;
+  // routed where it was measured faster than the pass + the plain kernel by more than the spread (profiles/gn_readers_shape_ab.txt, 2240
+  // images): up from 8 x 8 maps on (a 4 x 4 map leaves a thread one pixel: nothing to slide over, and the coefficient launch costs more
+  // than the pass saves), down from 16 x 16 on (at 8 x 8 half of a workgroup's threads have no output block)
+  const int64_t pixels = (int64_t)in_h * in_w;
+  return c.route == UFD_NHWC_UP2_BLOCK ? pixels >= 64 : c.route == UFD_NHWC_ROWS0 ? pixels >= 256 : 0;
 }

@@ -22,6 +22,7 @@ module list in the same order, so Lightning checkpoints load after stripping ``s
 Switch combinations that raise inside the reference itself are refused at construction (see oracle/models.py).
 """
 import math
+import os
 
 import numpy as np
 import torch
@@ -148,6 +149,10 @@ class Combine(nn.Module):
         self.Conv_0 = _conv(dim1, dim2, 1)
         self.method = method
 
+
+# an up block computes its 1x1 shortcut before the upsampling (NCSNpp._resblock); False: as the reference orders them.  Read at every
+# call; initialised like the library's switches, from the environment at import: IDIFF_NO_EARLY_SHORTCUT=1 turns it off (A/B runs)
+SHORTCUT_BEFORE_UPSAMPLE = os.environ.get("IDIFF_NO_EARLY_SHORTCUT", "0") in ("", "0")
 
 _ACT_NAMES = {"swish": "silu", "elu": "elu", "relu": "relu", "lrelu": "lrelu"}
 
@@ -306,7 +311,10 @@ class NCSNpp(NhwcExecutor):
         return pk["nin"][key]
 
     # -------------------------------------------------------------------------------------------- primitive steps
-    def _fir(self, x, pk, mode):
+    def _fir(self, x, pk, mode, gn=None, act=None):
+        """FIR resampling of ``x``; with ``gn``: of act(GroupNorm(x)), the norm applied by the resampling kernel to what it loads
+        (_lib.upfirdn2d_gn: one launch plus the coefficient launch instead of the pass and the FIR), or None where that form is not
+        served: ``x`` without column sums, a geometry off the two NHWC kernels, IDIFF_NO_FUSED_GN_FIR."""
         B = x.buf.shape[0]
         n = pk["fir_len"]
         if mode == "up":      # upsample_2d :195-224
@@ -320,6 +328,19 @@ class NCSNpp(NhwcExecutor):
             k, up, down, p0, p1 = pk["fir_down"], 1, 1, (p + 1) // 2, p // 2
         OH = _lib.upfirdn2d_out_size(x.H, up, down, p0, p1, n)
         OW = _lib.upfirdn2d_out_size(x.W, up, down, p0, p1, n)
+        if gn is not None:
+            if x.stats is None or x.pending is not None or _lib.ACT[act] not in (0, 1) or x.C % gn.num_groups or x.C % 4:
+                return None
+            coef = torch.empty(B * x.C * 2, device=x.buf.device, dtype=torch.float32)
+            y = self._new(B, OH, OW, x.C, x.buf)
+            if not _lib.upfirdn2d_gn_ok(x.buf, coef, act, y.buf, B, x.H, x.W, x.C, n, n, up, up, down, down, p0, p1, p0, p1):
+                return None
+            _lib.groupnorm_reader_coef(x.stats[0], x.stats[1], x.C, B, x.H * x.W, gn.num_groups, gn.eps, gn.weight.detach(),
+                                       gn.bias.detach(), coef)
+            _lib.upfirdn2d_gn(x.buf, k, coef, act, y.buf, B, x.H, x.W, x.C, up, up, down, down, p0, p1, p0, p1)
+            # what _gn_act sets on the norm's output, through the resampler's gain as below
+            y.norm = (gn, (x.C // gn.num_groups) * x.H * x.W, pk["fir_gain"][mode], False)
+            return y
         y = self._new(B, OH, OW, x.C, x.buf)
         _lib.upfirdn2d_raw(x.buf, k, y.buf, B, x.H, x.W, x.C, up, up, down, down, p0, p1, p0, p1)
         if x.norm is not None:
@@ -333,14 +354,23 @@ class NCSNpp(NhwcExecutor):
         rs = _INV_SQRT2 if self.skip_rescale else 1.0
         c_in = x.C + (x2.C if x2 is not None else 0)
         assert c_in == mod.in_ch, (c_in, mod.in_ch)
-        # (an up / down block's norm is read by the FIR as well: it stays a pass)
-        h = self._gn_act(x, mod.GroupNorm_0, self.act_name, x2, conv_cout=None if (mod.up or mod.down) else mod.out_ch)
+        early_shortcut = False
         if mod.up or mod.down:
             assert x2 is None
-            if self.fir:
-                h, x = self._fir(h, pk, "up" if mod.up else "down"), self._fir(x, pk, "up" if mod.up else "down")
-            else:
-                h, x = self._box(h, mod.up), self._box(x, mod.up)
+            # an up / down block's norm is read by the resampler alone: the FIR applies it to what it loads where that form is served
+            h = self._fir(x, pk, "up" if mod.up else "down", gn=mod.GroupNorm_0, act=self.act_name) if self.fir else None
+            if h is None:
+                h = self._gn_act(x, mod.GroupNorm_0, self.act_name)
+                h = self._fir(h, pk, "up" if mod.up else "down") if self.fir else self._box(h, mod.up)
+            resample = (lambda t: self._fir(t, pk, "up" if mod.up else "down")) if self.fir else (lambda t: self._box(t, mod.up))
+            # an up block's 1x1 shortcut runs BEFORE the upsampling (a 1x1 over the channels and a resampler over the pixels commute
+            # exactly): the GEMM on a quarter of the rows, the resampler on the shortcut's channel count.  Its bias goes behind both, into
+            # Conv_1's.  A down block resamples first already: the narrower side.
+            early_shortcut = SHORTCUT_BEFORE_UPSAMPLE and mod.up and (hasattr(mod, "Conv_2") or hasattr(mod, "NIN_0"))
+            if not early_shortcut:
+                x = resample(x)
+        else:
+            h = self._gn_act(x, mod.GroupNorm_0, self.act_name, x2, conv_cout=mod.out_ch)
         w0, b0 = self._conv_w(pk, (idx, 0), mod.Conv_0)
         off = pk["dense_off"][idx]
         h = self._conv_gn_act(h, w0, b0, mod.GroupNorm_1, self.act_name, rowbias=temb_all[:, off:off + mod.out_ch], normed=True,
@@ -355,7 +385,9 @@ class NCSNpp(NhwcExecutor):
                 ws = [w.view(w.shape[0], -1) for w in ws] if split is not None else ws.view(ws.shape[0], -1)
             else:
                 ws, bs = self._nin_w(pk, (idx, "nin"), mod.NIN_0, split)
-            if x2 is None:
+            if early_shortcut:
+                sc = resample(self._pointwise(x, ws, None))
+            elif x2 is None:
                 sc = self._pointwise(x, ws, bs)
             elif fused:
                 sc = self._new(x.buf.shape[0], x.H, x.W, ws.shape[0], x.buf)
@@ -368,6 +400,10 @@ class NCSNpp(NhwcExecutor):
             assert x2 is None
             sc = x
         w1, b1 = self._conv_w(pk, (idx, 1), mod.Conv_1)
+        if early_shortcut:
+            if (idx, "1+shortcut") not in pk["conv"]:
+                pk["conv"][(idx, "1+shortcut")] = (w1, (b1 + bs).contiguous())
+            b1 = pk["conv"][(idx, "1+shortcut")][1]
         return self._conv(h, w1, b1, residual=sc.buf, out_scale=rs, stats=True, normed=True)   # next: a GroupNorm_0 / skip
 
     def _attn(self, idx, x, pk):

@@ -54,7 +54,8 @@ const char *idiff_variant_flags(void);
  * IDIFF_NO_FUSED_GN (idiff_conv2d_wino1d_gn_ok answers 0: the GroupNorm behind a row-wise convolution stays a launch of its own), IDIFF_NO_FUSED_GN_LOAD
  * (idiff_conv2d_wino1d_normload_ok answers 0: the GroupNorm in front of a row-wise convolution stays a pass of its own),
  * IDIFF_NO_FUSED_GN_LOAD_2SRC (idiff_conv2d_wino1d_normload_2src_ok answers 0: the GroupNorm of cat[x1, x2] in front of a row-wise
- * convolution stays a pass of its own), IDIFF_NO_PAIRS (idiff_gemm_pairs_ok answers 0: the 1x1
+ * convolution stays a pass of its own), IDIFF_NO_FUSED_GN_FIR (idiff_upfirdn2d_gn_ok answers 0: the GroupNorm in front of the FIR
+ * resampling of an up / down block stays a pass of its own), IDIFF_NO_PAIRS (idiff_gemm_pairs_ok answers 0: the 1x1
  * projections behind a GroupNorm stay on idiff_gemm_f32's six-product form), IDIFF_PAIRS_MIN_TILES (tests: the number of 128 x 128
  * tiles from which idiff_gemm_pairs_ok answers 1; default 256).
  * Returns the previous value, -1 for an unknown name.  No reference counterpart. */
@@ -86,6 +87,23 @@ int idiff_upfirdn2d_f32(const float *x, const float *k, float *out, int major, i
  * why).  Launches nothing; no reference counterpart. */
 const char *idiff_upfirdn2d_route(const void *x, const void *out, int major, int in_h, int in_w, int minor, int kh, int kw,
                                   int up_x, int up_y, int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1);
+
+/* idiff_upfirdn2d_f32 on act(a x + b): x is the RAW input of a GroupNorm over [major = images, in_h, in_w, minor = channels], coef
+ * [major, minor, 2] floats (a, b) per (image, channel) from idiff_groupnorm_coef_f32, 16-byte aligned; act: IDIFF_ACT_SILU or
+ * IDIFF_ACT_NONE.  The norm is applied to every sample as it is loaded (one fma, the pass's own SiLU); taps outside the image are exact
+ * zeros, never act(b); the normalised tensor is never written.  Served where idiff_upfirdn2d_f32 takes "nhwc_up2_block" (up 2, 4x4
+ * taps, pads (2, 1)) or "nhwc_rows<0>" with down 2 and 4x4 taps (minor % 4 == 0: the score networks' FIR x2 / :2), by kernels of its
+ * own (a thread slides a 3 x 3 window along its row / forms a 2 x 2 output block, so that a sample's SiLU is evaluated 3 / 2.25 times
+ * and not 9 / 4); every other geometry or activation, and a null or misaligned coef, is refused with an error and nothing launched.
+ *   idiff_upfirdn2d_gn_ok   1 where the launcher serves these arguments AND the form was measured faster than the pass plus the plain
+ *                           kernel (up: maps of 64 pixels and more, down: of 256 and more); 0 otherwise and under
+ *                           IDIFF_NO_FUSED_GN_FIR.  Launches nothing.
+ * No reference counterpart. */
+int idiff_upfirdn2d_gn_f32(const float *x, const float *k, const float *coef, int act, float *out, int major, int in_h, int in_w,
+                           int minor, int kh, int kw, int up_x, int up_y, int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0,
+                           int pad_y1, void *stream);
+int idiff_upfirdn2d_gn_ok(const void *x, const void *coef, int act, const void *out, int major, int in_h, int in_w, int minor, int kh,
+                          int kw, int up_x, int up_y, int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1);
 
 /* Replaces `fused_bias_act(input, bias, refer, act, grad, alpha, scale)` of op/fused_bias_act.cpp:11-17
  * (kernel op/fused_bias_act_kernel.cu:18-49).  out[i] = f(x[i] + b[(i/step_b) % size_b]) * scale with
