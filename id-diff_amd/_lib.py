@@ -163,6 +163,10 @@ _SIGNATURES = {
     "idiff_empirical_score_f32": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i64, c_i, c_p]),
     "idiff_empirical_jacobian_ok": (c_i, [c_i64, c_i]),
     "idiff_empirical_jacobian_f64": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i64, c_i, c_p]),
+    "idiff_empirical_flipd_ok": (c_i, [c_i64, c_i, c_i]),
+    "idiff_empirical_flipd_workspace_doubles": (c_i64, [c_i64, c_i, c_i]),
+    "idiff_empirical_flipd_splits": (c_i, [c_i64, c_i64, c_i]),
+    "idiff_empirical_flipd_f64": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i, c_i, c_i, c_p]),
     "idiff_gemm_nn_ok": (c_i, [c_i, c_i, c_i]),
     "idiff_gemm_nn_f32": (c_i, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i, c_i, c_i, c_p]),
     "idiff_gemm_tn_ok": (c_i, [c_i, c_i, c_i]),
@@ -1681,6 +1685,79 @@ def empirical_jacobian(x, X, sigma, C=None, mean=None, ess=None):
     _check(lib().idiff_empirical_jacobian_f64(x.data_ptr(), X.data_ptr(), sigma.data_ptr(), C.data_ptr(), mean.data_ptr(), ess.data_ptr(),
                                               B, N, D, _stream()), "idiff_empirical_jacobian_f64")
     return C, mean, ess
+
+
+# ------------------------------------------------------------------------------------------- FLIPD of the empirical distribution
+FLIPD_S_MAX = 32              # idiff_empirical_flipd_ok: bandwidths a call
+
+
+def empirical_flipd_ok(N, D, S=1):
+    """True where empirical_flipd serves a cloud of N points in R^D at S bandwidths (idiff_empirical_flipd_ok: host only; any
+    D <= 65536, S <= 32)."""
+    return bool(lib().idiff_empirical_flipd_ok(int(N), int(D), int(S)))
+
+
+def empirical_flipd_splits(P, N, D):
+    """The ranges the cloud is cut into for P queries when the caller names none (idiff_empirical_flipd_splits: host only)."""
+    return int(lib().idiff_empirical_flipd_splits(int(P), int(N), int(D)))
+
+
+def empirical_flipd(x, pack, sigmas, exclude=None, flipd=None, ess=None, splits=None, workspace=None):
+    """``(flipd [P, S] fp64, ess [P, S] fp32)``: flipd[p, j] = sum_i w_i r_i^2 / sigma_j^2 with r_i^2 = |x_i - x_p|^2 and
+    w = softmax_i(-r_i^2 / (2 sigma_j^2)) over the packed cloud, ess = 1 / sum_i w_i^2 -- FLIPD, D + sigma^2 (tr grad s + |s|^2), of the
+    cloud's empirical distribution at every bandwidth from one pass over the distances (idiff_empirical_flipd_f64: two launches, fp64
+    throughout, any D).  x [P, D] and sigmas [S <= 32] fp32 on the device; ``pack`` from ``empirical_pack``.  ``exclude`` [P]: for each
+    query the cloud row left out of its softmax (-1: none), given ON THE HOST (a sequence, numpy array or CPU tensor of integers) so
+    that a value outside [-1, N) is refused here without reading the device back.  ``splits``: the ranges N is cut into across
+    workgroups (default ``empirical_flipd_splits``); equal splits give equal bits.  A query row that is not finite is NaN in its row, a
+    sigma that is not positive and finite in its column, a query with no admissible point everywhere.  A shape the kernel does not
+    serve is a RuntimeError before any launch.  No host sync."""
+    _dev(x, "x"); _dev(sigmas, "sigmas")
+    Y, h, c = _dev(pack["Y"], "pack Y", dtype=torch.float64), _dev(pack["h"], "pack h", dtype=torch.float64), \
+        _dev(pack["c"], "pack c", dtype=torch.float64)
+    N, D = int(pack["N"]), int(pack["D"])
+    if x.ndim != 2 or x.shape[1] != D or sigmas.ndim != 1 or tuple(Y.shape) != (N, (D + 3) // 4 * 4) or h.numel() != N \
+            or c.numel() != D:
+        raise RuntimeError(f"empirical_flipd: x {tuple(x.shape)}, sigmas {tuple(sigmas.shape)}, a cloud of {N} points in R^{D} packed "
+                           f"as Y {tuple(Y.shape)}, h {tuple(h.shape)}, c {tuple(c.shape)}")
+    P, S = x.shape[0], sigmas.numel()
+    if not empirical_flipd_ok(N, D, S):
+        raise RuntimeError(f"empirical_flipd: N = {N}, D = {D}, S = {S} is not served (idiff_empirical_flipd_ok): 1 <= D <= 65536, "
+                           f"1 <= S <= {FLIPD_S_MAX} bandwidths a call, 1 <= N")
+    if exclude is not None:
+        if isinstance(exclude, torch.Tensor) and exclude.is_cuda:
+            raise RuntimeError("empirical_flipd: exclude is checked on the host: pass a sequence, numpy array or CPU tensor")
+        ex = torch.as_tensor(exclude, dtype=torch.int64).reshape(-1)
+        if ex.numel() != P:
+            raise RuntimeError(f"empirical_flipd: exclude holds {ex.numel()} values for {P} queries")
+        if P and (int(ex.min()) < -1 or int(ex.max()) >= N):
+            raise RuntimeError(f"empirical_flipd: exclude out of range: values {int(ex.min())} .. {int(ex.max())} for a cloud of {N} "
+                               "points (-1 excludes nothing)")
+        exclude = ex.to(torch.int32).to(x.device, non_blocking=True)
+    if splits is None:
+        splits = empirical_flipd_splits(P, N, D)
+    splits = int(splits)
+    if not 1 <= splits <= 65535:
+        raise RuntimeError(f"empirical_flipd: splits = {splits}, must be 1 .. 65535")
+    if flipd is None:
+        flipd = torch.empty(P, S, device=x.device, dtype=torch.float64)
+    if ess is None:
+        ess = torch.empty(P, S, device=x.device, dtype=torch.float32)
+    _dev(flipd, "flipd", dtype=torch.float64); _dev(ess, "ess")
+    if tuple(flipd.shape) != (P, S) or tuple(ess.shape) != (P, S):
+        raise RuntimeError(f"empirical_flipd: flipd {tuple(flipd.shape)}, ess {tuple(ess.shape)} for {P} queries and {S} bandwidths")
+    need = int(lib().idiff_empirical_flipd_workspace_doubles(P, S, splits))
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), device=x.device, dtype=torch.float64)
+    _dev(workspace, "workspace", dtype=torch.float64)
+    if workspace.numel() < need:
+        raise RuntimeError(f"empirical_flipd: workspace of {workspace.numel()} doubles, P = {P}, S = {S}, splits = {splits} need {need}")
+    if P == 0:
+        return flipd, ess
+    _check(lib().idiff_empirical_flipd_f64(x.data_ptr(), Y.data_ptr(), h.data_ptr(), c.data_ptr(), sigmas.data_ptr(), _ptr(exclude),
+                                           flipd.data_ptr(), ess.data_ptr(), workspace.data_ptr(), workspace.numel(), P, N, D, S, splits,
+                                           _stream()), "idiff_empirical_flipd_f64")
+    return flipd, ess
 
 
 def sym_eigvals_batched(G):

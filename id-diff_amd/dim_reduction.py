@@ -375,12 +375,13 @@ def _tangent_refused(config, world):
                                   "the exchange of variable-width bases between ranks is not implemented")
 
 
-METHODS = ('sampling', 'jacobian')
+METHODS = ('sampling', 'jacobian', 'flipd')
 
 
 def estimation_method(config, method=None):
-    """'sampling' (the default: the score matrix of a perturbed cloud) or 'jacobian' (jacobian.py: the score Jacobian of an fcn network in
-    closed form); the argument wins over the config key ``dim_estimation.method``.  Anything else is a ValueError."""
+    """'sampling' (the default: the score matrix of a perturbed cloud), 'jacobian' (jacobian.py: the score Jacobian of an fcn network in
+    closed form) or 'flipd' (one score divergence a point: a real-valued reading, no spectrum); the argument wins over the config key
+    ``dim_estimation.method``.  Anything else is a ValueError."""
     if method is None:
         method = config.get('dim_estimation.method', None)
     method = 'sampling' if method is None else str(method)
@@ -395,6 +396,66 @@ def _jacobian_refused(config, world):
         raise NotImplementedError("dim_estimation.method = 'jacobian' needs a single rank and dim_estimation.shard = 'points' (got world "
                                   f"size {world}, shard = {config.get('dim_estimation.shard', 'points')!r}): the Jacobian method has no "
                                   "score rows to shard and its points are not distributed over ranks")
+
+
+FLIPD_MODELS = ('fcn', 'empirical_exact')
+
+
+def _flipd_refused(config, world, return_svd, want_tangent):
+    """method = 'flipd', before the GPU is touched: the models that have a divergence here, one rank, and nothing that needs a spectrum."""
+    name = config.model.get('name')
+    if name not in FLIPD_MODELS:
+        raise NotImplementedError(f"dim_estimation.method = 'flipd' serves model.name in {FLIPD_MODELS}, not {name!r}: the trace of the "
+                                  "score Jacobian needs a JVP or VJP of the network, which the image networks do not have here (and "
+                                  "finite differences are not a substitute)")
+    if name == 'fcn':
+        from . import jacobian
+        try:
+            jacobian.check_config(config)
+        except NotImplementedError as e:
+            raise NotImplementedError(str(e).replace("the Jacobian method", "the FLIPD method")) from None
+    if world > 1 or str(config.get('dim_estimation.shard', 'points')) == 'rows':
+        raise NotImplementedError("dim_estimation.method = 'flipd' needs a single rank and dim_estimation.shard = 'points' (got world "
+                                  f"size {world}, shard = {config.get('dim_estimation.shard', 'points')!r}): it has no score rows to "
+                                  "shard and its points are not distributed over ranks")
+    if return_svd or want_tangent:
+        raise NotImplementedError("dim_estimation.method = 'flipd' has no spectrum and no tangent basis: return_svd, return_tangent and "
+                                  "dim_estimation.save_tangent are not served (return_dims=True returns the rounded readings)")
+
+
+def _points_by_flipd(config, pl_module, points, device, seed):
+    """(flipd float64 numpy [P], what it was read at) of ``points``: an fcn network through ``jacobian.flipd`` at t = sampling_eps (exact
+    unless ``dim_estimation.flipd_probes`` > 0), the empirical score through the kernel at sigma = model.sigma_min with a point that is
+    a row of the cloud left out of its own softmax."""
+    xs = torch.stack([x.reshape(-1) for x, _ in points]).to(device=device, dtype=torch.float32).contiguous()
+    if config.model.get('name') == 'fcn':
+        from . import jacobian
+        n_probes = int(config.get('dim_estimation.flipd_probes', 0) or 0)
+        t = pl_module.sampling_eps
+        f = jacobian.flipd(pl_module, pl_module.sde, xs, t, exact=n_probes <= 0, n_probes=max(n_probes, 1), seed=seed)
+        return f.cpu().numpy(), {'t': float(t)}
+    cloud = pl_module.score_model.cloud.detach()
+    sigma = float(config.model.sigma_min)
+    same = (xs[:, None, :] == cloud[None, :, :]).all(dim=2)              # [P, N]: the driver's points are a handful
+    exclude = torch.where(same.any(dim=1), same.int().argmax(dim=1), torch.full((len(points),), -1, device=device)).cpu()
+    f, _ = _lib.empirical_flipd(xs, pl_module.score_model.packed(), torch.full((1,), sigma, device=device, dtype=torch.float32),
+                                exclude=exclude)
+    return f[:, 0].cpu().numpy(), {'sigma': sigma}
+
+
+def _deliver_flipd(flipd, where, return_dims, rank, save_path, name):
+    """The exit of method 'flipd': the rounded readings (``return_dims``) or ``<name>_flipd.pkl`` on rank 0."""
+    import numpy as np
+    flipd = np.asarray(flipd, dtype=np.float64)
+    if not np.isfinite(flipd).all():
+        raise RuntimeError(f"method 'flipd': {int((~np.isfinite(flipd)).sum())} of {len(flipd)} readings are not finite")
+    dims = np.rint(flipd).astype(np.int64)
+    if return_dims:
+        return dims.tolist()
+    if rank == 0:
+        Path(save_path).mkdir(parents=True, exist_ok=True)
+        with open(os.path.join(save_path, f'{name}_flipd.pkl'), 'wb') as f:
+            pickle.dump({'flipd': flipd, 'dims': dims, **where}, f)
 
 
 def _points_by_jacobian(pl_module, points, device, want_tangent):
@@ -551,7 +612,12 @@ def get_manifold_dimension(config, name=None, return_svd=False, return_dims=Fals
     'jacobian' (``model.name == 'fcn'`` without dropout, one rank, ``shard = 'points'``; NotImplementedError otherwise, before the
     GPU is touched) takes the same points and returns or writes the same layout, but its singular values are those of the score
     Jacobian at mean(t) x in closed form (jacobian.py), which the spectrum of the sampled score matrix estimates up to the factor
-    std(t) sqrt(M); dims and tangent bases are read off them by the same rules."""
+    std(t) sqrt(M); dims and tangent bases are read off them by the same rules.
+    'flipd' (``model.name`` 'fcn' or 'empirical_exact', one rank, ``shard = 'points'``; NotImplementedError otherwise, and for
+    ``return_svd`` / ``return_tangent`` / ``save_tangent``: it has no spectrum) reads D + sigma^2 (tr grad s + |s|^2) at the same points:
+    ``jacobian.flipd`` at t = sampling_eps (exact unless ``dim_estimation.flipd_probes`` > 0) or the empirical kernel at
+    sigma = model.sigma_min.  It writes ``<name>_flipd.pkl`` = ``{'flipd': float64 [P], 'dims': rint of it, 't' or 'sigma'}``;
+    ``return_dims=True`` returns the integers instead."""
     method = estimation_method(config, method)
     log_path, log_name = config.logging.log_path, config.logging.log_name
     save_path = os.path.join(log_path, log_name, 'svd')
@@ -560,6 +626,8 @@ def get_manifold_dimension(config, name=None, return_svd=False, return_dims=Fals
         from . import jacobian
         jacobian.check_config(config)
         _jacobian_refused(config, world)
+    if method == 'flipd':
+        _flipd_refused(config, world, return_svd, return_tangent or bool(config.get('dim_estimation.save_tangent', False)))
     if return_tangent and not return_svd:
         raise ValueError("return_tangent needs return_svd=True (set dim_estimation.save_tangent to have the bases written to disk)")
     save_tangent = not return_svd and bool(config.get('dim_estimation.save_tangent', False))
@@ -585,6 +653,9 @@ def get_manifold_dimension(config, name=None, return_svd=False, return_dims=Fals
     DataModule, pl_module, score_fn, device = setup_model(config)
     num_datapoints = _num_datapoints(config)
     points = collect_points(DataModule.train_dataloader(), num_datapoints)
+    if method == 'flipd':
+        flipd, where = _points_by_flipd(config, pl_module, points, device, seed) if points else ([], {})
+        return _deliver_flipd(flipd, where, return_dims, rank, save_path, name)
     if not points:                       # num_datapoints <= 1: the reference's loop body never runs (:159-164)
         return deliver({'singular_values': []}, [], [])
     if method == 'jacobian':

@@ -15,6 +15,11 @@ centred score matrix estimates |1 - eig(C)| with Monte-Carlo noise; ``jacobian_s
 bandwidths a launch, ``dims_from_jacobian`` reads the dimension off it (tangent eigenvalues are near 1, normal ones near 0), and
 ``scale_curve`` / ``stable_dims`` find the range of bandwidths over which that dimension holds -- the range ``sigma_from_knn`` only
 asks the user to look for.
+
+The third part needs no matrix either: FLIPD, D + sigma^2 (tr grad s + |s|^2) of the same score, is for a cloud the softmax-weighted
+mean of squared distances sum_i w_i |x_i - x|^2 / sigma^2 -- one real number per (point, bandwidth), every bandwidth from one pass over
+the distances, and nothing of width D kept per point, so it serves any D (csrc/empirical_flipd.hip): ``flipd_curve``, ``flipd_dims``.
+The D <= 192 of everything above does not apply to it; the need for N to grow exponentially in the intrinsic dimension does.
 """
 import os
 import pickle
@@ -254,6 +259,71 @@ def jacobian_tangent(X, sigma, points=None, rule='half', dtype=np.float32):
     return out
 
 
+# ------------------------------------------------------------------------------------------- FLIPD: one scalar per (point, bandwidth)
+def flipd_curve(X, sigmas=None, points=None, exclude_self=True):
+    """FLIPD (Kamkari et al. 2024; LIDL of Tempczyk et al. 2022 through the Fokker-Planck equation) of the cloud's empirical
+    distribution, D + sigma^2 (tr grad s + |s|^2) = sum_i w_i |x_i - x|^2 / sigma^2, at every listed point and every bandwidth
+    (default: ``sigma_grid(X)``): {'sigmas' [S], 'flipd' [P, S] fp64, 'ess' [P, S] fp64}.  A REAL-valued local dimension, not a count,
+    from one pass over the distances for the whole grid (``_lib.empirical_flipd``); nothing of width D is kept per point, so any D the
+    kernel admits is served, the image manifolds included.  ``points`` as in ``local_dims``; where they are rows of the cloud (None or
+    integers) and ``exclude_self``, each point is left out of its own softmax.  The reading means something only where the ESS is well
+    above 1 (``flipd_dims``): a sample-based score needs N to grow exponentially in the intrinsic dimension."""
+    Xd = _points(X)
+    sg = sigma_grid(Xd) if sigmas is None else _sigmas(sigmas)
+    xs = _select(Xd, points)
+    exclude = None
+    if exclude_self:
+        if points is None:
+            exclude = np.arange(xs.shape[0])
+        else:
+            pts = np.asarray(points.detach().cpu() if isinstance(points, torch.Tensor) else points)
+            if pts.ndim == 1 and np.issubdtype(pts.dtype, np.integer):
+                exclude = pts.astype(np.int64)
+    pack = _lib.empirical_pack(Xd)
+    sd = torch.from_numpy(sg.astype(np.float32)).to(Xd.device)
+    flipd = torch.empty(xs.shape[0], len(sg), dtype=torch.float64, device=Xd.device)
+    ess = torch.empty(xs.shape[0], len(sg), dtype=torch.float32, device=Xd.device)
+    for lo in range(0, len(sg), _lib.FLIPD_S_MAX):
+        f, e = _lib.empirical_flipd(xs, pack, sd[lo:lo + _lib.FLIPD_S_MAX].contiguous(), exclude=exclude)
+        flipd[:, lo:lo + f.shape[1]], ess[:, lo:lo + f.shape[1]] = f, e
+    return {'sigmas': sg, 'flipd': flipd.cpu().numpy(), 'ess': ess.double().cpu().numpy()}
+
+
+def flipd_dims(curve, ess_min=ESS_MIN):
+    """``(reading [P] float64, dims [P] int64, range [P, 2])`` from a ``flipd_curve`` (host only): ``stable_dims`` on the ROUNDED
+    curve -- of the bandwidths with ess >= ess_min, the longest run on which rint(flipd) stays the same -- gives the integer and the
+    run's (first, last) sigma; the real-valued reading is the mean of flipd over that run.  The same HEURISTIC as ``stable_dims``, no
+    more: -1, nan and (nan, nan) where no bandwidth qualifies or the curve is not finite there."""
+    sg, f, ess = np.asarray(curve['sigmas'], dtype=np.float64).ravel(), np.asarray(curve['flipd'], dtype=np.float64), \
+        np.asarray(curve['ess'], dtype=np.float64)
+    ok = np.isfinite(f)
+    rounded = np.where(ok, np.rint(np.where(ok, f, 0.0)), -1).astype(np.int64)
+    dims, rng = stable_dims(rounded, np.where(ok, ess, np.nan), sg, ess_min=ess_min)
+    reading = np.full(f.shape[0], np.nan)
+    for p in np.flatnonzero(dims >= 0):
+        run = (sg >= rng[p, 0]) & (sg <= rng[p, 1])
+        reading[p] = f[p, run].mean()
+    return reading, dims, rng
+
+
+def run_flipd(X, sigmas=None, points=None, out_dir='empirical'):
+    """``flipd_curve`` of the cloud into ``out_dir/flipd.pkl`` (the curve's dict plus 'reading', 'dims', 'range' of ``flipd_dims``);
+    prints the histogram of the rounded readings beside the median ESS at every bandwidth, then that of the stable ones.  -> the dict."""
+    curve = flipd_curve(X, sigmas=sigmas, points=points)
+    curve['reading'], curve['dims'], curve['range'] = flipd_dims(curve)
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, 'flipd.pkl'), 'wb') as f:
+        pickle.dump(curve, f)
+    print(f"FLIPD of the empirical score on {curve['flipd'].shape[0]} of {X.shape[0]} points, {len(curve['sigmas'])} bandwidths")
+    for s, sigma in enumerate(curve['sigmas']):
+        col = curve['flipd'][:, s]
+        print(f" sigma = {sigma:.4g}: median ESS {np.median(curve['ess'][:, s]):.1f}, median FLIPD {np.median(col):.3f}")
+        _histogram(np.rint(col[np.isfinite(col)]))
+    print(f" stable over the bandwidths with ESS >= {ESS_MIN:g} (-1: none qualifies):")
+    _histogram(curve['dims'])
+    return curve
+
+
 # ------------------------------------------------------------------------------------------- a data set from a config
 def _histogram(dims):
     for v, c in zip(*np.unique(dims, return_counts=True)):
@@ -277,12 +347,15 @@ def run_sweep(X, sigmas=None, points=None, out_dir='empirical', rule='half'):
     return curve
 
 
-def run(config, sigma=None, points=None, out_dir='empirical', sweep=False, sigmas=None):
+def run(config, sigma=None, points=None, out_dir='empirical', sweep=False, sigmas=None, flipd=False):
     """The train split of the config's data set (as the driver splits it) -> the diffusion ID of its first 100 points (or
     ``points``) at bandwidth ``sigma`` (default: ``sigma_from_knn``) into ``out_dir/local_dims.pkl`` = {'dims', 'ess_median',
     'sigma', 'batchsize'}; prints the histogram of the dimensions.  -> dims.  ``sweep=True`` takes the sampling-free path instead
-    (``run_sweep`` over ``sigmas``, default ``sigma_grid``): ``out_dir/scale_curve.pkl``, -> its dict."""
+    (``run_sweep`` over ``sigmas``, default ``sigma_grid``): ``out_dir/scale_curve.pkl``, -> its dict.  ``flipd=True`` takes
+    ``run_flipd`` over ``sigmas``: ``out_dir/flipd.pkl``, -> its dict; it serves any D the kernel admits."""
     X = _points(train_split(config))
+    if flipd:
+        return run_flipd(X, sigmas=sigmas, points=points, out_dir=out_dir)
     if sweep:
         return run_sweep(X, sigmas=sigmas, points=points, out_dir=out_dir)
     sigma = sigma_from_knn(X) if sigma is None else float(sigma)
@@ -307,10 +380,11 @@ def main(argv=None):
     ap.add_argument('--sigma', type=float, default=None)
     ap.add_argument('--out_dir', default='empirical')
     ap.add_argument('--sweep', action='store_true', help="the sampling-free scale curve (scale_curve.pkl) instead of one bandwidth")
-    ap.add_argument('--sigmas', default=None, help="comma-separated bandwidths of --sweep (default: sigma_grid)")
+    ap.add_argument('--flipd', action='store_true', help="FLIPD at every bandwidth (flipd.pkl): a real-valued reading, any D")
+    ap.add_argument('--sigmas', default=None, help="comma-separated bandwidths of --sweep / --flipd (default: sigma_grid)")
     args = ap.parse_args(argv)
     sigmas = None if args.sigmas is None else [float(v) for v in args.sigmas.split(',')]
-    run(read_config(args.config), sigma=args.sigma, out_dir=args.out_dir, sweep=args.sweep, sigmas=sigmas)
+    run(read_config(args.config), sigma=args.sigma, out_dir=args.out_dir, sweep=args.sweep, sigmas=sigmas, flipd=args.flipd)
 
 
 if __name__ == '__main__':

@@ -222,3 +222,50 @@ def local_tangent(model, sde, xs, t=None, dtype=np.float32):
     vectors as ``_lib.sym_lowvecs`` computed them: rounding an exact basis to float32 alone turns it by about 3e-8."""
     J = network_jacobians(model, sde, xs, t)
     return _tangents(J, dim_reduction.checked_spectra(_spectra_from(J)).numpy(), dtype=dtype)[1]
+
+
+def flipd(model, sde, xs, t=None, exact=True, n_probes=1, hutchinson_type='Rademacher', seed=0):
+    """FLIPD [P] fp64 on the device (Kamkari et al. 2024; LIDL of Tempczyk et al. 2022 through the Fokker-Planck equation): the REAL-valued
+    local dimension
+
+        D + std(t)^2 [ tr grad_y s(y, t) + |s(y, t)|^2 ],     y = mean(t) x,   s = -raw / std(t) the score ``get_score_fn`` makes
+
+    of a trained fcn network at every point of xs [P, D]: one forward and one trace, no Jacobian, no Gram, no eigensolve.  With
+    raw the network's output it is D - std tr(d raw / dy) + |raw|^2.  ``exact``: the trace from the forward-mode tangent rows up to the
+    last hidden layer and ``_lib.jvp_trace`` against the output weights, as the exact divergence of the likelihood (``FcnFlow.trace``);
+    otherwise Hutchinson's estimate, the mean over ``n_probes`` probe rows eps of eps^T (d raw / dy) eps through the backward
+    launches of ``FcnFlow.vjp`` (probe k is ``likelihood.probes(hutchinson_type, P, D, seed + k, device)``).  mean(t), std(t) and the
+    time label are evaluated in fp64 and rounded once, as in ``network_jacobians``; the [P]-sized combination is torch fp64 on the device.
+    ``t`` defaults as in ``network_jacobians``.  Same refusals (``_network``); nothing reads the device back."""
+    from . import likelihood
+    net, eps = _network(model)
+    _lib._dev(xs, "xs")
+    D = net.state_size
+    if xs.ndim != 2 or xs.shape[1] != D:
+        raise RuntimeError(f"flipd: xs must be [P, {D}], got {tuple(xs.shape)}")
+    if not exact and int(n_probes) < 1:
+        raise ValueError(f"flipd: n_probes must be at least 1 for Hutchinson's estimate, got {n_probes}")
+    if t is None:
+        t = default_eps(sde) if eps is None else eps
+    P, dev = xs.shape[0], xs.device
+    if P == 0:
+        return torch.empty(0, device=dev, dtype=torch.float64)
+    with torch.no_grad():
+        vec_t = torch.full((P,), float(t), device=dev, dtype=torch.float64)
+        centre, std = sde.marginal_prob(xs.double(), vec_t)
+        probe = None if exact else likelihood.probes(hutchinson_type, P, D, int(seed), dev)
+        flow = likelihood.FcnFlow(net, sde, P, aug=1, exact=exact, eps=probe)
+        flow.x32[:, :D] = centre.float()
+        flow.x32[:, D] = (vec_t * (sde.N - 1)).float()
+        raw = flow.forward()[:, :D].double()
+        if exact:
+            tr = flow.trace()
+        else:
+            tr = torch.zeros(P, device=dev, dtype=torch.float64)
+            for k in range(int(n_probes)):
+                if k:
+                    flow.eps[:, :D] = likelihood.probes(hutchinson_type, P, D, int(seed) + k, dev)
+                u = flow.vjp()
+                tr += (flow.eps[:, :D].double() * u[:, :D].double()).sum(dim=1)
+            tr /= int(n_probes)
+        return D - std * tr + (raw * raw).sum(dim=1)

@@ -25,6 +25,9 @@ GPU only) also writes ``<log_path>/<log_name>/svd/<log_name>_tangent.pkl`` = ``{
 ``--mode manifold_dimension`` with the config key ``dim_estimation.method = 'jacobian'`` (or ``--dim_method jacobian``; not in the
 reference; default 'sampling') writes the same pickle for the same points from the score Jacobian of an ``fcn`` network in closed form
 instead of the score matrix of a perturbed cloud (jacobian.py): no sampling noise, one GPU, ``model.dropout == 0``.
+``dim_estimation.method = 'flipd'`` (``--dim_method flipd``; models ``fcn`` and ``empirical_exact``, one GPU) writes
+``<log_name>_flipd.pkl`` = ``{'flipd': [P] float64, 'dims': rint of it, 't' or 'sigma'}`` instead: FLIPD, the real-valued
+D + sigma^2 (tr grad s + |s|^2), from one score divergence a point and no spectrum.
 """
 import argparse
 import os
@@ -71,9 +74,9 @@ def parse(argv=None):
                     help="(--mode generate) 'ode': draw the samples with the probability-flow ODE sampler instead of the config's")
     ap.add_argument("--exact", action="store_true",
                     help="(--mode likelihood) the exact divergence instead of Hutchinson's estimator")
-    ap.add_argument("--dim_method", default=None, choices=("sampling", "jacobian"),
-                    help="(--mode manifold_dimension) sets the config key dim_estimation.method: 'sampling' (default) or 'jacobian', the "
-                         "score Jacobian of an fcn network in closed form (one GPU)")
+    ap.add_argument("--dim_method", default=None, choices=("sampling", "jacobian", "flipd"),
+                    help="(--mode manifold_dimension) sets the config key dim_estimation.method: 'sampling' (default), 'jacobian', the "
+                         "score Jacobian of an fcn network in closed form, or 'flipd', one score divergence a point (both one GPU)")
     return ap.parse_args(argv)
 
 

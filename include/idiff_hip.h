@@ -783,6 +783,33 @@ int idiff_empirical_jacobian_ok(int64_t N, int D);
 int idiff_empirical_jacobian_f64(const float *x, const float *X, const float *sigma, double *C, double *mean, float *ess,
                                  int B, int64_t N, int D, void *stream);
 
+/* FLIPD of the same empirical distribution (Kamkari et al. 2024; LIDL of Tempczyk et al. 2022 through the Fokker-Planck equation):
+ * D + sigma^2 (tr grad s + |s|^2) of the score s above, which for a cloud is the softmax-weighted mean of squared distances
+ *   flipd[p, j] = sum_i w_i r_i^2 / sigma_j^2,   r_i^2 = |x_i - x_p|^2,   w = softmax_i(-r_i^2 / (2 sigma_j^2)),   ess[p, j] = 1 / sum_i w_i^2
+ * a real-valued local dimension per (query, bandwidth).  Nothing of width D is kept per query, so D only streams: any 1 <= D <= 65536
+ * is served.  The cloud is read as _lib.empirical_pack makes it (Y, h, c as for idiff_empirical_score_f32); q = x - c is formed in
+ * fp64 and r^2 = max(0, |q|^2 + 2 h_i - 2 q . y_i) with the product on v_mfma_f64_16x16x4_f64, q and Y staged through LDS in chunks of
+ * 32 columns (csrc/empirical_flipd.hip).  All S bandwidths share one r^2 tile and one running minimum per query.
+ *
+ * x [P, D] fp32; sigmas [S] fp32, 1 <= S <= 32; exclude [P] int32 or NULL: the cloud row left out of query p's softmax (leave-one-out
+ * when the query is a cloud point), any value outside [0, N) excluding nothing; flipd [P, S] fp64; ess [P, S] fp32.  N is cut into
+ * `splits` contiguous ranges of ceil(N / splits) points across workgroups; their partials (r^2 min, sum e, sum e^2, sum e r^2) go to
+ * `workspace` (idiff_empirical_flipd_workspace_doubles(P, S, splits) = 4 P S splits doubles, `workspace_doubles` what the caller
+ * has) and a second small launch merges them in range order, an empty range as the neutral element.  No atomics: the same inputs and
+ * the same `splits` give the same bits.  idiff_empirical_flipd_splits (host only, launches nothing) is the default: two workgroups a
+ * CU when P / 64 alone gives fewer than 256, never a range below 64 points, 1 when the queries fill the card.
+ *
+ * A query row that is not finite is NaN in its row of both outputs, a sigma that is not positive and finite in its column; a query
+ * with no admissible point (N = 1 and that point excluded) is NaN.  Nonzero (idiff_last_error says why) before any launch for a null
+ * or misaligned pointer, N < 1, D < 1, S < 1, a shape idiff_empirical_flipd_ok denies, splits outside 1 .. 65535 or a workspace that
+ * is too small.  P = 0 is a no-op.  No host synchronisation. */
+int idiff_empirical_flipd_ok(int64_t N, int D, int S);
+int64_t idiff_empirical_flipd_workspace_doubles(int64_t P, int S, int splits);
+int idiff_empirical_flipd_splits(int64_t P, int64_t N, int D);
+int idiff_empirical_flipd_f64(const float *x, const double *Y, const double *h, const double *c, const float *sigmas, const int *exclude,
+                              double *flipd, float *ess, double *workspace, int64_t workspace_doubles, int64_t P, int64_t N, int D, int S,
+                              int splits, void *stream);
+
 /* ------------------------------------------------------------------ training the fcn score network (csrc/fcn_train.hip) */
 
 /* The two contractions the backward pass of a Linear + ELU layer needs beside idiff_gemm_f32, on v_mfma_f32_32x32x2_f32 (a k-ordered
