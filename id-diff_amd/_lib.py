@@ -185,6 +185,8 @@ _SIGNATURES = {
     "idiff_rk_error_f64": (c_i, [c_p, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_i64, c_i64, c_i, c_d, c_d, c_p, c_p, c_p]),
     "idiff_flow_rhs_f64": (c_i, [c_p, c_i64, c_p, c_i64, c_d, c_d, c_p, c_i64, c_i64, c_i, c_i, c_p, c_i64, c_p, c_i64, c_p, c_p]),
     "idiff_jvp_trace_f64": (c_i, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i, c_i, c_i, c_p]),
+    "idiff_stein_rows_ok": (c_i, [c_i64, c_i64]),
+    "idiff_stein_rows_f64": (c_i, [c_p, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -1758,6 +1760,88 @@ def empirical_flipd(x, pack, sigmas, exclude=None, flipd=None, ess=None, splits=
                                            flipd.data_ptr(), ess.data_ptr(), workspace.data_ptr(), workspace.numel(), P, N, D, S, splits,
                                            _stream()), "idiff_empirical_flipd_f64")
     return flipd, ess
+
+
+# ------------------------------------------------------------------------------------------- Stein divergence from sampled score rows
+STEIN_P_MAX = 65535           # points idiff_stein_rows_f64 takes per call
+
+
+def stein_rows_ok(M, D):
+    """True where stein_rows serves M rows of width D a point (idiff_stein_rows_ok: host only; 1 <= M < 2^31, 1 <= D <= 2^30)."""
+    return bool(lib().idiff_stein_rows_ok(int(M), int(D)))
+
+
+def column_means(S):
+    """fp64 column means [P, D] of the contiguous S [P, M, D] (idiff_colmean_f64: two-stage, fixed order; the means the spectrum
+    centres with)."""
+    _dev(S, "scores")
+    if S.ndim != 3 or S.shape[0] > 65535 or S.shape[1] < 1 or S.shape[2] < 1:
+        raise RuntimeError(f"column_means: scores must be [P <= 65535, M >= 1, D >= 1], got {tuple(S.shape)}")
+    P, M, D = S.shape
+    mean = torch.empty(P, D, dtype=torch.float64, device=S.device)
+    if P:
+        scratch = torch.empty(P * 32 * D, dtype=torch.float64, device=S.device)
+        _check(lib().idiff_colmean_f64(S.data_ptr(), P, M, D, mean.data_ptr(), scratch.data_ptr(), _stream()), "idiff_colmean_f64")
+    return mean
+
+
+def _rows3(t, name, P, M, D):
+    """(row pitch, point stride) in elements of the fp32 [P, M, D] (or [M, D]: one point) device tensor ``t`` whose rows are dense."""
+    _dev(t, name, contiguous=False)
+    if t.ndim == 2:
+        t = t.unsqueeze(0)
+    if tuple(t.shape) != (P, M, D) or (D > 1 and t.stride(2) != 1) or (M > 1 and t.stride(1) < D) or \
+            (P > 1 and t.stride(0) < (M - 1) * t.stride(1) + D):
+        raise RuntimeError(f"stein_rows: {name} must be [{P}, {M}, {D}] with dense rows that do not overlap, got shape {tuple(t.shape)} "
+                           f"strides {tuple(t.stride())}")
+    return (t.stride(1) if M > 1 else D), (t.stride(0) if P > 1 else M * D)
+
+
+def stein_rows(S, mean, seeds=None, Z=None, row0=0, rows_out=None, sums_out=None):
+    """``(rows [P, M, 2], sums [P, 5])`` fp64 of the score rows S [P, M, D] (or [M, D]: one point) fp32, rows dense and possibly
+    pitched: per row a' = z . (s - mean) and q = |z|^2, per point the sums of a', a'^2, q, q^2, a' q (idiff_stein_rows_f64: one pass over S,
+    fp64 throughout, fixed order, no atomics).  ``mean`` [P, D] fp64, the column means (``column_means``).  Noise: ``Z``, shaped as S,
+    or (D % 4 == 0) ``seeds``, one integer a point: row i is row ``row0 + i`` of the in-kernel Philox stream ``perturb_randn`` drew
+    from that seed -- the same bits, never materialised.  A point with a non-finite value in S, Z or its mean has NaN there and in
+    its sums, and no other point has.  A shape the kernel does not serve is a RuntimeError before any launch.  No host sync beyond
+    the copy of the seeds."""
+    if S.ndim not in (2, 3):
+        raise RuntimeError(f"stein_rows: scores must be [M, D] or [P, M, D], got {tuple(S.shape)}")
+    P, M, D = (1,) + tuple(S.shape) if S.ndim == 2 else tuple(S.shape)
+    if not stein_rows_ok(M, D) or P > STEIN_P_MAX:
+        raise RuntimeError(f"stein_rows: P = {P}, M = {M}, D = {D} is not served (idiff_stein_rows_ok; at most {STEIN_P_MAX} points a call)")
+    lds, stride_s = _rows3(S, "scores", P, M, D)
+    _dev(mean, "mean", dtype=torch.float64)
+    if mean.numel() != P * D:
+        raise RuntimeError(f"stein_rows: mean holds {mean.numel()} values for {P} points of width {D}")
+    ldz = stride_z = 0
+    if Z is not None:
+        ldz, stride_z = _rows3(Z, "Z", P, M, D)
+    elif seeds is None:
+        raise RuntimeError("stein_rows: pass Z or seeds")
+    elif D % 4:
+        raise RuntimeError(f"stein_rows: D = {D} is no multiple of 4: the in-kernel Philox stream draws 4-column groups, pass Z")
+    else:
+        seeds = [int(s) & 0xFFFFFFFFFFFFFFFF for s in ([seeds] if isinstance(seeds, int) else seeds)]
+        if len(seeds) != P:
+            raise RuntimeError(f"stein_rows: {len(seeds)} seeds for {P} points")
+        # (uint64 bit patterns through int64: torch has no unsigned 64-bit arithmetic, the kernel reads the bits)
+        seeds = torch.tensor([s - (1 << 64) if s >> 63 else s for s in seeds], dtype=torch.int64).to(S.device)
+    if int(row0) < 0:
+        raise RuntimeError(f"stein_rows: row0 = {row0}")
+    if rows_out is None:
+        rows_out = torch.empty(P, M, 2, device=S.device, dtype=torch.float64)
+    if sums_out is None:
+        sums_out = torch.empty(P, 5, device=S.device, dtype=torch.float64)
+    _dev(rows_out, "rows_out", dtype=torch.float64); _dev(sums_out, "sums_out", dtype=torch.float64)
+    if rows_out.numel() != P * M * 2 or sums_out.numel() != P * 5:
+        raise RuntimeError(f"stein_rows: rows_out {tuple(rows_out.shape)}, sums_out {tuple(sums_out.shape)} for {P} points of {M} rows")
+    if P == 0:
+        return rows_out, sums_out
+    _check(lib().idiff_stein_rows_f64(S.data_ptr(), lds, stride_s, mean.data_ptr(), _ptr(Z), ldz, stride_z,
+                                      0 if Z is not None else seeds.data_ptr(), int(row0), rows_out.data_ptr(), sums_out.data_ptr(),
+                                      P, M, D, _stream()), "idiff_stein_rows_f64")
+    return rows_out, sums_out
 
 
 def sym_eigvals_batched(G):

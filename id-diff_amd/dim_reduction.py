@@ -506,11 +506,24 @@ def _group_scores(builder, points, ids, batched, point_seed):
             _safe_rebuild(builder, x, batchsize, seed=point_seed(ids[0])))
 
 
-def _points_with_tangent(builder, points, batched, groups, point_seed):
-    """The loop of ``get_manifold_dimension(return_tangent=True)``: every launch group is taken to completion -- score matrix,
-    spectrum, ID on the host, ``_lib.tangent_basis(S, d)``, S released -- on ONE stream: the width of the basis is known only
+def _group_stein_sums(builder, points, ids, S, point_seed):
+    """[P, 6] fp64 on the device for the launch group ``ids`` whose score matrices are S [P, M, D]: the five sums of ``_lib.stein_rows``
+    and |mean score|^2, from the noise ``build`` / ``build_many`` perturbed with -- the in-kernel Philox stream of ``point_seed(p)``,
+    regenerated and never stored, or for D % 4 != 0 the seeded matrix of ``_seeded_noise``."""
+    from . import stein
+    P, M, D = S.shape
+    seeds = [point_seed(p) for p in ids]
+    Z = torch.stack([builder._seeded_noise(M, D, seed) for seed in seeds]) if D % 4 else None
+    sums, norm2 = stein.sums_of(S.contiguous(), seeds=None if D % 4 else seeds, Z=Z)
+    return torch.cat([sums, norm2[:, None]], dim=1)
+
+
+def _points_with_tangent(builder, points, batched, groups, point_seed, want_tangent=True, stein_sums=None):
+    """The loop of ``get_manifold_dimension(return_tangent=True)`` and of ``return_flipd=True``: every launch group is taken to
+    completion -- score matrix, (``stein_sums``, a list: the group's ``_group_stein_sums`` appended to it) spectrum, ID on the host,
+    (``want_tangent``) ``_lib.tangent_basis(S, d)``, S released -- on ONE stream: the width of the basis is known only
     once the spectrum has reached the host, so nothing of the next point is queued under it.  Score matrices and spectra come
-    from the same launches as without the flag.  -> (spectra [P, D] on the device, dims, tangent)."""
+    from the same launches as without the flags.  -> (spectra [P, D] on the device, dims, tangent)."""
     import warnings
     pipe = SpectrumPipeline(builder.device, overlap=False)
     spectra, dims, tangent, capped = [], [], [], 0
@@ -520,12 +533,16 @@ def _points_with_tangent(builder, points, batched, groups, point_seed):
         if rebuild is not None and not bool(torch.isfinite(S).all()):
             warn_non_finite_point()
             S = rebuild()
+        if stein_sums is not None:                   # of the matrix the spectrum is taken of: a rebuilt point is read from the rebuilt one
+            stein_sums.append(_group_stein_sums(builder, points, ids, S if batched else S[None], point_seed))
         pipe.submit(S)
         svs = pipe.results()[0] if batched else torch.stack(pipe.results())
         for S_p, sv, p in zip(S if batched else [S], checked_spectra(svs), ids):
             x, b = points[p]
             d, k = tangent_width(sv[:_sv_count(x.shape, b)].tolist(), x.numel())
             dims.append(d)
+            if not want_tangent:
+                continue
             capped += d > _lib.TANGENT_MAX
             if k is None:
                 tangent.append(None)
@@ -540,7 +557,41 @@ def _points_with_tangent(builder, points, batched, groups, point_seed):
     if capped:
         warnings.warn(f"id-diff_amd: {capped} point(s) have an intrinsic dimension above {_lib.TANGENT_MAX}, the widest tangent "
                       "basis that is computed: their entry of `tangent` is None")
-    return torch.stack(spectra), dims, tangent
+    return torch.stack(spectra), dims, (tangent if want_tangent else None)
+
+
+def _sampled_flipd_refused(config, world, method):
+    """return_flipd / dim_estimation.save_flipd, before the GPU is touched: the reading is taken of the rows of the sampled path, every
+    point to completion on one rank."""
+    if method != 'sampling':
+        raise NotImplementedError(f"return_flipd / dim_estimation.save_flipd reads the score rows of method 'sampling', and "
+                                  f"dim_estimation.method = {method!r} has none (method 'flipd' is itself a FLIPD reading)")
+    if world > 1 or str(config.get('dim_estimation.shard', 'points')) == 'rows':
+        raise NotImplementedError("return_flipd / dim_estimation.save_flipd needs a single rank and dim_estimation.shard = 'points' (got "
+                                  f"world size {world}, shard = {config.get('dim_estimation.shard', 'points')!r}): the exchange of the "
+                                  "readings between ranks and the reduction of a point's row sums over ranks are not implemented")
+
+
+def _sampled_flipd_readings(stein_sums, spectra, points, sde, t):
+    """The dict ``return_flipd`` delivers, float64 arrays [P]: the readings of ``stein.reading_from_sums`` for every point from ONE
+    read-back of the [P, 6] sums and from the points' spectra on the host (their squared singular values sum to the centred trace of
+    the finite-M correction), 'dims' (rint of 'flipd') and where they were read ('t', 'sigma' = std(t))."""
+    import numpy as np
+    from . import stein
+    host = torch.cat(stein_sums).cpu().numpy() if stein_sums else np.zeros((0, 6))
+    sigma = stein.level_sigma(sde, t)
+    out = {k: np.empty(len(points), dtype=np.float64) for k in stein.KEYS}
+    for p, (x, b) in enumerate(points):              # (M and D are per point: loader batches may differ)
+        one = stein.reading_from_sums(host[p, :5], batching(tuple(x.shape), b)[2], x.numel(), sigma, host[p, 5],
+                                      centred_trace=stein.trace_of(spectra[p].numpy()))
+        for k in stein.KEYS:
+            out[k][p] = one[k][0]
+    if not np.isfinite(out['flipd']).all():
+        raise RuntimeError(f"return_flipd: {int((~np.isfinite(out['flipd'])).sum())} of {len(points)} readings are not finite")
+    out['dims'] = np.rint(out['flipd'])
+    out['t'] = np.full(len(points), float(t), dtype=np.float64)
+    out['sigma'] = np.full(len(points), sigma, dtype=np.float64)
+    return out
 
 
 def build_many(builder, xs, batchsize, seeds):
@@ -590,7 +641,8 @@ def collect_points(loader, num_datapoints):
     return pts
 
 
-def get_manifold_dimension(config, name=None, return_svd=False, return_dims=False, return_tangent=False, method=None):
+def get_manifold_dimension(config, name=None, return_svd=False, return_dims=False, return_tangent=False, method=None,
+                           return_flipd=False):
     """Drop-in for dim_reduction.py:116-215.  ``return_dims=True`` (not in the reference; needs ``return_svd``) also
     returns the integer ID of every point, computed by the reference's rule on the rank that owns the point and gathered
     as int32 in the same collective as the spectra.
@@ -617,7 +669,16 @@ def get_manifold_dimension(config, name=None, return_svd=False, return_dims=Fals
     ``return_svd`` / ``return_tangent`` / ``save_tangent``: it has no spectrum) reads D + sigma^2 (tr grad s + |s|^2) at the same points:
     ``jacobian.flipd`` at t = sampling_eps (exact unless ``dim_estimation.flipd_probes`` > 0) or the empirical kernel at
     sigma = model.sigma_min.  It writes ``<name>_flipd.pkl`` = ``{'flipd': float64 [P], 'dims': rint of it, 't' or 'sigma'}``;
-    ``return_dims=True`` returns the integers instead."""
+    ``return_dims=True`` returns the integers instead.
+
+    ``return_flipd=True`` (with ``return_svd``; method 'sampling', one rank, ``shard = 'points'``: NotImplementedError otherwise, before
+    the GPU is touched) serves EVERY model: FLIPD of the score smoothed over the sampling ball, read off the score rows the spectrum
+    is taken of by Stein's identity (stein.py; ``_lib.stein_rows``) at zero extra network evaluations.  Every point is taken to
+    completion on one stream, as with ``return_tangent``; a point rebuilt on the safe route is read from the rebuilt matrix.  It
+    appends, after whatever ``return_dims`` / ``return_tangent`` append, one dict of float64 arrays [P]: ``{'flipd', 'stderr', 'plain',
+    'beta', 'dims' (rint of flipd), 't', 'sigma'}``.  Singular values, dims and tangent bases are those of a call without the flag, bit
+    for bit.  Without ``return_svd`` the config key ``dim_estimation.save_flipd`` (default False) selects the mode and writes that
+    dict to ``<name>_flipd_sampled.pkl`` beside the unchanged ``<name>.pkl``."""
     method = estimation_method(config, method)
     log_path, log_name = config.logging.log_path, config.logging.log_name
     save_path = os.path.join(log_path, log_name, 'svd')
@@ -633,13 +694,19 @@ def get_manifold_dimension(config, name=None, return_svd=False, return_dims=Fals
     save_tangent = not return_svd and bool(config.get('dim_estimation.save_tangent', False))
     if return_tangent or save_tangent:
         _tangent_refused(config, world)
+    if return_flipd and not return_svd:
+        raise ValueError("return_flipd needs return_svd=True (set dim_estimation.save_flipd to have the readings written to disk)")
+    save_flipd = not return_svd and bool(config.get('dim_estimation.save_flipd', False))
+    if return_flipd or save_flipd:
+        _sampled_flipd_refused(config, world, method)
     if rank == 0 and not return_svd:
         Path(save_path).mkdir(parents=True, exist_ok=True)
 
-    def deliver(info, dims=None, tangent=None):
+    def deliver(info, dims=None, tangent=None, flipd=None):
         """The one exit of every mode: what the flags ask for (``dims=None``: a mode that serves no IDs), or the pickles on rank 0."""
         if return_svd:
-            out = (info,) + ((dims,) if return_dims and dims is not None else ()) + ((tangent,) if return_tangent else ())
+            out = (info,) + ((dims,) if return_dims and dims is not None else ()) + ((tangent,) if return_tangent else ()) + \
+                ((flipd,) if return_flipd else ())
             return out if len(out) > 1 else info
         if rank == 0:
             with open(os.path.join(save_path, f'{name}.pkl'), 'wb') as f:
@@ -647,6 +714,9 @@ def get_manifold_dimension(config, name=None, return_svd=False, return_dims=Fals
             if save_tangent:
                 with open(os.path.join(save_path, f'{name}_tangent.pkl'), 'wb') as f:
                     pickle.dump({'tangent': tangent, 'dims': dims}, f)
+            if save_flipd:
+                with open(os.path.join(save_path, f'{name}_flipd_sampled.pkl'), 'wb') as f:
+                    pickle.dump(flipd, f)
 
     seed = int(config.get('seed', 42))
     torch.manual_seed(seed)  # same data split / loader order on every rank
@@ -657,7 +727,8 @@ def get_manifold_dimension(config, name=None, return_svd=False, return_dims=Fals
         flipd, where = _points_by_flipd(config, pl_module, points, device, seed) if points else ([], {})
         return _deliver_flipd(flipd, where, return_dims, rank, save_path, name)
     if not points:                       # num_datapoints <= 1: the reference's loop body never runs (:159-164)
-        return deliver({'singular_values': []}, [], [])
+        return deliver({'singular_values': []}, [], [], _sampled_flipd_readings([], [], [], pl_module.sde, pl_module.sampling_eps)
+                       if return_flipd or save_flipd else None)
     if method == 'jacobian':
         return deliver(*_points_by_jacobian(pl_module, points, device, return_tangent or save_tangent))
     builder = ScoreMatrixBuilder(score_fn, pl_module.sde, pl_module.sampling_eps, device,
@@ -679,9 +750,14 @@ def get_manifold_dimension(config, name=None, return_svd=False, return_dims=Fals
     mine = parallel.my_points(len(points), rank, world)
     batched, groups = _launch_groups(config, points, mine)
     keep = [_sv_count(x.shape, b) for x, b in points]
+    flipd = None
     with torch.no_grad():
-        if return_tangent or save_tangent:           # one rank: ``mine`` is every point, nothing to exchange
-            spectra, dims, tangent = _points_with_tangent(builder, points, batched, groups, point_seed)
+        if return_tangent or save_tangent or return_flipd or save_flipd:   # one rank: ``mine`` is every point, nothing to exchange
+            stein_sums = [] if return_flipd or save_flipd else None
+            spectra, dims, tangent = _points_with_tangent(builder, points, batched, groups, point_seed,
+                                                          want_tangent=return_tangent or save_tangent, stein_sums=stein_sums)
+            if stein_sums is not None:
+                flipd = _sampled_flipd_readings(stein_sums, checked_spectra(spectra), points, pl_module.sde, pl_module.sampling_eps)
         else:
             pipe = SpectrumPipeline(device, overlap=bool(config.get('dim_estimation.overlap_spectrum', True)))
             for ids in groups:
@@ -693,7 +769,7 @@ def get_manifold_dimension(config, name=None, return_svd=False, return_dims=Fals
             my_dims = [estimate_dim(sv[:keep[p]].tolist()) if keep[p] >= 3 else -1 for sv, p in zip(checked_spectra(local), mine)]
             spectra, dims = parallel.gather_spectra(local, len(points), n_sv, device, dims=my_dims)
             dims, tangent = dims.tolist(), None
-    return deliver({'singular_values': [s[:k].tolist() for s, k in zip(checked_spectra(spectra), keep)]}, dims, tangent)
+    return deliver({'singular_values': [s[:k].tolist() for s, k in zip(checked_spectra(spectra), keep)]}, dims, tangent, flipd)
 
 
 def collect_labelled_points(loader, num_datapoints, label=1):

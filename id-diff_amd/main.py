@@ -28,6 +28,9 @@ instead of the score matrix of a perturbed cloud (jacobian.py): no sampling nois
 ``dim_estimation.method = 'flipd'`` (``--dim_method flipd``; models ``fcn`` and ``empirical_exact``, one GPU) writes
 ``<log_name>_flipd.pkl`` = ``{'flipd': [P] float64, 'dims': rint of it, 't' or 'sigma'}`` instead: FLIPD, the real-valued
 D + sigma^2 (tr grad s + |s|^2), from one score divergence a point and no spectrum.
+``dim_estimation.save_flipd = True`` (``--sampled_flipd``; method 'sampling', EVERY model, one GPU) also writes
+``<log_name>_flipd_sampled.pkl`` = ``{'flipd', 'stderr', 'plain', 'beta', 'dims', 't', 'sigma'}`` (float64 [P]) beside the unchanged
+spectra: FLIPD of the score smoothed over the sampling ball, read off the score rows already evaluated (stein.py).
 """
 import argparse
 import os
@@ -77,6 +80,9 @@ def parse(argv=None):
     ap.add_argument("--dim_method", default=None, choices=("sampling", "jacobian", "flipd"),
                     help="(--mode manifold_dimension) sets the config key dim_estimation.method: 'sampling' (default), 'jacobian', the "
                          "score Jacobian of an fcn network in closed form, or 'flipd', one score divergence a point (both one GPU)")
+    ap.add_argument("--sampled_flipd", action="store_true",
+                    help="(--mode manifold_dimension) sets the config key dim_estimation.save_flipd: beside the spectra, the real-valued "
+                         "FLIPD reading of every point from the score rows already evaluated, for any model (one GPU)")
     return ap.parse_args(argv)
 
 
@@ -131,6 +137,8 @@ def main(argv=None):
         config.model.allow_random_init = True
     if flags.dim_method is not None:
         config['dim_estimation.method'] = flags.dim_method
+    if flags.sampled_flipd:
+        config['dim_estimation.save_flipd'] = True
     if flags.mode == 'train':
         run_train(flags, config)
         return

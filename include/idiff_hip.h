@@ -936,6 +936,29 @@ int idiff_flow_rhs_f64(const float *x32, int64_t ldx, const float *v, int64_t ld
 int idiff_jvp_trace_f64(const float *T, int64_t ldt, int64_t strideT, const float *Wout, int64_t ldw, double *tr, int P, int D, int N,
                         void *stream);
 
+/* ------------------------------------------------------------------ Stein divergence from sampled score rows (csrc/stein.hip)
+ * The score rows s_i = s(y + sigma z_i), z_i ~ N(0, I), that the sampled ID path evaluates hold the divergence of the score smoothed
+ * over the sampling ball: E[z . s(y + sigma z)] = sigma tr grad (s * N(0, sigma^2 I))(y) (Stein's identity), so FLIPD needs no JVP of
+ * the network.  For P points of M rows each:
+ *   rows[p, i] = (a', q),   a' = sum_c z_ic (s_ic - mean_pc),   q = sum_c z_ic^2                      [P, M, 2] fp64
+ *   sums[p]    = (sum a', sum a'^2, sum q, sum q^2, sum a' q) over the M rows                          [P, 5] fp64
+ * S fp32: row i of point p at S + p stride_s + i lds (lds >= D; stride_s >= (M - 1) lds + D when P > 1); mean [P, D] fp64 (the column
+ * means, idiff_colmean_f64).  Noise: Z fp32, addressed as S with ldz / stride_z; or Z NULL and seeds [P] uint64 on the device, D % 4 == 0:
+ * the element (row0 + i, c) of the Philox stream idiff_perturb_randn_f32 draws for that seed in a matrix of width D, the same bits,
+ * never written anywhere.  row0 only indexes that stream: the M rows given are rows row0 .. row0 + M - 1 of the point's noise matrix.
+ *
+ * One wave per row, 16-byte loads where the pointer, pitch and point stride allow, every product an fp64 fma of converted fp32
+ * values, a fixed order that depends on D alone: a row's (a', q) is the same bits whatever P, M, row0 or the source of the same z.
+ * The sums: one workgroup a point, fixed order.  No atomics, no workspace.  A row with a non-finite value in S, Z or the mean is NaN
+ * in both of its values, and so are its point's sums; other points are not touched.
+ *
+ * Nonzero (idiff_last_error starts "stein_rows: ") before any launch for a null or misaligned pointer (S, Z 4 bytes; mean, seeds,
+ * rows, sums 8), neither Z nor seeds, Z NULL with D % 4 != 0, M < 1, D < 1, a shape idiff_stein_rows_ok (host only) denies (M < 2^31,
+ * D <= 2^30), P outside 0 .. 65535, a negative row0 or a pitch below D.  P = 0 is a no-op.  No host synchronisation. */
+int idiff_stein_rows_ok(int64_t M, int64_t D);
+int idiff_stein_rows_f64(const float *S, int64_t lds, int64_t stride_s, const double *mean, const float *Z, int64_t ldz, int64_t stride_z,
+                         const uint64_t *seeds, int64_t row0, double *rows, double *sums, int64_t P, int64_t M, int64_t D, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
