@@ -971,7 +971,9 @@ int r1_run(const float *x, const float *u, float *out, int B, int H, int W, int 
     return fail("conv2d_wino1d: geometry B=%d H=%d W=%d Cin=%d Cout=%d not supported (ask idiff_conv2d_wino1d_ok)", B, H, W, Cin, Cout);
   int64_t res_bytes = 0;
   if (int rc = wino_check_call("conv2d_wino1d", x, u, out, ep, B, H, W, Cout, R1_X_LIMIT, res_bytes)) return rc;
-  if (ep && ep->colstats && idiff_conv2d_wino1d_colstats_split(B, H, W, Cin, Cout) <= 0)
+  // (the loader forms serve a single K step, which the plain kernel and with it the query do not: the column sums are the tail's and do not
+  // depend on Cin, so such a call is asked about as one of two steps)
+  if (ep && ep->colstats && idiff_conv2d_wino1d_colstats_split(B, H, W, nl && Cin < 2 * R1_KC ? 2 * R1_KC : Cin, Cout) <= 0)
     return fail("conv2d_wino1d: colstats are switched off (IDIFF_NO_COLSTATS): ask idiff_conv2d_wino1d_colstats_split");
   if (gn) {
     // nothing is launched unless the tail can finish every (image, group) inside one round of one workgroup and store act(GN(.)) alone

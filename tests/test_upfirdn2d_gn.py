@@ -7,6 +7,7 @@ import torch
 import torch.nn.functional as F
 
 import id_diff_amd
+import normfused_cases
 import normload_cases
 from helpers import fill_from_seed, ncsnpp_config, rel_err
 from id_diff_amd import _lib, sde_lib
@@ -28,6 +29,7 @@ MODES = {"up": (2, 1, 2, 1, 4.0), "down": (1, 2, 1, 1, 1.0)}
 # maps of 4 x 4 (every pixel on the border) and 8 x 8; C = 8: two channel quads, 32 pixels per workgroup row; C = 64: sixteen quads
 CASES = [(hw, c, mode, act) for hw in (4, 8) for c in (8, 64) for mode in ("up", "down") for act in ("silu", None)]
 _cache = {}
+_tol = {}                            # the absolute, reference-derived bound of tests/normfused_cases.py (the end-to-end chain's), per case
 
 
 def _fir_taps(gain):
@@ -56,6 +58,7 @@ def _case(HW, C, mode, act):
     ref = upfirdn2d_ref(n, k.double(), up, up, down, down, p0, p1, p0, p1).permute(0, 2, 3, 1).contiguous()
     OH, OW = ref.shape[1], ref.shape[2]
     assert OH == _lib.upfirdn2d_out_size(H, up, down, p0, p1, 4)
+    _tol[key] = normfused_cases.chain_bound_fir(x, gamma, beta, G, mode, act)[1]
 
     xd = x.permute(0, 2, 3, 1).contiguous().view(B, H * W, C).to(DEV)        # the raw tensor, NHWC
     cs = normload_cases.colsums(xd)
@@ -101,6 +104,8 @@ def test_fir_of_groupnorm_vs_fp64_and_two_launch(HW, C, mode, act):
     # a tap outside the image left at act(b) is an error of order 0.1 on these slices alone
     for what, e in {"row 0": e_fused[:, 0], "last row": e_fused[:, -1], "col 0": e_fused[:, :, 0], "last col": e_fused[:, :, -1]}.items():
         assert float(e.max()) <= FUSED_VS_TWO_LAUNCH * max_two, what
+    # a second view: the absolute, reference-derived bound of tests/normfused_cases.py, element by element
+    assert float((e_fused / _tol[(HW, C, mode, act)]).max()) <= 1.0
 
 
 def test_fir_gn_query_switches_and_refusals():

@@ -6,6 +6,7 @@ import torch
 import torch.nn.functional as F
 
 import id_diff_amd
+import normfused_cases
 from helpers import fill_from_seed, ncsnpp_config, overrides_from_golden, rel_err
 from id_diff_amd import _lib
 from id_diff_amd.models import utils as mutils
@@ -84,6 +85,9 @@ def test_fused_gn_vs_fp64_oracle(B, H, W, Cin, Cout, groups, offset):
     assert rms_fused <= FUSED_VS_TWO_LAUNCH * rms_two
     # and the two-launch path itself is a sane yardstick: fp32 rounding of values of size 1 + offset, far below the activations' scale
     assert max_two < 1e-4 * max(1.0, float(ref.abs().max())) * (1.0 + offset)
+    # a second view: the absolute, reference-derived bound of tests/normfused_cases.py, element by element
+    tol = normfused_cases.tail_bound(x, w, b, temb, gamma, beta, groups)[1]
+    assert float((e_fused / tol).max()) <= 1.0
 
 
 def test_fused_gn_refusals():

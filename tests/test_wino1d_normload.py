@@ -8,6 +8,7 @@ import torch
 import torch.nn.functional as F
 
 import id_diff_amd
+import normfused_cases
 import normload_cases
 from helpers import fill_from_seed, ncsnpp_config, rel_err
 from id_diff_amd import _lib
@@ -26,6 +27,7 @@ B, H, W = 3, 32, 32                  # an odd image count: the row blocks (16 ro
 # Cin = 16: one K step (the loop is never entered), 48: three; Cout = 64 / 128: one and two tiles staging the same input
 CASES = [(cin, cout, act) for cin in (16, 48) for cout in (64, 128) for act in ("silu", None)]
 _cache = {}
+_tol = {}                            # the absolute, reference-derived bound of tests/normfused_cases.py (the end-to-end chain's), per case
 
 
 def _case(Cin, Cout, act):
@@ -45,6 +47,7 @@ def _case(Cin, Cout, act):
     n = F.group_norm(x.double(), G, gamma.double(), beta.double(), EPS)
     n = F.silu(n) if act == "silu" else n
     ref = F.conv2d(n, w.double(), b.double(), padding=1).permute(0, 2, 3, 1).contiguous()
+    _tol[key] = normfused_cases.chain_bound_conv(x, None, gamma, beta, G, w, b, act)[1]
 
     xd = x.permute(0, 2, 3, 1).contiguous().to(DEV)                      # the raw tensor, NHWC
     cs = normload_cases.colsums(xd.view(B, H * W, Cin))
@@ -102,6 +105,8 @@ def test_normload_vs_fp64_and_two_launch(small_batches, Cin, Cout, act):
               "row 16": e_fused[:, 16], "row 31": e_fused[:, 31]}
     for what, e in slices.items():
         assert float(e.max()) <= FUSED_VS_TWO_LAUNCH * max_two, what
+    # a second view: the absolute, reference-derived bound of tests/normfused_cases.py, element by element
+    assert float((e_fused / _tol[(Cin, Cout, act)]).max()) <= 1.0
 
 
 def test_normload_query_switches_and_refusals():

@@ -10,6 +10,7 @@ import torch
 import torch.nn.functional as F
 
 import id_diff_amd
+import normfused_cases
 import normload_cases
 from helpers import fill_from_seed, ncsnpp_config, rel_err
 from normload_cases import colsums as _colsums
@@ -54,6 +55,12 @@ def _inputs(C1, C2, Cout, act):
     out = (x1, x2, w, b, gamma, beta, G, ref)
     _inputs_cache[key] = out
     return out
+
+
+def _tol(C1, C2, Cout, act):
+    """the absolute, reference-derived bound of tests/normfused_cases.py (the end-to-end chain's), [B, H, W, Cout]"""
+    x1, x2, w, b, gamma, beta, G, _ = _inputs(C1, C2, Cout, act)
+    return normfused_cases.chain_bound_conv(x1, x2, gamma, beta, G, w, b, act)[1]
 
 
 def _case(C1, C2, Cout, act):
@@ -134,6 +141,8 @@ def test_normload_2src_vs_fp64_and_two_launch(small_batches, C1, C2, Cout, act):
               "row 16": e_fused[:, 16], "row 31": e_fused[:, 31]}
     for what, e in slices.items():
         assert float(e.max()) <= FUSED_VS_TWO_LAUNCH * max_two, what
+    # a second view: the absolute bound, element by element
+    assert float((e_fused / _tol(C1, C2, Cout, act)).max()) <= 1.0
 
 
 @gpu
