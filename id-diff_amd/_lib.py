@@ -87,10 +87,6 @@ _SIGNATURES = {
     "idiff_conv2d_wino1d_normload_2src_f32": (c_i, [c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_i, ctypes.POINTER(Epilogue), c_p, c_i, c_p]),
     "idiff_groupnorm_coef_f32": (c_i, [c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p]),
     "idiff_conv2d_wino1d_gn_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(Epilogue), c_i, c_p, c_p, c_f, c_i, c_p]),
-    "idiff_conv2d_winograd_split_ok": (c_i, [c_i] * 5),
-    "idiff_winograd_split_weight_floats": (c_i64, [c_i, c_i]),
-    "idiff_winograd_pack_split_f32": (c_i, [c_p, c_p, c_i, c_i, c_p]),
-    "idiff_conv2d_winograd_split_f32": (c_i, [c_p, c_p, c_p] + [c_i] * 5 + [ctypes.POINTER(Epilogue), c_p]),
     "idiff_groupnorm_finalize_f32": (c_i, [c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p]),
     "idiff_groupnorm_nsplit": (c_i, [c_i, c_i, c_i]),
     "idiff_groupnorm_stats_f32": (c_i, [c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p]),
@@ -593,15 +589,14 @@ def conv2d_route(x, wt, out, B, H, W, Cin, Cout, KH, KW, stride, pad, epilogue=N
     return None if name is None else name.decode()
 
 
-# ---- Winograd convolutions.  Five kernel forms, named by the stem of their entry points (idiff_<stem>_weight_floats,
-# idiff_<stem>_pack_f32, idiff_conv2d_<stem>_f32): winograd / winograd_split = F(2x2, 3x3) on the fp32 matrix cores / on three bf16 per
-# operand, winograd43 / winograd43h = F(4x4, 3x3) on fp32 / on fp16 pairs, wino1d = F(4, 3) along the rows on fp16 pairs.
+# ---- Winograd convolutions.  Four kernel forms, named by the stem of their entry points (idiff_<stem>_weight_floats,
+# idiff_<stem>_pack_f32, idiff_conv2d_<stem>_f32): winograd = F(2x2, 3x3) on the fp32 matrix cores, winograd43 / winograd43h = F(4x4, 3x3) on fp32 / on fp16 pairs, wino1d = F(4, 3) along the rows on fp16 pairs.
 def _wino_pack(stem, name, wt, Cin, Cout):
     """wt [Cout, 3, 3, Cin] (the direct kernel's panel) -> the transformed filter bank of idiff_conv2d_<stem>_f32."""
     _dev(wt, "wt")
     if tuple(wt.shape) != (Cout, 3, 3, Cin):
         raise RuntimeError(f"{name}: expected {Cout}x3x3x{Cin} weights, got {tuple(wt.shape)}")
-    entry = "idiff_winograd_pack_split_f32" if stem == "winograd_split" else f"idiff_{stem}_pack_f32"
+    entry = f"idiff_{stem}_pack_f32"
     u = torch.empty(getattr(lib(), f"idiff_{stem}_weight_floats")(Cin, Cout), device=wt.device, dtype=torch.float32)
     _check(getattr(lib(), entry)(wt.data_ptr(), u.data_ptr(), Cin, Cout, _stream()), entry)
     return u
@@ -645,24 +640,18 @@ def conv2d_winograd_ok(B, H, W, Cin, Cout):
     return bool(lib().idiff_conv2d_winograd_ok(B, H, W, Cin, Cout))
 
 
-def conv2d_winograd_split_ok(B, H, W, Cin, Cout):
-    """True when the opt-in split-precision Winograd kernel (IDIFF_WINO_SPLIT) serves this geometry NOW: asked per call, so a
-    switch flipped after a bank was packed, or another (B, H, W) through the same layer, is seen."""
-    return bool(lib().idiff_conv2d_winograd_split_ok(B, H, W, Cin, Cout))
-
-
 def conv2d_winograd_colstats_split(B, H, W, Cin, Cout):
     return lib().idiff_conv2d_winograd_colstats_split(B, H, W, Cin, Cout)
 
 
-def winograd_pack(wt, Cin, Cout, split=False):
-    """The filter bank of idiff_conv2d_winograd_f32, or -- ``split=True`` -- of idiff_conv2d_winograd_split_f32 (three bf16 per weight)."""
-    return _wino_pack("winograd_split" if split else "winograd", "winograd_pack", wt, Cin, Cout)
+def winograd_pack(wt, Cin, Cout):
+    """The filter bank of idiff_conv2d_winograd_f32."""
+    return _wino_pack("winograd", "winograd_pack", wt, Cin, Cout)
 
 
-def conv2d_winograd(x, u, out, B, H, W, Cin, Cout, epilogue=None, split=False):
-    """``split`` names the kernel; the bank must be the one ``winograd_pack(..., split=split)`` made."""
-    return _wino_conv("winograd_split" if split else "winograd", f"winograd_pack(..., split={split})", x, u, out, B, H, W, Cin, Cout, epilogue)
+def conv2d_winograd(x, u, out, B, H, W, Cin, Cout, epilogue=None):
+    """The bank must be the one ``winograd_pack`` made."""
+    return _wino_conv("winograd", "winograd_pack", x, u, out, B, H, W, Cin, Cout, epilogue)
 
 
 def conv2d_winograd43_ok(B, H, W, Cin, Cout):

@@ -963,7 +963,7 @@ IgemmPlan igemm_tile(int M, int N, int batch, int want) {
   }
   // >= 4 workgroups per CU available: single LDS buffer, 128 registers, four resident workgroups per CU
   // (measured 135-142 TFLOP/s vs 124-135 for the double-buffered two-workgroup form)
-  else if (N > 64 && wg_big >= 1024 && !idiff::option(idiff::OPT_DBUF_ONLY)) tile(128, 128, AR_FP32_1BUF);
+  else if (N > 64 && wg_big >= 1024) tile(128, 128, AR_FP32_1BUF);
   else if (N > 64 && wg_big >= 256) tile(128, 128, AR_FP32);
   // narrow outputs (the 3-channel image conv at the end of the U-Nets): one 32-wide MFMA column instead of two
   else if (N <= 32 && M >= 4096) tile(128, 32, AR_FP32);

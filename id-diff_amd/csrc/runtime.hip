@@ -15,9 +15,9 @@ void set_error(const char *fmt, ...) {
 
 namespace {
 const char *const kOptionNames[OPT_COUNT] = {"IDIFF_NO_WINOGRAD", "IDIFF_NO_COLSTATS", "IDIFF_NO_PIPE", "IDIFF_SCALAR_EPILOGUE",
-                                             "IDIFF_DBUF_ONLY", "IDIFF_TRIDIAG_ONESTAGE", "IDIFF_UFD_ROWS", "IDIFF_CHASE_WAVEFRONT",
-                                             "IDIFF_WINO_NGROUP", "IDIFF_GRAM_SMALL_TILES", "IDIFF_CHASE_SPIN_LIMIT",
-                                             "IDIFF_FAKE_CU_COUNT", "IDIFF_SBR_SYNC", "IDIFF_SBR_FULL", "IDIFF_NO_SPLIT", "IDIFF_WINO_SPLIT", "IDIFF_SBR_LOOKAHEAD",
+                                             "IDIFF_TRIDIAG_ONESTAGE", "IDIFF_UFD_ROWS", "IDIFF_CHASE_WAVEFRONT",
+                                             "IDIFF_GRAM_SMALL_TILES", "IDIFF_CHASE_SPIN_LIMIT",
+                                             "IDIFF_FAKE_CU_COUNT", "IDIFF_SBR_SYNC", "IDIFF_NO_SPLIT",
                                              "IDIFF_NO_WINO43", "IDIFF_NO_WINO43H", "IDIFF_NO_PAIRS", "IDIFF_PAIRS_MIN_TILES", "IDIFF_NO_FUSED_ATTN", "IDIFF_NO_WINO1D", "IDIFF_NO_FUSED_GN", "IDIFF_NO_FUSED_GN_LOAD", "IDIFF_NO_FUSED_GN_LOAD_2SRC", "IDIFF_NO_FUSED_GN_FIR"};
 struct OptionTable {
   int v[OPT_COUNT];

@@ -355,7 +355,7 @@ typedef unsigned int sbr_uintx4 __attribute__((ext_vector_type(4)));
 typedef unsigned int sbr_uintx2 __attribute__((ext_vector_type(2)));
 template <bool BUF>
 __global__ void __launch_bounds__(256) trailing_y_kernel(PanelGeom g, const double *__restrict__ V, double *__restrict__ Ypart, int krange,
-                                                         int off /* lo & 63, or -1: both triangles of A' are valid */) {
+                                                         int off /* lo & 63; the host passes no other value (< 0 would read both triangles of A' directly) */) {
   __shared__ double Vs[KSPLIT_COLS][BW];
   const int rb = blockIdx.x, ks = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), fl = lane & 15, fk = lane >> 4;
@@ -633,78 +633,8 @@ __global__ void __launch_bounds__(256) trailing_tz_kernel(PanelGeom g, const dou
   }
 }
 
-// k11: A' -= V Z^T + Z V^T on 64 x 64 tiles (wave = 32 x 32 = 2 x 2 MFMA tiles, K = 2 BW).  Tiles below the diagonal run
-// the two products in the opposite order of the tiles above it, so that (i, j) and (j, i) add the same numbers in the
-// same order: A' stays exactly symmetric; diagonal tiles write their lower half and its mirror.
-__global__ void __launch_bounds__(256) trailing_update_kernel(PanelGeom g, const double *__restrict__ V, const double *__restrict__ Z) {
-  const int ti = blockIdx.y, tj = blockIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, fl = lane & 15, fk = lane >> 4;
-  const int wi = ti * 64 + (wave >> 1) * 32, wj = tj * 64 + (wave & 1) * 32;
-  const bool below = ti > tj;
-  // operands: rows of V / Z, four consecutive k per lane
-  doublex4 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = (doublex4){0.0, 0.0, 0.0, 0.0};
-  // the tile of A' is requested first: its HBM / L2 latency runs under the operand loads and the 64 MFMAs
-  double *Ap = g.A + (int64_t)g.lo * g.D + g.lo;
-  double cold[2][2][4];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int gi = wi + a * 16 + fk + 4 * r, gj = wj + b * 16 + fl;
-        cold[a][b][r] = (gi < g.m && gj < g.m) ? Ap[(int64_t)gi * g.D + gj] : 0.0;
-      }
-  const double *first = below ? Z : V, *second = below ? V : Z;      // acc += first_i second_j^T + second_i first_j^T
-#pragma unroll
-  for (int pass = 0; pass < 2; ++pass) {
-    const double *Ai = pass == 0 ? first : second, *Bj = pass == 0 ? second : first;
-#pragma unroll
-    for (int kc = 0; kc < BW; kc += 16) {
-      double av[2][4], bv[2][4];
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const int ri = min(wi + q * 16 + fl, g.m - 1), rj = min(wj + q * 16 + fl, g.m - 1);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          av[q][u] = Ai[(int64_t)ri * BW + kc + 4 * fk + u];
-          bv[q][u] = Bj[(int64_t)rj * BW + kc + 4 * fk + u];
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-          for (int b = 0; b < 2; ++b) acc[a][b] = mfma(av[a][u], bv[b][u], acc[a][b]);
-    }
-  }
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int gi = wi + a * 16 + fk + 4 * r, gj = wj + b * 16 + fl;
-        if (gi < g.m && gj < g.m) {
-          if (ti != tj) {
-            Ap[(int64_t)gi * g.D + gj] = cold[a][b][r] - acc[a][b][r];
-          } else if (gi >= gj) {
-            const double val = cold[a][b][r] - acc[a][b][r];
-            Ap[(int64_t)gi * g.D + gj] = val;
-            Ap[(int64_t)gj * g.D + gi] = val;
-          }
-        }
-      }
-}
-
-
 // ---------------------------------------------------------------------------------------------- stage 1: lower-triangle form
-// From here on only the LOWER triangle of the trailing block A' is kept up to date, at the granularity of an ABSOLUTE
+// Only the LOWER triangle of the trailing block A' is kept up to date, at the granularity of an ABSOLUTE
 // grid of 64 x 64 tiles (tile index = matrix index >> 6, so a tile is the same set of elements for every panel although
 // the trailing block starts 32 further each time): tiles below the diagonal and the diagonal tiles (both halves) are
 // valid, tiles above it are stale.  trailing_update then reads and writes half the bytes (k11s); Y = A' V (k7) fetches a
@@ -712,12 +642,11 @@ __global__ void __launch_bounds__(256) trailing_update_kernel(PanelGeom g, const
 //
 // k11s: A' -= V Z^T + Z V^T on the tiles of the absolute 64-grid at or below the diagonal (wave = 32 x 32 = 2 x 2 MFMA
 // tiles, K = 2 BW).  Diagonal tiles write their lower half and its mirror, so they stay valid in both halves.
-// part 0: the whole block.  Look-ahead (sbr_to_band): part 1 = only the first 32 columns of A' (the next panel and the band
-// block above it; launched over tile column 0, one workgroup per tile row), part 2 = everything else -- the two parts
-// write disjoint elements (a wave owns 32 columns, and wj == 0 names exactly the waves of columns [0, 32)).
-// sel 0: every tile (triangular launch); sel 1: tile column 0 (nt workgroups; with part 1); sel 2: only the tiles the
-// pipelined kernel below leaves out -- the diagonal, tile column 0 when the block starts inside a tile, the last tile row
-// when it ends inside one (3 nt workgroups, duplicates exit).
+// part: the host passes 0, the whole block (1 / 2 would take only the waves of the first 32 columns of A' / all others).
+// sel 0: every tile (triangular launch); sel 2: only the tiles the pipelined kernel below leaves out -- the diagonal, tile
+// column 0 when the block starts inside a tile, the last tile row when it ends inside one (3 nt workgroups, duplicates
+// exit); sel 1 (tile column 0 alone) is not launched.  The device code of this kernel, of the strip kernel and of
+// trailing_y_kernel is kept as measured: the forms with these parameters folded away ran the band reduction 1 % slower.
 __global__ void __launch_bounds__(256) trailing_update_lower_kernel(PanelGeom g, int off, const double *__restrict__ V,
                                                                     const double *__restrict__ Z, int part, int sel, int nt) {
   // triangular launch: block b -> (ti, tj), tj <= ti
@@ -1452,51 +1381,12 @@ __global__ void __launch_bounds__(256) fro2_kernel(const double *__restrict__ A,
 
 namespace idiff {
 
-// Helper stream and the two events of the band reduction's look-ahead: one set per host thread and device, made on first
-// use with the priority of the stream that asked, kept for the life of the thread.
-constexpr int LOOKAHEAD_MIN_M = 4096;
-struct Lookahead {
-  hipStream_t side = nullptr;
-  hipEvent_t fork = nullptr, join = nullptr;
-};
-static Lookahead *lookahead_for(hipStream_t st) {
-  thread_local Lookahead cache[64];
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return nullptr; }
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  Lookahead &l = cache[dev & 63];
-  if (!l.side) {
-    // A priority class of its own: the runtime maps streams of one class onto a small pool of hardware queues, and a
-    // helper that lands on the caller's queue runs its launches in line with the caller's (measured inside bench.py, where
-    // a third stream exists: band reduction at D = 12288 253 ms with the helper in the caller's class, 231 ms serial).
-    // The update is the bandwidth-bound half, so it takes the lower class where there is one.
-    int prio = 0, least = 0, greatest = 0;
-    if (hipStreamGetPriority(st, &prio) != hipSuccess) { (void)hipGetLastError(); prio = 0; }
-    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { (void)hipGetLastError(); least = greatest = prio; }
-    if (prio < least) ++prio;                          // numerically larger = lower priority
-    else if (prio > greatest) --prio;
-    hipStream_t s2 = nullptr;
-    hipEvent_t a = nullptr, b = nullptr;
-    if (hipStreamCreateWithPriority(&s2, hipStreamNonBlocking, prio) != hipSuccess ||
-        hipEventCreateWithFlags(&a, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&b, hipEventDisableTiming) != hipSuccess) {
-      (void)hipGetLastError();
-      if (a) (void)hipEventDestroy(a);
-      if (s2) (void)hipStreamDestroy(s2);
-      return nullptr;                                   // no helper stream: the serial form is always available
-    }
-    l.side = s2; l.fork = a; l.join = b;
-  }
-  return &l;
-}
-
 int64_t sbr_scratch_doubles(int D) {
   const int64_t m = D;
   const int64_t nchunk = (m + CHUNK - 1) / CHUNK, nks = (m + KSPLIT_COLS - 1) / KSPLIT_COLS;
   return (int64_t)(D + PAD) * LDB             // band, zero-padded
          + (int64_t)D * (BW + 1)              // carried reflectors of stage 2
-         + 5 * m * BW                         // Q, V (two: look-ahead), Y, Z
+         + 4 * m * BW                         // Q, V, Y, Z
          + nks * m * BW                       // Ypart
          + 5 * nchunk * BW * BW               // Gram partials (G, G2, VtV, VtP, K)
          + 8 * BW * BW + BW + 16;             // R1, R2, U, Vtop, Tinv, C, W2, spare | sgn | scalars
@@ -1505,10 +1395,10 @@ int64_t sbr_scratch_doubles(int D) {
 // The read-modify-write pass over the lower triangle of A': strips of tiles through the pipelined kernel once there are
 // enough tiles to fill the chip with strips, one tile per workgroup below that.
 constexpr int STRIP_MIN_TILES = 2048;
-static void launch_update(hipStream_t st, const PanelGeom &g, int off, const double *V, const double *Z, int part, int nt) {
+static void launch_update(hipStream_t st, const PanelGeom &g, int off, const double *V, const double *Z, int nt) {
   const int tiles = nt * (nt + 1) / 2;
   if (tiles < STRIP_MIN_TILES) {
-    hipLaunchKernelGGL(trailing_update_lower_kernel, dim3(tiles), dim3(256), 0, st, g, off, V, Z, part, 0, nt);
+    hipLaunchKernelGGL(trailing_update_lower_kernel, dim3(tiles), dim3(256), 0, st, g, off, V, Z, 0, 0, nt);
     return;
   }
   const int strip = min(8, max(2, tiles / 1024));
@@ -1516,8 +1406,8 @@ static void launch_update(hipStream_t st, const PanelGeom &g, int off, const dou
   const int ti_lo = 1, ti_hi = ragged ? nt - 2 : nt - 1, tj_lo = off ? 1 : 0;       // rows ti_lo .. ti_hi, columns tj_lo .. ti - 1
   if (ti_hi >= ti_lo && ti_hi - 1 >= tj_lo)
     hipLaunchKernelGGL(trailing_update_strip_kernel, dim3(ceil_div(ti_hi - tj_lo, strip), ti_hi - ti_lo + 1), dim3(256), 0, st, g, off, V, Z,
-                       part, strip, ti_lo, tj_lo);
-  hipLaunchKernelGGL(trailing_update_lower_kernel, dim3(3 * nt), dim3(256), 0, st, g, off, V, Z, part, 2, nt);
+                       0, strip, ti_lo, tj_lo);
+  hipLaunchKernelGGL(trailing_update_lower_kernel, dim3(3 * nt), dim3(256), 0, st, g, off, V, Z, 0, 2, nt);
 }
 
 // Stage 1: G (D x D, both triangles, overwritten) -> compact lower band AB = scratch[0 .. D * LDB) (column-major band:
@@ -1526,8 +1416,7 @@ int sbr_to_band(double *G, int D, double *scratch, hipStream_t st) {
   double *AB = scratch;
   double *vs = AB + (int64_t)(D + PAD) * LDB;
   double *Q = vs + (int64_t)D * (BW + 1);
-  double *Vbuf[2] = {Q + (int64_t)D * BW, Q + 2 * (int64_t)D * BW};
-  double *Y = Vbuf[1] + (int64_t)D * BW, *Z = Y + (int64_t)D * BW;
+  double *V = Q + (int64_t)D * BW, *Y = V + (int64_t)D * BW, *Z = Y + (int64_t)D * BW;
   const int64_t nchunk_max = (D + CHUNK - 1) / CHUNK, nks_max = (D + KSPLIT_COLS - 1) / KSPLIT_COLS;
   double *Ypart = Z + (int64_t)D * BW;
   double *Gp = Ypart + nks_max * D * BW;
@@ -1552,22 +1441,8 @@ int sbr_to_band(double *G, int D, double *scratch, hipStream_t st) {
     fflush(stderr);
   };
   after("fro2", 0);
-  // IDIFF_SBR_FULL (A/B): the round-2 form that keeps both triangles of the trailing block up to date
-  const bool full = option(OPT_SBR_FULL);
-  // Look-ahead (OPT-IN, IDIFF_SBR_LOOKAHEAD): the six panel kernels of panel j + 1 need only the first 32 columns of the
-  // updated block.  Those are updated first (part 1, m x 32), then the rest of the update (part 2: the launch that moves
-  // the bytes) runs on a helper stream BESIDE the latency-bound panel chain and joins before Y = A' V needs the whole
-  // block.  Only for blocks large enough that the update outlasts the cross-stream hand-off.  Measured at D = 12288:
-  // band reduction 164 -> 151 ms in a process with two or three streams; 164 -> 262 ms once the process had made a few
-  // more (bench.py after its config-2 leg): the runtime then maps the helper onto the caller's hardware queue, whatever
-  // its priority class, and every fork / join becomes an in-queue barrier.  A library cannot see that mapping, so the
-  // default is the serial form.
-  Lookahead *la = (full || dbg || !option(OPT_SBR_LOOKAHEAD) || D - BW < LOOKAHEAD_MIN_M) ? nullptr : lookahead_for(st);
-  bool join_pending = false;
-  int j0 = 0, panel = 0;
+  int j0 = 0;
   while (D - j0 > CORNER) {
-    double *V = Vbuf[panel & 1];
-    ++panel;
     PanelGeom g;
     g.A = G; g.D = D; g.j0 = j0; g.lo = j0 + BW; g.m = D - g.lo;
     g.chunk_rows = CHUNK;
@@ -1587,42 +1462,18 @@ int sbr_to_band(double *G, int D, double *scratch, hipStream_t st) {
     hipLaunchKernelGGL(panel_v_kernel, dim3(g.nchunk), dim3(256), 0, st, g, Gp2, Q, Vtop, V, VtVp, VtPp);
     after("panel_v_kernel", j0);
     const int off = g.lo & 63;                           // the trailing block starts `off` into its first tile of the absolute grid
-    if (join_pending) {                                  // the rest of the previous update
-      if (hipError_t e2 = hipStreamWaitEvent(st, la->join, 0); e2 != hipSuccess) { set_error("sbr: hipStreamWaitEvent: %s", hipGetErrorString(e2)); return (int)e2; }
-      join_pending = false;
-    }
     if ((int64_t)D * D * 8 < 0xFFFFFFFFll)
-      hipLaunchKernelGGL(trailing_y_kernel<true>, dim3(rbs, nks), dim3(256), 0, st, g, V, Ypart, krange, full ? -1 : off);
+      hipLaunchKernelGGL(trailing_y_kernel<true>, dim3(rbs, nks), dim3(256), 0, st, g, V, Ypart, krange, off);
     else
-      hipLaunchKernelGGL(trailing_y_kernel<false>, dim3(rbs, nks), dim3(256), 0, st, g, V, Ypart, krange, full ? -1 : off);
+      hipLaunchKernelGGL(trailing_y_kernel<false>, dim3(rbs, nks), dim3(256), 0, st, g, V, Ypart, krange, off);
     after("trailing_y_kernel", j0);
     hipLaunchKernelGGL(trailing_yk_kernel, dim3(g.nchunk), dim3(256), 0, st, g, Ypart, nks, V, Y, Kp);
     after("trailing_yk_kernel", j0);
     hipLaunchKernelGGL(trailing_tz_kernel, dim3(g.nchunk), dim3(256), 0, st, g, VtVp, VtPp, Vtop, Kp, Y, V, Z, scal);
     after("trailing_tz_kernel", j0);
-    const int tiles = ceil_div(g.m, 64);
-    if (full) {
-      hipLaunchKernelGGL(trailing_update_kernel, dim3(tiles, tiles), dim3(256), 0, st, g, V, Z);
-    } else {
-      const int nt = ceil_div(g.m + off, 64);
-      if (la && g.m >= LOOKAHEAD_MIN_M) {
-        hipLaunchKernelGGL(trailing_update_lower_kernel, dim3(nt), dim3(256), 0, st, g, off, V, Z, 1, 1, nt);
-        hipError_t e2 = hipEventRecord(la->fork, st);
-        if (e2 == hipSuccess) e2 = hipStreamWaitEvent(la->side, la->fork, 0);
-        if (e2 != hipSuccess) { set_error("sbr: look-ahead fork: %s", hipGetErrorString(e2)); return (int)e2; }
-        launch_update(la->side, g, off, V, Z, 2, nt);
-        e2 = hipEventRecord(la->join, la->side);
-        if (e2 != hipSuccess) { set_error("sbr: look-ahead join: %s", hipGetErrorString(e2)); return (int)e2; }
-        join_pending = true;
-      } else {
-        launch_update(st, g, off, V, Z, 0, nt);
-      }
-    }
-    after("trailing_update_kernel", j0);
+    launch_update(st, g, off, V, Z, ceil_div(g.m + off, 64));
+    after("trailing_update", j0);
     j0 += BW;
-  }
-  if (join_pending) {
-    if (hipError_t e2 = hipStreamWaitEvent(st, la->join, 0); e2 != hipSuccess) { set_error("sbr: hipStreamWaitEvent: %s", hipGetErrorString(e2)); return (int)e2; }
   }
   {
     const int n = D - j0;

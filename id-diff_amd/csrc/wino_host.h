@@ -140,8 +140,8 @@ template <class P> auto wino_fill_consts(P &p, int) -> decltype((void)p.c_nb2) {
 template <class P> void wino_fill_consts(P &, long) {}      // WinoParams: F(2x2, 3x3) has no such constants
 
 // Pointers, dimensions, byte extents (u_floats: the bank without a header), epilogue, the 6-point transforms' constants where the struct has
-// them, and the output-channel tiles: ngroup of them are scheduled together (tile_n innermost inside a group) -- IDIFF_WINO_NGROUP where it
-// divides tiles_n, else `ngroup_pairs ? two : all` (see the callers for which and why)
+// them, and the output-channel tiles: ngroup of them are scheduled together (tile_n innermost inside a group):
+// `ngroup_pairs ? two : all` (see the callers for which and why)
 template <class P>
 void wino_fill(P &p, const float *x, const float *u, float *out, int B, int H, int W, int Cin, int Cout, int64_t u_floats, int64_t res_bytes,
                const idiff_epilogue *ep, int cout_tile, bool ngroup_pairs) {
@@ -151,8 +151,7 @@ void wino_fill(P &p, const float *x, const float *u, float *out, int B, int H, i
   idiff::set_epilogue(p, ep);
   wino_fill_consts(p, 0);
   p.tiles_n = Cout / cout_tile;
-  const int want = idiff::option_value(idiff::OPT_WINO_NGROUP);
-  p.ngroup = (want > 0 && p.tiles_n % want == 0) ? want : ((ngroup_pairs && p.tiles_n > 2 && p.tiles_n % 2 == 0) ? 2 : p.tiles_n);
+  p.ngroup = (ngroup_pairs && p.tiles_n > 2 && p.tiles_n % 2 == 0) ? 2 : p.tiles_n;
 }
 
 // the tile grid of WinoParams / Wino43Params: output tiles of edge x edge pixels, wg_tiles of them per workgroup

@@ -97,16 +97,10 @@ __device__ __forceinline__ void split_tile(const WinoParams &p, int T, int &img,
   }
 }
 
-// ---------------------------------------------------------------- tail (shared by the fp32 and the split-precision kernel)
-// MODE 0 (fp32 kernel, 4 waves): acc[2 j + h] = M at position (wi, j) for this wave's 32 tiles x cout half h, in the 32x32
-//   accumulator layout.
-// MODE 1 (split kernel, 8 waves): wave (wi, jh) holds only positions j = 2 jh, 2 jh + 1: acc[2 jj + h].  The waves of
-//   jh = 1 park their share of z_ib in LDS, the waves of jh = 0 add theirs on top, and waves 0 .. 3 (tid < THREADS) finish as
-//   in mode 0; the other four only keep the barriers company.
-template <int MODE>
+// ---------------------------------------------------------------- tail
+// acc[2 j + h] = M at position (wi, j) for this wave's 32 tiles x cout half h, in the 32x32 accumulator layout.
 __device__ __forceinline__ void wino_tail(const WinoParams &p, const floatx16 *acc, float *lds, const int tile0, const int n0,
                                           const int tile_m, const int tid, const int lane, const int wave, const int wi, const int tb) {
-  const bool active = MODE == 0 || tid < THREADS;     // wave-uniform
   // This thread finishes 4 channels (n .. n+3) of tiles 2g and 2g+1: output pixels (2ty + a, 2tx + b).  Everything here
   // is VALU work that no MFMA hides (a wave's non-MFMA VALU instructions were split about evenly between the K loop and
   // prologue + tail at Cin = 256), so the tail is written to issue as few of them as it can: 32-bit byte offsets into
@@ -132,7 +126,7 @@ __device__ __forceinline__ void wino_tail(const WinoParams &p, const floatx16 *a
   uint32_t ooff[2];            // its byte offset (+ this thread's channels), INVALID_PIXEL beyond the last tile
   float4 badd[2], res[2][4];
   float sc[2];
-  if (active) {
+  {
     int T = tile0 + 2 * g, img, ty, tx;
     split_tile(p, T, img, ty, tx);
     float4 bias = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -162,47 +156,19 @@ __device__ __forceinline__ void wino_tail(const WinoParams &p, const floatx16 *a
   // z_ib for this wave's row i: z_i0 = m_i0 + m_i1 + m_i2, z_i1 = m_i1 - m_i2 - m_i3 -> LDS [i][tile][b][cout]
   {
     float *zp = lds + ((wi * WG_TILES + tb * 32 + 4 * (lane >> 5)) * 2) * 64 + (lane & 31);
-    if (MODE == 0) {
 #pragma unroll
-      for (int ch = 0; ch < 2; ++ch)
+    for (int ch = 0; ch < 2; ++ch)
 #pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-          const float m0 = acc[ch][reg], m1 = acc[2 + ch][reg], m2 = acc[4 + ch][reg], m3 = acc[6 + ch][reg];
-          const int trow = (reg & 3) + 8 * (reg >> 2);        // + 4 * (lane >> 5): row of the 32x32 accumulator tile
-          zp[(trow * 2) * 64 + ch * 32] = m0 + m1 + m2;
-          zp[(trow * 2 + 1) * 64 + ch * 32] = m1 - m2 - m3;
-        }
-    } else {
-      const bool second = wave >= 4;                           // jh = 1: positions (wi, 2), (wi, 3)
-      if (second) {
-#pragma unroll
-        for (int ch = 0; ch < 2; ++ch)
-#pragma unroll
-          for (int reg = 0; reg < 16; ++reg) {
-            const float m2 = acc[ch][reg], m3 = acc[2 + ch][reg];
-            const int trow = (reg & 3) + 8 * (reg >> 2);
-            zp[(trow * 2) * 64 + ch * 32] = m2;
-            zp[(trow * 2 + 1) * 64 + ch * 32] = -m2 - m3;
-          }
+      for (int reg = 0; reg < 16; ++reg) {
+        const float m0 = acc[ch][reg], m1 = acc[2 + ch][reg], m2 = acc[4 + ch][reg], m3 = acc[6 + ch][reg];
+        const int trow = (reg & 3) + 8 * (reg >> 2);        // + 4 * (lane >> 5): row of the 32x32 accumulator tile
+        zp[(trow * 2) * 64 + ch * 32] = m0 + m1 + m2;
+        zp[(trow * 2 + 1) * 64 + ch * 32] = m1 - m2 - m3;
       }
-      __syncthreads();
-      if (!second) {
-#pragma unroll
-        for (int ch = 0; ch < 2; ++ch)
-#pragma unroll
-          for (int reg = 0; reg < 16; ++reg) {
-            const float m0 = acc[ch][reg], m1 = acc[2 + ch][reg];
-            const int trow = (reg & 3) + 8 * (reg >> 2);
-            zp[(trow * 2) * 64 + ch * 32] = (m0 + m1) + zp[(trow * 2) * 64 + ch * 32];
-            zp[(trow * 2 + 1) * 64 + ch * 32] = m1 + zp[(trow * 2 + 1) * 64 + ch * 32];
-          }
-      }
-    }
   }
   __syncthreads();
 
   double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
-  if (active) {
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
 #pragma unroll
@@ -252,7 +218,6 @@ __device__ __forceinline__ void wino_tail(const WinoParams &p, const floatx16 *a
       }
     }
   }
-  }
   if (want_stats && p.tiles_per_img < WG_TILES) {
     // Maps smaller than a workgroup (8x8: 16 tiles, 4x4: 4 tiles per sample): the workgroup holds WG_TILES / tiles_per_img
     // whole samples and writes one slot per (sample, channel), layout [B][1][Cout][2].  A thread's two tiles lie in one
@@ -260,16 +225,14 @@ __device__ __forceinline__ void wino_tail(const WinoParams &p, const floatx16 *a
     // 64 x samples threads add up the tile pairs of their sample in a fixed order.
     __syncthreads();                                          // every z has been read: the area is free again
     double *red = reinterpret_cast<double *>(lds);           // [16 tile pairs][64 channels][2]
-    if (active) {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        red[((g * WG_COUT) + 4 * cq + e) * 2] = s1[e];
-        red[((g * WG_COUT) + 4 * cq + e) * 2 + 1] = s2[e];
-      }
+    for (int e = 0; e < 4; ++e) {
+      red[((g * WG_COUT) + 4 * cq + e) * 2] = s1[e];
+      red[((g * WG_COUT) + 4 * cq + e) * 2 + 1] = s2[e];
     }
     __syncthreads();
     const int pairs = p.tiles_per_img >> 1, samples = WG_TILES / p.tiles_per_img;
-    for (int o = active ? tid : samples * WG_COUT; o < samples * WG_COUT; o += THREADS) {
+    for (int o = tid; o < samples * WG_COUT; o += THREADS) {
       const int smp = o / WG_COUT, ch = o - smp * WG_COUT;
       const int64_t img = (int64_t)tile_m * samples + smp;
       if (img >= p.B) continue;
@@ -287,7 +250,7 @@ __device__ __forceinline__ void wino_tail(const WinoParams &p, const floatx16 *a
     }
     __syncthreads();                                          // every z has been read: the area is free again
     double *red = reinterpret_cast<double *>(lds);           // [NWAVES][64][2]
-    if (lane < 16 && active) {
+    if (lane < 16) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         red[((wave * WG_COUT) + 4 * cq + e) * 2] = s1[e];
@@ -487,242 +450,7 @@ winograd_kernel(const WinoParams p) {
   }
   if (early) run(std::true_type()); else run(std::false_type());
 
-  wino_tail<0>(p, acc, lds, tile0, n0, tile_m, tid, lane, wave, wi, tb);
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// Split-precision form: the same algorithm with the 16 position-wise contractions M_p = V_p U_p^T on the bf16 matrix cores.
-// Every fp32 operand element is cut EXACTLY into three bf16 pieces (8 + 8 + 8 mantissa bits, x = x1 + x2 + x3) and a product
-// is the six partial products of weight >= 2^-16, fp32 accumulation: what is left out is < 2^-23 |a b| per product, one fp32
-// rounding (igemm.hip, split4; measured 1.7e-7 against 2.0e-7 for the fp32 MFMA chain).  v_mfma_f32_32x32x16_bf16 retires
-// 16 channels in 32 cycles where the fp32 form needs 8 x 64: six of them are 2.7x cheaper, and they leave the vector ALU
-// free for the transforms and the splitting.
-//   * U is split once, in idiff_winograd_pack_split_f32: per 16-channel step, output tile, position and piece a block of
-//     [64 cout][16 cin] bf16 (32 bytes per output channel: the fragment of lane half 0, then that of lane half 1).
-//   * V stays fp32 in LDS, in the layout of the fp32 kernel: a 16-channel step is two of its 8-channel stages.  Lane
-//     (tile fr, half fh) reads the eight channels of stage fh for its tile (two 16-byte reads, the conflict-free one first:
-//     lane half 1 therefore gets its two quads in the opposite order, and the packed U matches) and splits them in
-//     registers: each V element is consumed by exactly one wave, so splitting on the reading side costs the same vector
-//     work as on the writing side and keeps the LDS traffic at 4 bytes per element.
-//   * 8 waves = 4 rows of the transform domain x 2 pairs of positions, 32 tiles x 64 output channels per workgroup, one
-//     workgroup per CU: a wave holds 2 positions x 2 channel halves (64 accumulators) and its 12 U fragments a step ahead
-//     (48 registers), which fits TWO waves per SIMD (256 registers each) -- with one wave per SIMD (the first version: 4
-//     waves x 4 positions, 128 accumulators + 96 registers of U) nothing covered a wait and the kernel ran at 0.8x of the
-//     fp32 one, its matrix pipe busy 24 % of the time.  One LDS stage of V: fragments go to registers, a barrier, then
-//     the stage is rewritten under this step's matrix instructions.
-//   * What bounds it (round 3, profiles/r03_split_winograd_phases.txt + PMC): a 16-channel step moves 96 KB of U and 32 KB of x from
-//     L2 into the CU, 128 KB in ~3.9k cycles = 33 B/clk/CU = 13.6 TB/s chip-wide -- the rate the vector-memory path of a
-//     CU sustains from L2 (MI355X_MICROARCH.md, 'Indexed rows': 66-73 GB/s per CU), against 1536 cycles of matrix work per
-//     SIMD.  Re-ordering the step (M1 held back across the barrier, roles in separate loops) only moved the waiting from
-//     one phase to another.  Fewer bytes per product need 64 tiles per workgroup (U read once for twice the tiles), i.e.
-//     128 accumulators per wave next to ~130 other registers at two waves per SIMD: does not fit.  Hence opt-in, not default.
-constexpr int SPLIT_KC = 16;
-constexpr size_t SPLIT_LDS_BYTES = sizeof(float) * (size_t)(4 * STAGE_FLOATS > TAIL_FLOATS ? 4 * STAGE_FLOATS : TAIL_FLOATS);   // 133 KB: two stages of 2 x 8 channels
-constexpr int SPLIT_POS_BYTES = 3 * 64 * SPLIT_KC * 2;          // one position of one slab: 3 pieces x [64 cout][16 cin] bf16
-constexpr int SPLIT_SLAB_BYTES = NPOS * SPLIT_POS_BYTES;        // 98304
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void split8(const float4 lo, const float4 hi, bf16x8 &p1, bf16x8 &p2, bf16x8 &p3) {
-  const float x[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-  uintx4 q1, q2, q3;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    uint32_t t1[2], t2[2], t3[2];
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      t1[e] = __float_as_uint(x[2 * j + e]) & 0xffff0000u;
-      const float r1 = x[2 * j + e] - __uint_as_float(t1[e]);
-      t2[e] = __float_as_uint(r1) & 0xffff0000u;
-      t3[e] = __float_as_uint(r1 - __uint_as_float(t2[e]));
-    }
-    q1[j] = (t1[0] >> 16) | t1[1];
-    q2[j] = (t2[0] >> 16) | t2[1];
-    q3[j] = (t3[0] >> 16) | (t3[1] & 0xffff0000u);
-  }
-  p1 = __builtin_bit_cast(bf16x8, q1); p2 = __builtin_bit_cast(bf16x8, q2); p3 = __builtin_bit_cast(bf16x8, q3);
-}
-
-constexpr int SPLIT_THREADS = 512;
-
-__global__ void __launch_bounds__(SPLIT_THREADS, 1)
-winograd_split_kernel(const WinoParams p) {
-  static_assert(WG_TILES == 32 && THREADS == 256, "the split kernel is written for 32 tiles: 8 waves = 4 rows x 2 position pairs");
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int nwg = p.tiles_m * p.tiles_n;
-  int bid = blockIdx.x;
-  {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, local = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
-  }
-  const int per_group = p.tiles_m * p.ngroup;
-  const int grp = bid / per_group, in_grp = bid - grp * per_group;
-  const int tile_n = grp * p.ngroup + in_grp % p.ngroup, tile_m = in_grp / p.ngroup;
-  const int tile0 = tile_m * WG_TILES, n0 = tile_n * WG_COUT;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wi = wave & 3, jh = wave >> 2;          // transform-domain row; positions j = 2 jh, 2 jh + 1
-
-  const __amdgpu_buffer_rsrc_t rX = __builtin_amdgcn_make_buffer_rsrc((void *)p.x, 0, (int)p.x_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rU = __builtin_amdgcn_make_buffer_rsrc((void *)p.u, 0, (int)p.u_bytes, 0x00020000);
-
-  // ---------------------------------------------------------------- loader state: thread = row r of the 4x4 patch of one
-  // (tile, 8-channel stage h, 4-channel quad q) unit; the four rows of a unit are the four lanes of a DPP quad
-  uint32_t v_src[4], u_src[2];
-  int v_dst;
-  float sgn;
-  {
-    const int r = tid & 3, q = (tid >> 2) & 1, h = (tid >> 3) & 1, tl = tid >> 4;
-    const int T = tile0 + tl;
-    const bool tv = T < p.total_tiles;
-    const int TT = tv ? T : 0;
-    int img, ty, tx;
-    split_tile(p, TT, img, ty, tx);
-    const int y = 2 * ty - 1 + r, x0 = 2 * tx - 1;
-    const bool yok = tv && y >= 0 && y < p.H;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int xx = x0 + j;
-      v_src[j] = (yok && xx >= 0 && xx < p.W) ? (uint32_t)(((img * p.H + y) * p.W + xx) * p.Cin + h * KC + q * 4) * 4u : INVALID_PIXEL;
-    }
-    v_dst = h * STAGE_FLOATS + r * V_SLOT + tl * KC + 4 * (q ^ ((tl >> 3) & 1));
-    sgn = (r == 1) ? 1.f : -1.f;
-    const int fr_ = lane & 31, fh_ = lane >> 5;
-#pragma unroll
-    for (int jj = 0; jj < 2; ++jj) u_src[jj] = (uint32_t)((4 * (2 * jh + jj) + wi) * SPLIT_POS_BYTES + fr_ * (SPLIT_KC * 2) + 16 * fh_);
-  }
-
-  float4 ldv[2][4];                 // the inputs of the next two steps (fetched two steps ahead: HBM latency under load)
-  uintx4 bfr[2][2][3];              // [position jj][cout half][piece]
-  const int nsteps = p.Cin / SPLIT_KC;
-  int f_step = 0;
-  auto fetch = [&](float4 (&lv)[4]) {
-    // beyond the last step the LAST step is fetched again (never consumed): the scalar offset of a raw buffer load is not
-    // range-checked, so it must not run past the tensor
-    const int choff = min(f_step, nsteps - 1) * (SPLIT_KC * 4);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) lv[j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rX, (int)v_src[j], choff, 0));
-    ++f_step;
-  };
-  auto stage = [&](int buf, const float4 (&lv)[4]) {
-    float *Vd = lds + buf * 2 * STAGE_FLOATS + v_dst;
-    float4 c[4];
-    c[0] = f4sub(lv[0], lv[2]); c[1] = f4add(lv[1], lv[2]); c[2] = f4sub(lv[2], lv[1]); c[3] = f4sub(lv[1], lv[3]);
-#define IDIFF_QFMA(x) "v_fmac_f32_dpp " x ", " x ", %16 quad_perm:[2,2,1,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n"
-    asm volatile("s_nop 1\n" IDIFF_QFMA("%0") IDIFF_QFMA("%1") IDIFF_QFMA("%2") IDIFF_QFMA("%3") IDIFF_QFMA("%4") IDIFF_QFMA("%5")
-                 IDIFF_QFMA("%6") IDIFF_QFMA("%7") IDIFF_QFMA("%8") IDIFF_QFMA("%9") IDIFF_QFMA("%10") IDIFF_QFMA("%11")
-                 IDIFF_QFMA("%12") IDIFF_QFMA("%13") IDIFF_QFMA("%14") IDIFF_QFMA("%15")
-                 : "+v"(c[0].x), "+v"(c[0].y), "+v"(c[0].z), "+v"(c[0].w), "+v"(c[1].x), "+v"(c[1].y), "+v"(c[1].z), "+v"(c[1].w),
-                   "+v"(c[2].x), "+v"(c[2].y), "+v"(c[2].z), "+v"(c[2].w), "+v"(c[3].x), "+v"(c[3].y), "+v"(c[3].z), "+v"(c[3].w)
-                 : "v"(sgn));
-#undef IDIFF_QFMA
-#pragma unroll
-    for (int j = 0; j < 4; ++j) *reinterpret_cast<float4 *>(Vd + j * 4 * V_SLOT) = c[j];
-  };
-
-  floatx16 acc[4];                  // [position jj][cout half]
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-
-  const int fr = lane & 31, fh = lane >> 5, sw = (fr >> 3) & 1;
-  // stage fh, row fr; first the half the fp32 kernel's lane would read (conflict-free), then the other one
-  const int a_first = fh * STAGE_FLOATS + (4 * 2 * jh + wi) * V_SLOT + fr * KC + 4 * (fh ^ sw);
-  const int a_second = fh * STAGE_FLOATS + (4 * 2 * jh + wi) * V_SLOT + fr * KC + 4 * (fh ^ sw ^ 1);
-
-  auto load_b = [&](int jj, int step) {
-    const int slab = (step * p.tiles_n + tile_n) * SPLIT_SLAB_BYTES;
-#pragma unroll
-    for (int hb = 0; hb < 2; ++hb)
-#pragma unroll
-      for (int q = 0; q < 3; ++q)
-        bfr[jj][hb][q] = __builtin_amdgcn_raw_buffer_load_b128(rU, (int)u_src[jj] + q * (64 * SPLIT_KC * 2) + hb * (32 * SPLIT_KC * 2), slab, 0);
-  };
-
-  load_b(0, 0);
-  load_b(1, 0);
-  fetch(ldv[0]);
-  stage(0, ldv[0]);
-  fetch(ldv[0]);                    // step 1
-  fetch(ldv[1]);                    // step 2
-  __syncthreads();
-
-  constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};     // the six partial products, smallest first
-  const bool early = jh == 0;
-  // step s: the V of step s + 1 is in ldv[s & 1] (requested two steps ago); `lv` is that set
-  auto step = [&](int s, float4 (&lv)[4]) {
-    const int buf = s & 1;
-    const float *S = lds + buf * 2 * STAGE_FLOATS;
-    float4 alo[2], ahi[2];
-#pragma unroll
-    for (int jj = 0; jj < 2; ++jj) {
-      alo[jj] = *reinterpret_cast<const float4 *>(S + a_first + 4 * jj * V_SLOT);
-      ahi[jj] = *reinterpret_cast<const float4 *>(S + a_second + 4 * jj * V_SLOT);
-    }
-    // waves w and w + 4 share a SIMD: one writes the other stage (vector work) while its partner's matrix instructions run
-    if (early) { stage(buf ^ 1, lv); fetch(lv); }
-    const int snext = min(s + 1, nsteps - 1);
-#pragma unroll
-    for (int jj = 0; jj < 2; ++jj) {
-      bf16x8 a[3];
-      split8(alo[jj], ahi[jj], a[0], a[1], a[2]);
-#pragma unroll
-      for (int t = 0; t < 6; ++t)
-#pragma unroll
-        for (int hb = 0; hb < 2; ++hb)
-          acc[2 * jj + hb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA[t]], __builtin_bit_cast(bf16x8, bfr[jj][hb][PB[t]]), acc[2 * jj + hb], 0, 0, 0);
-      load_b(jj, snext);
-    }
-    if (!early) { stage(buf ^ 1, lv); fetch(lv); }
-    __syncthreads();
-  };
-  for (int s = 0; s < nsteps; s += 2) {
-    step(s, ldv[0]);
-    if (s + 1 < nsteps) step(s + 1, ldv[1]);
-  }
-  wino_tail<1>(p, acc, lds, tile0, n0, tile_m, tid, lane, wave, wi, 0);
-}
-
-// U = G g G^T (fp64, rounded once to fp32 exactly as idiff_winograd_pack_f32 does), then cut into the three bf16 pieces and
-// laid out for winograd_split_kernel: [Cin / 16][Cout / 64][16 positions][3 pieces][64 cout][16 cin], where the 16 channels
-// of a row are the eight of lane half 0 (channels 0 .. 7 of the step) followed by the eight of lane half 1 in ITS reading
-// order (channels 12 .. 15, then 8 .. 11).
-__global__ void winograd_pack_split_kernel(const float *wt, unsigned short *u, int Cin, int Cout) {
-  const int64_t total = (int64_t)Cin * Cout;
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    const int cin = (int)(idx % Cin), cout = (int)(idx / Cin);
-    double g[3][3];
-    for (int ky = 0; ky < 3; ++ky)
-      for (int kx = 0; kx < 3; ++kx) g[ky][kx] = (double)wt[((int64_t)cout * 9 + ky * 3 + kx) * Cin + cin];
-    double gg[4][3];   // G g
-    for (int kx = 0; kx < 3; ++kx) {
-      gg[0][kx] = g[0][kx];
-      gg[1][kx] = 0.5 * (g[0][kx] + g[1][kx] + g[2][kx]);
-      gg[2][kx] = 0.5 * (g[0][kx] - g[1][kx] + g[2][kx]);
-      gg[3][kx] = g[2][kx];
-    }
-    const int s = cin / SPLIT_KC, c16 = cin % SPLIT_KC, nt = cout / WG_COUT, co = cout % WG_COUT;
-    const int half = c16 >> 3, e = c16 & 7;
-    const int pos_in_row = half * 8 + (half ? ((e >> 2) ^ 1) * 4 + (e & 3) : e);
-    unsigned short *dst = u + ((int64_t)(s * (Cout / WG_COUT) + nt) * NPOS * 3 * 64 + co) * SPLIT_KC + pos_in_row;
-    for (int i = 0; i < 4; ++i) {
-      const double r0 = gg[i][0], r1 = gg[i][1], r2 = gg[i][2];
-      const double v[4] = {r0, 0.5 * (r0 + r1 + r2), 0.5 * (r0 - r1 + r2), r2};
-      const double sign = i == 3 ? -1.0 : 1.0;     // the kernel's input transform produces row 3 negated
-      for (int j = 0; j < 4; ++j) {
-        const float x = (float)(sign * v[j]);
-        const uint32_t t1 = __float_as_uint(x) & 0xffff0000u;
-        const float r1f = x - __uint_as_float(t1);
-        const uint32_t t2 = __float_as_uint(r1f) & 0xffff0000u;
-        const uint32_t t3 = __float_as_uint(r1f - __uint_as_float(t2));
-        unsigned short *d = dst + (int64_t)(j * 4 + i) * 3 * 64 * SPLIT_KC;
-        d[0] = (unsigned short)(t1 >> 16);
-        d[64 * SPLIT_KC] = (unsigned short)(t2 >> 16);
-        d[2 * 64 * SPLIT_KC] = (unsigned short)(t3 >> 16);
-      }
-    }
-  }
+  wino_tail(p, acc, lds, tile0, n0, tile_m, tid, lane, wave, wi, tb);
 }
 
 // U = G g G^T in fp64, rounded once; g[ky][kx] = wt[cout][ky][kx][cin] (the K-contiguous panel of the direct kernel).
@@ -779,28 +507,6 @@ IDIFF_API int idiff_conv2d_winograd_colstats_split(int B, int H, int W, int Cin,
 
 IDIFF_API int64_t idiff_winograd_weight_floats(int Cin, int Cout) { return (int64_t)16 * Cin * Cout; }
 
-// The split-precision form (winograd_split_kernel): Cin % 16 == 0 on top of the fp32 kernel's conditions.  OPT-IN
-// (IDIFF_WINO_SPLIT): correct to the same bars, but measured 0.8x the fp32 kernel on the NCSN++ layers.
-IDIFF_API int idiff_conv2d_winograd_split_ok(int B, int H, int W, int Cin, int Cout) {
-  if (!idiff::option(idiff::OPT_WINO_SPLIT) || idiff::option(idiff::OPT_NO_SPLIT) || idiff::option(idiff::OPT_NO_WINOGRAD)) return 0;
-  if (!geometry_ok(B, H, W, Cin, Cout) || Cin % SPLIT_KC) return 0;
-  if ((int64_t)24 * Cin * Cout * 4 >= X_LIMIT) return 0;
-  return 1;
-}
-
-IDIFF_API int64_t idiff_winograd_split_weight_floats(int Cin, int Cout) { return (int64_t)24 * Cin * Cout; }   // 3 bf16 per weight
-
-IDIFF_API int idiff_winograd_pack_split_f32(const float *wt, float *u, int Cin, int Cout, void *stream) {
-  using namespace idiff;
-  if (Cin <= 0 || Cout <= 0 || Cin % SPLIT_KC || Cout % WG_COUT)
-    return fail("winograd_pack_split: Cin must be a multiple of %d and Cout of %d (got %d, %d)", SPLIT_KC, WG_COUT, Cin, Cout);
-  if (!wt || !u) return fail("winograd_pack_split: null pointer");
-  const int64_t total = (int64_t)Cin * Cout;
-  hipLaunchKernelGGL(winograd_pack_split_kernel, dim3(streaming_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, wt,
-                     reinterpret_cast<unsigned short *>(u), Cin, Cout);
-  return launch_status("winograd_pack_split");
-}
-
 IDIFF_API int idiff_winograd_pack_f32(const float *wt, float *u, int Cin, int Cout, void *stream) {
   using namespace idiff;
   if (Cin <= 0 || Cout <= 0 || Cin % KC || Cout % WG_COUT)
@@ -811,23 +517,8 @@ IDIFF_API int idiff_winograd_pack_f32(const float *wt, float *u, int Cin, int Co
   return launch_status("winograd_pack");
 }
 
-namespace {
-int conv2d_winograd_impl(const float *x, const float *u, float *out, int B, int H, int W, int Cin, int Cout,
-                         const idiff_epilogue *ep, void *stream, bool split);
-}
 IDIFF_API int idiff_conv2d_winograd_f32(const float *x, const float *u, float *out, int B, int H, int W, int Cin, int Cout,
                                         const idiff_epilogue *ep, void *stream) {
-  return conv2d_winograd_impl(x, u, out, B, H, W, Cin, Cout, ep, stream, false);
-}
-// u: the bank of idiff_winograd_pack_split_f32
-IDIFF_API int idiff_conv2d_winograd_split_f32(const float *x, const float *u, float *out, int B, int H, int W, int Cin, int Cout,
-                                              const idiff_epilogue *ep, void *stream) {
-  if (Cin % SPLIT_KC) return idiff::fail("conv2d_winograd_split: Cin must be a multiple of %d (got %d)", SPLIT_KC, Cin);
-  return conv2d_winograd_impl(x, u, out, B, H, W, Cin, Cout, ep, stream, true);
-}
-namespace {
-int conv2d_winograd_impl(const float *x, const float *u, float *out, int B, int H, int W, int Cin, int Cout,
-                         const idiff_epilogue *ep, void *stream, bool split) {
   using namespace idiff;
   if (B == 0) return 0;
   if (!geometry_ok(B, H, W, Cin, Cout))
@@ -841,13 +532,13 @@ int conv2d_winograd_impl(const float *x, const float *u, float *out, int B, int 
     const int64_t cut = host_cut_row(B, H * W, ep);
     if (!cut) return fail("conv2d_winograd: cannot split the batch inside an epilogue row group");
     return run_cut((int64_t)B * H * W, cut, ep, false, [&](int64_t r0, int64_t r1, const idiff_epilogue *e) {
-      return conv2d_winograd_impl(x + r0 * Cin, u, out + r0 * Cout, (int)((r1 - r0) / (H * W)), H, W, Cin, Cout, e, stream, split);
+      return idiff_conv2d_winograd_f32(x + r0 * Cin, u, out + r0 * Cout, (int)((r1 - r0) / (H * W)), H, W, Cin, Cout, e, stream);
     });
   }
   WinoParams p = {};
   // two output-channel tiles per scheduling group: the workgroups of an XCD then stream two filter slabs instead of
   // four (1.5-3 % on the Cout = 256 layers; the slabs of four tiles plus the live input lines overflow the 4 MB L2)
-  wino_fill(p, x, u, out, B, H, W, Cin, Cout, (int64_t)(split ? 24 : 16) * Cin * Cout, res_bytes, ep, WG_COUT, true);
+  wino_fill(p, x, u, out, B, H, W, Cin, Cout, (int64_t)16 * Cin * Cout, res_bytes, ep, WG_COUT, true);
   wino_fill_tiles(p, 2, WG_TILES);
   if (ep && ep->colstats && p.tiles_per_img % WG_TILES && !(p.tiles_per_img >= 2 && p.tiles_per_img % 2 == 0 && WG_TILES % p.tiles_per_img == 0))
     return fail("conv2d_winograd: colstats needs whole workgroups per sample or whole samples per workgroup "
@@ -858,17 +549,9 @@ int conv2d_winograd_impl(const float *x, const float *u, float *out, int B, int 
     if (int rc = set_dynamic_lds_once(guard, fns, 2, (int)LDS_BYTES, "conv2d_winograd")) return rc;
   }
   const int nwg = p.tiles_m * p.tiles_n;
-  if (split) {
-    static AttrGuard sguard;
-    const void *fn = reinterpret_cast<const void *>(winograd_split_kernel);
-    if (int rc = set_dynamic_lds_once(sguard, &fn, 1, (int)SPLIT_LDS_BYTES, "conv2d_winograd_split")) return rc;
-    hipLaunchKernelGGL(winograd_split_kernel, dim3(nwg), dim3(SPLIT_THREADS), SPLIT_LDS_BYTES, (hipStream_t)stream, p);
-    return launch_status("conv2d_winograd_split");
-  }
   if (nwg >= PEEL_MIN_WORKGROUPS)
     hipLaunchKernelGGL(winograd_kernel<true>, dim3(nwg), dim3(THREADS), LDS_BYTES, (hipStream_t)stream, p);
   else
     hipLaunchKernelGGL(winograd_kernel<false>, dim3(nwg), dim3(THREADS), LDS_BYTES, (hipStream_t)stream, p);
   return launch_status("conv2d_winograd");
 }
-}  // namespace

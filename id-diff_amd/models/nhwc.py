@@ -112,11 +112,9 @@ CONV3X3_ROUTES = (
                  "conv2d_winograd43", lambda *geom: {"pairs": True}),
     Conv3x3Route("wino43_fp32", "wino43", _wino43_fp32_serves, "winograd43_pack", "conv2d_winograd43_colstats_split",
                  "conv2d_winograd43", lambda *geom: {"pairs": False}),
-    # Winograd F(2x2, 3x3): 2.25x fewer MFMA flops than the implicit GEMM.  The bank is keyed by the kernel form too: the
-    # split-precision form is asked for per call, so a switch flipped later or another geometry through this layer picks its
-    # own bank instead of inheriting the first one packed
+    # Winograd F(2x2, 3x3): 2.25x fewer MFMA flops than the implicit GEMM
     Conv3x3Route("wino22", "wino", _wino22_serves, "winograd_pack", "conv2d_winograd_colstats_split", "conv2d_winograd",
-                 lambda *geom: {"split": _lib.conv2d_winograd_split_ok(*geom)}),
+                 lambda *geom: {}),
 )
 
 

@@ -39,16 +39,13 @@ const char *idiff_variant_flags(void);
 
 /* Debug / A-B switches, named like the environment variables that initialise them at load time:
  * IDIFF_NO_WINOGRAD (3x3 convs on the implicit GEMM), IDIFF_NO_COLSTATS, IDIFF_NO_PIPE, IDIFF_SCALAR_EPILOGUE,
- * IDIFF_DBUF_ONLY, IDIFF_TRIDIAG_ONESTAGE (per-column Householder instead of the two-stage band reduction),
+ * IDIFF_TRIDIAG_ONESTAGE (per-column Householder instead of the two-stage band reduction),
  * IDIFF_UFD_ROWS, IDIFF_CHASE_WAVEFRONT (bulge chasing one launch per wavefront instead of the persistent systolic kernel),
  * IDIFF_CHASE_SPIN_LIMIT (polls before a waiting node of the systolic chase gives up; default 2^24), IDIFF_FAKE_CU_COUNT
  * (CU count used when sizing the systolic chase; tests), IDIFF_SBR_SYNC (band reduction waits for and names every launch on
- * stderr: a fault then names its kernel), IDIFF_SBR_FULL (band reduction keeps both triangles up to date, the round-2 form),
+ * stderr: a fault then names its kernel),
  * IDIFF_NO_SPLIT (contractions of idiff_gemm_f32 / idiff_conv2d_nhwc_f32 on the fp32 matrix cores instead of the
- * split-precision products described there), IDIFF_WINO_SPLIT (opt-in: the split-precision Winograd kernel),
- * IDIFF_SBR_LOOKAHEAD (opt-in: band reduction with the look-ahead -- the bulk of a panel's trailing update on a helper
- * stream beside the next panel's factorisation; 5 % at D = 12288 when the helper gets a hardware queue of its own, 50 %
- * SLOWER when the runtime maps it onto the caller's queue, which happens once a process has made a few streams),
+ * split-precision products described there),
  * IDIFF_NO_WINO43 (3x3 convolutions on the F(2x2,3x3) kernel instead of F(4x4,3x3)), IDIFF_NO_WINO43H (F(4x4,3x3) with its
  * contractions on the fp32 matrix cores instead of fp16 pairs), IDIFF_NO_FUSED_ATTN (idiff_attention256_ok and idiff_attention_heads_ok answer 0), IDIFF_NO_WINO1D (idiff_conv2d_wino1d_ok answers 0),
  * IDIFF_NO_FUSED_GN (idiff_conv2d_wino1d_gn_ok answers 0: the GroupNorm behind a row-wise convolution stays a launch of its own), IDIFF_NO_FUSED_GN_LOAD
@@ -375,20 +372,6 @@ int idiff_conv2d_wino1d_normload_f32(const float *x, const float *u, float *out,
 int idiff_conv2d_wino1d_normload_2src_ok(int B, int H, int W, int C1, int C2, int Cout);
 int idiff_conv2d_wino1d_normload_2src_f32(const float *x1, int C1, const float *x2, int C2, const float *u, float *out, int B, int H, int W,
                                           int Cout, const idiff_epilogue *ep, const float *coef, int act, void *stream);
-
-/* Split-precision form of the same convolution: the 16 position-wise contractions run on the bf16 matrix cores with every
- * fp32 operand cut exactly into three bf16 pieces and six of the nine partial products kept (fp32 accumulation; what is
- * dropped is < 2^-23 of a product, one fp32 rounding -- the result meets the same parity bars as the fp32 form).
- *   idiff_conv2d_winograd_split_ok       1 when served: the fp32 form's conditions, Cin % 16 == 0, and IDIFF_WINO_SPLIT set
- *                                        (opt-in: measured slower than the fp32 form on the NCSN++ layers).
- *   idiff_winograd_split_weight_floats   size of its filter bank (24 * Cin * Cout floats: three bf16 per transformed weight).
- *   idiff_winograd_pack_split_f32        wt [Cout, 3, 3, Cin] -> that bank, once per layer.
- *   idiff_conv2d_winograd_split_f32      as idiff_conv2d_winograd_f32 with that bank (same epilogue, same colstats split). */
-int idiff_conv2d_winograd_split_ok(int B, int H, int W, int Cin, int Cout);
-int64_t idiff_winograd_split_weight_floats(int Cin, int Cout);
-int idiff_winograd_pack_split_f32(const float *wt, float *u, int Cin, int Cout, void *stream);
-int idiff_conv2d_winograd_split_f32(const float *x, const float *u, float *out, int B, int H, int W, int Cin, int Cout,
-                                    const idiff_epilogue *ep, void *stream);
 
 /* ------------------------------------------------------------------ normalisation / pointwise (HBM-bound) */
 

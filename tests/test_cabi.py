@@ -92,14 +92,14 @@ def test_thread_option_acts_on_the_calling_thread_only():
     """idiff_set_thread_option: the fail-soft re-solve selects a slower eigensolver form for ITS launch; another host thread's
     launches keep reading the process-wide value (checked through a host-only query that reads a switch)."""
     import threading
-    ask = lambda: _lib.conv2d_winograd_split_ok(4, 16, 16, 64, 64)       # reads IDIFF_WINO_SPLIT, no device call
-    assert ask() is False
+    ask = lambda: _lib.conv2d_winograd_ok(4, 16, 16, 64, 64)             # reads IDIFF_NO_WINOGRAD, no device call
+    assert ask() is True
     seen = {}
-    with _lib.thread_option("IDIFF_WINO_SPLIT", 1):
-        assert ask() is True
+    with _lib.thread_option("IDIFF_NO_WINOGRAD", 1):
+        assert ask() is False
         t = threading.Thread(target=lambda: seen.setdefault("other", ask()))
         t.start(); t.join()
-    assert seen["other"] is False and ask() is False
+    assert seen["other"] is True and ask() is True
     with pytest.raises(KeyError):
         with _lib.thread_option("IDIFF_NO_SUCH_SWITCH", 1):
             pass

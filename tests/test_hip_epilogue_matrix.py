@@ -31,7 +31,6 @@ Measured on the MI355X (combinations run, largest err / tol; a ratio above 0.5 i
     conv2d_winograd43, fp32 contraction                        2         960          0.277
     conv2d_winograd43, fp16 pairs                              2         960          0.132
     conv2d_winograd, fp32                                      3         960          0.128
-    conv2d_winograd, split bf16                                3         960          0.126
     conv2d_nhwc, default / IDIFF_NO_SPLIT / IDIFF_NO_PIPE    3 each   960 / 960 / 720   0.200 / 0.213 / 0.213
     conv2d_nhwc narrow head, the same three                  3 each     720 each      0.175 / 0.141 / 0.117
     gemm (routes of GEMM_CASES)                                9        2880          0.235
@@ -41,7 +40,7 @@ Measured on the MI355X (combinations run, largest err / tol; a ratio above 0.5 i
     gemm, 128-row tiles (TILE_CASES)                           7         872          0.296
     gemm_2src                                                  1         240          0.184
     gemm_pairs / weight_is_a batched / gemm_pairs_2src         3     240 / 336 / 240  0.143 / 0.178 / 0.143
-17,048 launches compared element by element; no ratio above 0.5, the largest 0.296 (gemm (4096, 64, 32) on the 128 x 64 split tile).  The
+16,088 launches compared element by element; no ratio above 0.5, the largest 0.296 (gemm (4096, 64, 32) on the 128 x 64 split tile).  The
 bias-only combination stays within the bound on every launcher.  No combination failed: the matrix exposed no kernel bug.
 """
 import itertools
@@ -211,24 +210,26 @@ def test_winograd43_matrix(B, H, W, Cin, Cout, pairs):
     run_matrix(f)
 
 
-@pytest.mark.parametrize("split", [False, True], ids=["fp32", "split"])
-@pytest.mark.parametrize("B,H,W,Cin,Cout,rows", [(3, 6, 10, 32, 64, "image"), (3, 6, 10, 32, 64, "row"), (2, 16, 16, 32, 128, "image")])
-def test_winograd_matrix(B, H, W, Cin, Cout, rows, split):
+WINO22_MATRIX_CASES = [(3, 6, 10, 32, 64, "image"), (3, 6, 10, 32, 64, "row"), (2, 16, 16, 32, 128, "image")]
+
+
+@pytest.mark.parametrize("B,H,W,Cin,Cout,rows", WINO22_MATRIX_CASES, ids=["-".join(map(str, c)) + "-fp32" for c in WINO22_MATRIX_CASES])
+def test_winograd_matrix(B, H, W, Cin, Cout, rows):
     assert _lib.conv2d_winograd_ok(B, H, W, Cin, Cout)
     xd, wt, acc, A, _, _ = conv_operands(B, H, W, Cin, Cout)
-    u = _lib.winograd_pack(wt, Cin, Cout, split=split)
+    u = _lib.winograd_pack(wt, Cin, Cout)
     out = torch.empty(B * H * W, Cout, device=DEV)
     rpg = H * W if rows == "image" else W
     ns = _lib.conv2d_winograd_colstats_split(B, H, W, Cin, Cout)
     assert (ns > 0) == ((H, W) == (16, 16))                # 15 tiles of 2 x 2 per image: no whole workgroups, no whole samples
-    f = Form("conv2d_winograd" + ("_split" if split else ""), (B, H, W, Cin, Cout, f"rows_per_group={rpg}"), B * H * W, Cout, rpg, acc, A,
-             E_DIRECT, out, lambda ep: _lib.conv2d_winograd(xd, u, out, B, H, W, Cin, Cout, epilogue=ep, split=split),
+    f = Form("conv2d_winograd", (B, H, W, Cin, Cout, f"rows_per_group={rpg}"), B * H * W, Cout, rpg, acc, A,
+             E_DIRECT, out, lambda ep: _lib.conv2d_winograd(xd, u, out, B, H, W, Cin, Cout, epilogue=ep),
              stats_rows=H * W // ns if ns else 0)
     run_matrix(f)
     if not ns:
         cs = torch.zeros(B * Cout * 2, device=DEV, dtype=torch.float64)
         with pytest.raises(RuntimeError, match="colstats"):
-            _lib.conv2d_winograd(xd, u, out, B, H, W, Cin, Cout, epilogue=_lib.make_epilogue(colstats=cs), split=split)
+            _lib.conv2d_winograd(xd, u, out, B, H, W, Cin, Cout, epilogue=_lib.make_epilogue(colstats=cs))
 
 
 # ------------------------------------------------------------------------------------------- conv2d_nhwc
@@ -529,9 +530,7 @@ def test_terms_a_launcher_does_not_take_are_refused():
              ("conv2d_winograd43", _lib.winograd43_pack(wt, Cin, Cout), lambda u, ep: _lib.conv2d_winograd43(x, u, out, B, H, W, Cin, Cout, epilogue=ep), True),
              ("conv2d_winograd43h", _lib.winograd43_pack(wt, Cin, Cout, pairs=True),
               lambda u, ep: _lib.conv2d_winograd43(x, u, out, B, H, W, Cin, Cout, epilogue=ep, pairs=True), True),
-             ("conv2d_winograd", _lib.winograd_pack(wt, Cin, Cout), lambda u, ep: _lib.conv2d_winograd(x, u, out, B, H, W, Cin, Cout, epilogue=ep), False),
-             ("conv2d_winograd_split", _lib.winograd_pack(wt, Cin, Cout, split=True),
-              lambda u, ep: _lib.conv2d_winograd(x, u, out, B, H, W, Cin, Cout, epilogue=ep, split=True), False)]
+             ("conv2d_winograd", _lib.winograd_pack(wt, Cin, Cout), lambda u, ep: _lib.conv2d_winograd(x, u, out, B, H, W, Cin, Cout, epilogue=ep), False)]
     for name, u, call, per_image_only in forms:
         if per_image_only:
             with pytest.raises(RuntimeError, match="per image"):

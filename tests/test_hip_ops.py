@@ -480,17 +480,15 @@ def test_conv2d_narrow_head_vs_cpu(B, H, W, Cout):
     assert rel_err(out.cpu(), direct.double().cpu()) < 2e-6
 
 
-@pytest.mark.parametrize("split", [False, True], ids=["fp32", "split"])
-@pytest.mark.parametrize("B,H,W,Cin,Cout", [(3, 32, 32, 128, 128), (5, 16, 16, 256, 64), (7, 8, 8, 64, 128),
-                                              (9, 4, 4, 32, 64), (2, 6, 10, 8, 64), (1, 2, 2, 16, 64), (33, 4, 4, 8, 64),
-                                              (2, 16, 16, 512, 256), (130, 2, 2, 48, 64)])
-def test_conv2d_winograd_vs_cpu(B, H, W, Cin, Cout, split):
-    """F(2x2, 3x3) conv against the fp64 CPU convolution, with every epilogue term (per-sample bias, activation,
-    residual, scales); tile counts that do not fill a workgroup, maps smaller than a workgroup's 64 tiles.  Both forms of
-    the position-wise contractions -- fp32 matrix cores, and operands cut exactly into three bf16 pieces with six partial
-    products on the bf16 matrix cores -- are held to the same 3e-6."""
-    if split and Cin % 16:
-        pytest.skip("the split-precision kernel takes 16 channels per step")
+WINO22_CASES = [(3, 32, 32, 128, 128), (5, 16, 16, 256, 64), (7, 8, 8, 64, 128), (9, 4, 4, 32, 64), (2, 6, 10, 8, 64),
+                (1, 2, 2, 16, 64), (33, 4, 4, 8, 64), (2, 16, 16, 512, 256), (130, 2, 2, 48, 64)]
+
+
+@pytest.mark.parametrize("B,H,W,Cin,Cout", WINO22_CASES, ids=["-".join(map(str, c)) + "-fp32" for c in WINO22_CASES])
+def test_conv2d_winograd_vs_cpu(B, H, W, Cin, Cout):
+    """F(2x2, 3x3) conv (position-wise contractions on the fp32 matrix cores) against the fp64 CPU convolution, with every
+    epilogue term (per-sample bias, activation, residual, scales); tile counts that do not fill a workgroup, maps smaller
+    than a workgroup's 64 tiles."""
     g = torch.Generator().manual_seed(B * H + Cin)
     x = torch.randn(B, Cin, H, W, generator=g)
     w = torch.randn(Cout, Cin, 3, 3, generator=g) / (Cin * 9) ** 0.5
@@ -501,22 +499,19 @@ def test_conv2d_winograd_vs_cpu(B, H, W, Cin, Cout, split):
     assert _lib.conv2d_winograd_ok(B, H, W, Cin, Cout)
     xd = x.permute(0, 2, 3, 1).contiguous().to(DEV)
     wt = w.permute(0, 2, 3, 1).contiguous().to(DEV)
-    with _lib.thread_option("IDIFF_WINO_SPLIT", 1):        # the split-precision Winograd kernel is opt-in; asked per call
-        assert _lib.conv2d_winograd_split_ok(B, H, W, Cin, Cout) == (Cin % 16 == 0)
-    assert not _lib.conv2d_winograd_split_ok(B, H, W, Cin, Cout)
-    u = _lib.winograd_pack(wt, Cin, Cout, split=split)
-    assert u.numel() == (24 if split else 16) * Cin * Cout
+    u = _lib.winograd_pack(wt, Cin, Cout)
+    assert u.numel() == 16 * Cin * Cout
     out = torch.empty(B, H, W, Cout, device=DEV)
-    with pytest.raises(RuntimeError, match="filter bank"):  # the bank of the other form is refused, never reinterpreted
-        _lib.conv2d_winograd(xd, u, out, B, H, W, Cin, Cout, split=not split)
-    _lib.conv2d_winograd(xd, u, out, B, H, W, Cin, Cout, epilogue=_lib.make_epilogue(bias=b.to(DEV)), split=split)
+    with pytest.raises(RuntimeError, match="filter bank"):  # the bank of another form is refused, never reinterpreted
+        _lib.conv2d_winograd(xd, _lib.winograd43_pack(wt, Cin, Cout), out, B, H, W, Cin, Cout)
+    _lib.conv2d_winograd(xd, u, out, B, H, W, Cin, Cout, epilogue=_lib.make_epilogue(bias=b.to(DEV)))
     ref = F.conv2d(x.double(), w.double(), b.double(), padding=1)
     assert rel_err(out.permute(0, 3, 1, 2).cpu(), ref) < 3e-6
     direct = torch.empty_like(out)
     _lib.conv2d_nhwc(xd, wt, direct, B, H, W, Cin, Cout, 3, 3, 1, 1, epilogue=_lib.make_epilogue(bias=b.to(DEV)))
     assert rel_err(out.cpu(), direct.double().cpu()) < 3e-6
     resd = res.permute(0, 2, 3, 1).contiguous().to(DEV)
-    _lib.conv2d_winograd(xd, u, out, B, H, W, Cin, Cout, split=split,
+    _lib.conv2d_winograd(xd, u, out, B, H, W, Cin, Cout,
                          epilogue=_lib.make_epilogue(bias=b.to(DEV), rowbias=temb.to(DEV), rows_per_group=H * W, act="silu",
                                                      residual=resd, out_scale=0.7071, rowscale=rsc.to(DEV)))
     ref2 = (F.silu(ref + temb.double()[:, :, None, None]) + res.double()) * 0.7071 * rsc.double()[:, None, None, None]
@@ -599,9 +594,11 @@ def test_conv2d_winograd_rejects_what_it_cannot_take():
         _lib.conv2d_winograd(x, torch.zeros(16 * 32 * 64, device=DEV), torch.zeros(2, 7, 8, 64, device=DEV), 2, 7, 8, 32, 64)
 
 
-@pytest.mark.parametrize("split", [False, True], ids=["fp32", "split"])
-@pytest.mark.parametrize("B,H,Cin,Cout", [(3, 32, 64, 128), (6, 16, 128, 64), (5, 8, 64, 128), (11, 4, 32, 64), (64, 4, 8, 64)])
-def test_winograd_colstats_feed_groupnorm(B, H, Cin, Cout, split):
+WINO22_COLSTATS_CASES = [(3, 32, 64, 128), (6, 16, 128, 64), (5, 8, 64, 128), (11, 4, 32, 64), (64, 4, 8, 64)]
+
+
+@pytest.mark.parametrize("B,H,Cin,Cout", WINO22_COLSTATS_CASES, ids=["-".join(map(str, c)) + "-fp32" for c in WINO22_COLSTATS_CASES])
+def test_winograd_colstats_feed_groupnorm(B, H, Cin, Cout):
     """Column sums from the conv epilogue = a statistics pass over its output; maps of 8x8 and 4x4 (several whole samples per
     workgroup, one slot per sample) with sample counts that leave the last workgroup partly empty."""
     g = torch.Generator().manual_seed(B)
@@ -612,11 +609,9 @@ def test_winograd_colstats_feed_groupnorm(B, H, Cin, Cout, split):
     assert ns == max(1, H * H // 128)                   # 32 output tiles (of 2x2 pixels) per workgroup
     cs = torch.empty(B * ns * Cout * 2, device=DEV, dtype=torch.float64)
     out = torch.empty(B, H * H, Cout, device=DEV)
-    if split and Cin % 16:
-        pytest.skip("the split-precision kernel takes 16 channels per step")
-    u = _lib.winograd_pack(w, Cin, Cout, split=split)
-    assert u.numel() == (24 if split else 16) * Cin * Cout
-    _lib.conv2d_winograd(x, u, out, B, H, H, Cin, Cout, split=split,
+    u = _lib.winograd_pack(w, Cin, Cout)
+    assert u.numel() == 16 * Cin * Cout
+    _lib.conv2d_winograd(x, u, out, B, H, H, Cin, Cout,
                          epilogue=_lib.make_epilogue(bias=bias, act="silu", rows_per_group=H * H, colstats=cs))
     G = 32
     st_a, st_b = torch.empty(B * G * 2, device=DEV), torch.empty(B * G * 2, device=DEV)

@@ -554,7 +554,7 @@ _IGEMM_ROUTES = [
     ((), "gemm", dict(M=128, N=65, K=64, batch=256), None, "pipe 128x128 split scalar"),
     (("IDIFF_NO_SPLIT",), "gemm", dict(M=128 * 128, N=256, K=64), None, "pipe 128x128 fp32 buf-row"),
     (("IDIFF_NO_SPLIT",), "gemm", dict(M=128 * 512, N=256, K=64), None, "pipe 128x128 fp32-1buf buf-row"),
-    (("IDIFF_NO_SPLIT", "IDIFF_DBUF_ONLY"), "gemm", dict(M=128 * 512, N=256, K=64), None, "pipe 128x128 fp32 buf-row"),
+    (("IDIFF_NO_SPLIT",), "gemm", dict(M=128 * 511, N=256, K=64), None, "pipe 128x128 fp32 buf-row"),        # 1022 tiles: the last below 1buf
     (("IDIFF_NO_SPLIT",), "gemm", dict(M=4096, N=32, K=64), None, "pipe 128x32 fp32 buf-row"),
     (("IDIFF_NO_PIPE",), "gemm", dict(M=128 * 128, N=256, K=64), None, "direct-vec 128x128 fp32 scalar"),
     (("IDIFF_NO_PIPE",), "gemm", dict(M=4096, N=64, K=64), None, "direct-vec 128x64 fp32 scalar"),
