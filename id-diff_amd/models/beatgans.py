@@ -204,7 +204,7 @@ class BeatGANsUNetModel(NhwcExecutor):
             assert x2 is None
             h, x = self._box(h, mod.up), self._box(x, mod.up)
         w0, b0 = self._cw(pk, mod.in_layers[2])
-        h = self._conv(h, w0, b0, stats=True, normed=True)
+        h = self._conv(h, w0, b0, then_norm=True, normed=True)
         off = pk["emb_off"][id(mod)]
         h = self._gn_act(h, mod.out_layers[0], "silu", mod=emb_all[:, off:off + 2 * mod.out_channels])
         if isinstance(mod.skip_connection, nn.Identity):
@@ -218,7 +218,7 @@ class BeatGANsUNetModel(NhwcExecutor):
                 part = self._pointwise(x, ws[0].view(ws[0].shape[0], -1), bsk)
                 sc = self._pointwise(x2, ws[1].view(ws[1].shape[0], -1), None, residual=part.buf)
         w1, b1 = self._cw(pk, mod.out_layers[3])
-        return self._conv(h, w1, b1, residual=sc.buf, stats=True, normed=True)
+        return self._conv(h, w1, b1, residual=sc.buf, then_norm=True, normed=True)
 
     def _attn(self, mod, x, pk):
         """AttentionBlock._forward (BeatGANsblocks.py:433-443) with QKVAttentionLegacy (:466-491) or QKVAttention (:498-526): the head
@@ -232,7 +232,7 @@ class BeatGANsUNetModel(NhwcExecutor):
             pk["lin"][key] = (*pack_qkv_heads(w, b, mod.num_heads, mod.use_new_attention_order),
                               mod.proj_out.weight.detach().float().view(C, C).contiguous(),
                               mod.proj_out.bias.detach().float().contiguous())
-        return self._attention(pk, x, n, mod.norm, *pk["lin"][key], pk["lin"], (id(mod), "attn_scale"), heads=mod.num_heads)
+        return self._attention(pk, x, n, *pk["lin"][key], pk["lin"], (id(mod), "attn_scale"), heads=mod.num_heads)
 
     def _resample(self, mod, x, pk):
         if mod.up:

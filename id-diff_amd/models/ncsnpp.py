@@ -30,7 +30,7 @@ import torch.nn as nn
 
 from .. import _lib
 from . import utils
-from .nhwc import NhwcExecutor, _T, _pad4
+from .nhwc import NhwcExecutor, NormedBy, _T, _pad4
 
 _INV_SQRT2 = float(1.0 / np.sqrt(2.0))
 
@@ -326,25 +326,23 @@ class NCSNpp(NhwcExecutor):
         else:                 # FIR in front of the stride-2 conv, conv_downsample_2d :171-178 (3x3 conv)
             p = (n - 2) + 2
             k, up, down, p0, p1 = pk["fir_down"], 1, 1, (p + 1) // 2, p // 2
-        OH = _lib.upfirdn2d_out_size(x.H, up, down, p0, p1, n)
-        OW = _lib.upfirdn2d_out_size(x.W, up, down, p0, p1, n)
-        if gn is not None:
-            if x.stats is None or x.pending is not None or _lib.ACT[act] not in (0, 1) or x.C % gn.num_groups or x.C % 4:
-                return None
-            coef = torch.empty(B * x.C * 2, device=x.buf.device, dtype=torch.float32)
-            y = self._new(B, OH, OW, x.C, x.buf)
-            if not _lib.upfirdn2d_gn_ok(x.buf, coef, act, y.buf, B, x.H, x.W, x.C, n, n, up, up, down, down, p0, p1, p0, p1):
-                return None
-            _lib.groupnorm_reader_coef(x.stats[0], x.stats[1], x.C, B, x.H * x.W, gn.num_groups, gn.eps, gn.weight.detach(),
-                                       gn.bias.detach(), coef)
-            _lib.upfirdn2d_gn(x.buf, k, coef, act, y.buf, B, x.H, x.W, x.C, up, up, down, down, p0, p1, p0, p1)
-            # what _gn_act sets on the norm's output, through the resampler's gain as below
-            y.norm = (gn, (x.C // gn.num_groups) * x.H * x.W, pk["fir_gain"][mode], False)
-            return y
+        OH, OW = (_lib.upfirdn2d_out_size(size, up, down, p0, p1, n) for size in (x.H, x.W))
+        if gn is not None and (x.stats is None or x.pending is not None or _lib.ACT[act] not in (0, 1) or x.C % gn.num_groups or x.C % 4):
+            return None
         y = self._new(B, OH, OW, x.C, x.buf)
-        _lib.upfirdn2d_raw(x.buf, k, y.buf, B, x.H, x.W, x.C, up, up, down, down, p0, p1, p0, p1)
-        if x.norm is not None:
-            y.norm = (x.norm[0], x.norm[1], x.norm[2] * pk["fir_gain"][mode], x.norm[3])
+        geom, taps = (B, x.H, x.W, x.C), (up, up, down, down, p0, p1, p0, p1)
+        norm = x.norm
+        if gn is not None:
+            coef = torch.empty(B * x.C * 2, device=x.buf.device, dtype=torch.float32)
+            if not _lib.upfirdn2d_gn_ok(x.buf, coef, act, y.buf, *geom, n, n, *taps):
+                return None
+            _lib.groupnorm_reader_coef(*x.stats, x.C, B, x.H * x.W, gn.num_groups, gn.eps, gn.weight.detach(), gn.bias.detach(), coef)
+            _lib.upfirdn2d_gn(x.buf, k, coef, act, y.buf, *geom, *taps)
+            norm = NormedBy.of(gn, x.C, x.H * x.W)
+        else:
+            _lib.upfirdn2d_raw(x.buf, k, y.buf, *geom, *taps)
+        if norm is not None:
+            y.norm = norm.through(pk["fir_gain"][mode])
         return y
 
     # -------------------------------------------------------------------------------------------- blocks
@@ -358,11 +356,11 @@ class NCSNpp(NhwcExecutor):
         if mod.up or mod.down:
             assert x2 is None
             # an up / down block's norm is read by the resampler alone: the FIR applies it to what it loads where that form is served
-            h = self._fir(x, pk, "up" if mod.up else "down", gn=mod.GroupNorm_0, act=self.act_name) if self.fir else None
+            mode = "up" if mod.up else "down"
+            resample = (lambda t: self._fir(t, pk, mode)) if self.fir else (lambda t: self._box(t, mod.up))
+            h = self._fir(x, pk, mode, gn=mod.GroupNorm_0, act=self.act_name) if self.fir else None
             if h is None:
-                h = self._gn_act(x, mod.GroupNorm_0, self.act_name)
-                h = self._fir(h, pk, "up" if mod.up else "down") if self.fir else self._box(h, mod.up)
-            resample = (lambda t: self._fir(t, pk, "up" if mod.up else "down")) if self.fir else (lambda t: self._box(t, mod.up))
+                h = resample(self._gn_act(x, mod.GroupNorm_0, self.act_name))
             # an up block's 1x1 shortcut runs BEFORE the upsampling (a 1x1 over the channels and a resampler over the pixels commute
             # exactly): the GEMM on a quarter of the rows, the resampler on the shortcut's channel count.  Its bias goes behind both, into
             # Conv_1's.  A down block resamples first already: the narrower side.
@@ -404,7 +402,7 @@ class NCSNpp(NhwcExecutor):
             if (idx, "1+shortcut") not in pk["conv"]:
                 pk["conv"][(idx, "1+shortcut")] = (w1, (b1 + bs).contiguous())
             b1 = pk["conv"][(idx, "1+shortcut")][1]
-        return self._conv(h, w1, b1, residual=sc.buf, out_scale=rs, stats=True, normed=True)   # next: a GroupNorm_0 / skip
+        return self._conv(h, w1, b1, residual=sc.buf, out_scale=rs, then_norm=True, normed=True)   # next: a GroupNorm_0 / skip
 
     def _attn(self, idx, x, pk):
         """AttnBlockpp (layerspp.py:62-91)."""
@@ -414,7 +412,7 @@ class NCSNpp(NhwcExecutor):
             wq, bq = self._nin_w(pk, (idx, 0), mod.NIN_0)
             wk, bk = self._nin_w(pk, (idx, 1), mod.NIN_1)
             pk["nin"][(idx, "qk")] = (torch.cat([wq, wk], 0).contiguous(), torch.cat([bq, bk], 0).contiguous())
-        return self._attention(pk, x, n, mod.GroupNorm_0, *pk["nin"][(idx, "qk")], *self._nin_w(pk, (idx, 2), mod.NIN_2),
+        return self._attention(pk, x, n, *pk["nin"][(idx, "qk")], *self._nin_w(pk, (idx, 2), mod.NIN_2),
                                *self._nin_w(pk, (idx, 3), mod.NIN_3), pk["nin"], (idx, "attn_scale"),
                                out_scale=_INV_SQRT2 if self.skip_rescale else 1.0)
 
@@ -474,7 +472,7 @@ class NCSNpp(NhwcExecutor):
                     _lib.nchw_to_nhwc(x, xin.buf, B, C, H * W, cp, 2.0, -1.0)  # 2x - 1, ncsnpp.py:264-266
                 pyr_in = xin
                 w, b = self._conv_w(pk, (step[1], "stem"), M[step[1]])
-                hs = [self._conv(xin, w, b, stats=True)]
+                hs = [self._conv(xin, w, b, then_norm=True)]
             elif op == "res_push":
                 h = self._resblock(step[1], hs[-1], temb_all, pk)
                 if step[2] is not None:

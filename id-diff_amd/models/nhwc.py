@@ -3,7 +3,9 @@
 An activation is a ``_T`` ([B, H*W, C] + geometry); every step is one or a few launches from libidiff_hip.so.  ``NCSNpp`` (and
 ``DDPM``) and ``BeatGANsUNetModel`` inherit ``NhwcExecutor`` and add what is theirs: the module list (= the reference's
 ``state_dict`` layout), the plan, the weight packing, FIR resampling.  Which kernel serves a 3x3 convolution is decided in one
-place, ``CONV3X3_ROUTES`` / ``conv3x3_route``: host logic only, testable without a GPU.
+place, ``CONV3X3_ROUTES`` / ``conv3x3_route``: host logic only, testable without a GPU.  A GroupNorm reaches its reader by one of
+several kernels (its own pass, a convolution's tail or loader, a resampler's loader); whichever did it leaves the same ``NormedBy``
+record on its output, and ``_conv`` returns one thing, a ``_T``, whether or not its tail applied the norm that follows.
 """
 from typing import Callable, NamedTuple, Optional
 
@@ -25,11 +27,32 @@ class PendingNorm(NamedTuple):
     gn: torch.nn.Module
     src2: Optional["_T"]     # the second source of a concatenation that was not made, or None
 
-    def served(self, B, H, W, cout):
-        """Does the loader (still) apply this norm in front of a convolution of [B, H, W] to ``cout`` channels?  The query of its source count."""
+    def applied_by(self, route, B, H, W, cout):
+        """Does the convolution of [B, H, W] to ``cout`` channels on ``route`` (still) apply this norm in its loader?  Asked by _defer_norm
+        before it puts the pass off and again by _conv before it launches (a switch flipped in between: no, the pass after all)."""
+        if route is None or route.name != "wino1d":
+            return False
         if self.src2 is None:
             return _lib.conv2d_wino1d_normload_ok(B, H, W, self.src.C, cout)
         return _lib.conv2d_wino1d_normload_2src_ok(B, H, W, self.src.C, self.src2.C, cout)
+
+
+class NormedBy(NamedTuple):
+    """On the output of a GroupNorm (and kept through the resamplers): what HipScoreModel.pairs_admissible needs to decide whether the
+    consumer may run on fp16 pairs.  Every kernel that applies a norm records it with ``of``; a resampler passes it ``through``."""
+    gn: torch.nn.Module
+    group_elems: int         # elements per normalised group
+    gain: float              # absolute gain of what followed the norm
+    modulated: bool          # a per-sample scale-shift followed it
+
+    @classmethod
+    def of(cls, gn, channels, pixels, modulated=False):
+        """``gn`` over ``channels`` channels (of all its sources) on maps of ``pixels`` pixels."""
+        return cls(gn, (channels // gn.num_groups) * pixels, 1.0, modulated)
+
+    def through(self, gain):
+        """Behind a linear map whose output stays within ``gain`` times its input's range (a FIR resampler's absolute tap sum)."""
+        return self._replace(gain=self.gain * gain)
 
 
 class _T:
@@ -41,9 +64,17 @@ class _T:
         self.buf, self.H, self.W, self.C, self.stats = buf, H, W, C, stats
         # a PendingNorm where a GroupNorm was NOT applied: ``buf`` is still the norm's raw input
         self.pending = pending
-        # set on the output of a GroupNorm (and kept through the resamplers): (module, elements per normalised group, absolute gain of
-        # what followed, modulated?) -- what HipScoreModel.pairs_admissible needs to decide whether the consumer may run on fp16 pairs
+        # a NormedBy on the output of a GroupNorm (and of the resamplers behind one)
         self.norm = norm
+
+    @property
+    def is_normed(self):
+        """``buf`` holds a GroupNorm's output (not a convolution's that a norm is still to read, _conv's ``then_norm``)."""
+        return self.norm is not None and self.pending is None
+
+
+# the second source of a concatenation where there is none, as far as a norm reads one: no buffer, no channels, no column sums to add
+_NO_SOURCE = NamedTuple("_NoSource", [(field, object) for field in ("buf", "C", "stats", "pending")])(None, 0, (None, 0), None)    # immutable
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -164,114 +195,116 @@ class NhwcExecutor(HipScoreModel):
         loader.  cat[x, x2] (both with column sums) goes the same way where the two-source query routes its class (its own switch,
         IDIFF_NO_FUSED_GN_LOAD_2SRC): neither the concatenated nor the normalised tensor is made, the record carries ``x2`` as ``src2`` and
         the tensor handed on is the first source under the concatenation's channel count (_defer_norm)."""
-        B = x.buf.shape[0]
-        HW = x.H * x.W
-        C2 = x2.C if x2 is not None else 0
-        G = gn.num_groups
-        norm = (gn, ((x.C + C2) // G) * HW, 1.0, mod is not None)
-        if conv_cout is not None and mod is None:
-            deferred = self._defer_norm(x, x2, gn, act, norm, conv_cout)
+        B, HW, G = x.buf.shape[0], x.H * x.W, gn.num_groups
+        s2 = _NO_SOURCE if x2 is None else x2
+        C = x.C + s2.C
+        norm = NormedBy.of(gn, C, HW, modulated=mod is not None)
+        # every source carries the column sums its producing contraction wrote: no pass over the activations for the statistics
+        summed = x.stats is not None and s2.stats is not None
+        if conv_cout is not None and mod is None and summed:
+            deferred = self._defer_norm(PendingNorm(None, act, x, gn, x2), norm, conv_cout)
             if deferred is not None:
                 return deferred
-        if x.stats is not None and (x2 is None or x2.stats is not None) and x.C + C2 <= 1024 and B <= 65535:
-            # both sources carry the column sums their producing contraction wrote: no pass over the activations, and the
-            # statistics are finished inside the apply kernel (one launch per GroupNorm)
-            ws2, ns2 = x2.stats if x2 is not None else (None, 0)
-            y = self._new(B, x.H, x.W, x.C + C2, x.buf)
-            _lib.groupnorm_apply_colstats(x.buf, x.C, x2.buf if x2 is not None else None, C2, B, HW, G, x.stats[0], x.stats[1],
-                                          ws2, ns2, gn.eps, gn.weight.detach(), gn.bias.detach(), act, y.buf, mod=mod)
-            y.norm = norm
+        y = self._new(B, x.H, x.W, C, x.buf)
+        y.norm = norm
+        sources, affine = (x.buf, x.C, s2.buf, s2.C, B, HW, G), (gn.weight.detach(), gn.bias.detach(), act, y.buf)
+        if summed and C <= 1024 and B <= 65535:
+            # the statistics are finished inside the apply kernel (one launch per GroupNorm)
+            _lib.groupnorm_apply_colstats(*sources, *x.stats, *s2.stats, gn.eps, *affine, mod=mod)
             return y
         stats = torch.empty(B * G * 2, device=x.buf.device, dtype=torch.float32)
-        if x.stats is not None and (x2 is None or x2.stats is not None):
-            ws2, ns2 = x2.stats if x2 is not None else (None, 0)
-            _lib.groupnorm_finalize(x.stats[0], x.stats[1], x.C, ws2, ns2, C2, B, HW, G, gn.eps, stats)
+        if summed:
+            _lib.groupnorm_finalize(*x.stats, x.C, *s2.stats, s2.C, B, HW, G, gn.eps, stats)
         else:
-            nsplit = _lib.groupnorm_nsplit(B, HW, x.C + C2)
-            ws = torch.empty(B * nsplit * (x.C + C2) * 2, device=x.buf.device, dtype=torch.float64)
-            _lib.groupnorm_stats(x.buf, x.C, x2.buf if x2 is not None else None, C2, B, HW, G, gn.eps, ws, stats)
-        y = self._new(B, x.H, x.W, x.C + C2, x.buf)
-        _lib.groupnorm_apply(x.buf, x.C, x2.buf if x2 is not None else None, C2, B, HW, G, stats,
-                             gn.weight.detach(), gn.bias.detach(), act, y.buf, mod=mod)
-        y.norm = norm
+            ws = torch.empty(B * _lib.groupnorm_nsplit(B, HW, C) * C * 2, device=x.buf.device, dtype=torch.float64)
+            _lib.groupnorm_stats(*sources, gn.eps, ws, stats)
+        _lib.groupnorm_apply(*sources, stats, *affine, mod=mod)
         return y
 
-    def _defer_norm(self, x, x2, gn, act, norm, conv_cout):
-        """_gn_act's unmodulated norm in front of a 3x3 convolution to ``conv_cout`` channels: the raw tensor with a PendingNorm where the
-        convolution's loader applies it (_gn_act's conditions), else None."""
-        srcs = (x,) if x2 is None else (x, x2)
-        B, C = x.buf.shape[0], sum(s.C for s in srcs)
-        pending = PendingNorm(None, act, x, gn, x2)                 # the coefficients follow once every condition holds
-        if not (all(s.stats is not None and s.pending is None for s in srcs) and x.W == 32 and _lib.ACT[act] in (0, 1)
-                and pending.served(B, x.H, x.W, conv_cout)
-                and self.pairs_admissible(gn, norm[1], gain=1.0, transform=True, modulated=False)):
+    def _pairs_ok(self, norm, transform, **asked):
+        """May the consumer of what ``norm`` (a NormedBy) describes run on fp16 pairs?  ``asked``: fields to ask about instead of the record's."""
+        norm = norm._replace(**asked)
+        return self.pairs_admissible(norm.gn, norm.group_elems, gain=norm.gain, transform=transform, modulated=norm.modulated)
+
+    def _defer_norm(self, pending, norm, conv_cout):
+        """_gn_act's unmodulated norm of sources with column sums in front of a 3x3 convolution to ``conv_cout`` channels: the raw tensor
+        with ``pending`` (and its coefficients) where the convolution's loader applies it (_gn_act's conditions), else None."""
+        x, s2, gn = pending.src, pending.src2 or _NO_SOURCE, pending.gn
+        B, C = x.buf.shape[0], x.C + s2.C
+        if not (x.pending is None and s2.pending is None and x.W == 32 and _lib.ACT[pending.act] in (0, 1)
+                and pending.applied_by(conv3x3_route(B, x.H, x.W, C, conv_cout, True, True), B, x.H, x.W, conv_cout)
+                and self._pairs_ok(norm, transform=True)):
             return None
-        route = conv3x3_route(B, x.H, x.W, C, conv_cout, True, True)
-        if route is None or route.name != "wino1d":
-            return None
-        ws2, ns2, C2 = (*x2.stats, x2.C) if x2 is not None else (None, 0, 0)
         coef = torch.empty(B * C * 2, device=x.buf.device, dtype=torch.float32)
-        _lib.groupnorm_coef(x.stats[0], x.stats[1], x.C, ws2, ns2, C2, B, x.H * x.W, gn.num_groups, gn.eps, gn.weight.detach(),
-                            gn.bias.detach(), coef)
+        _lib.groupnorm_coef(*x.stats, x.C, *s2.stats, s2.C, B, x.H * x.W, gn.num_groups, gn.eps, gn.weight.detach(), gn.bias.detach(), coef)
         return _T(x.buf, x.H, x.W, C, norm=norm, pending=pending._replace(coef=coef))
 
-    def _conv(self, x, wt, bias, stride=1, pad=1, pad_hi=None, stats=False, normed=False, fuse_gn=None, **ep):
-        """``stats=True``: the output feeds a GroupNorm -> ask the epilogue for its per-tile column sums.
-        ``fuse_gn=(gn, act)`` (instead of ``stats``; _conv_gn_act's argument): that GroupNorm is unmodulated and reads nothing else.
-        Returns ``(y, fused)``: where the row-wise kernel applies the norm in its own tail, ``y`` is the GroupNorm's output (``norm``
-        set, no ``stats``) and ``fused`` is True; otherwise ``y`` is the convolution's output with its column sums.
+    def _conv(self, x, wt, bias, stride=1, pad=1, pad_hi=None, normed=False, then_norm=None, **ep):
+        """``then_norm``: what reads the output.  True: a GroupNorm -> ask the epilogue for the per-tile column sums (``stats``).
+        ``(gn, act)`` (_conv_gn_act's argument): that GroupNorm, unmodulated, and nothing else -> where the row-wise kernel applies it in
+        its own tail the result is the GroupNorm's output (``is_normed``, no ``stats``), otherwise the convolution's with its column sums.
         ``normed=True``: the input is the output of a GroupNorm (+ activation, + FIR resampling), i.e. bounded by
         sqrt(group size) * |gamma| + |beta| -- only then may the Winograd contraction run on fp16 pairs, whose transformed input
         must stay below 65504 (include/idiff_hip.h), and only if THIS checkpoint's gamma / beta keep that bound inside the range
         (base.HipScoreModel.pairs_admissible, decided once per layer at pack time); any other input takes the fp32 contraction."""
-        B = x.buf.shape[0]
+        y, geom, route = self._conv_route(x, wt, stride, pad, pad_hi, normed, ep)
+        x = self._settle_pending(x, route, geom)
+        if route is not None:
+            return self._conv3x3(route, x, wt, bias, y, geom, then_norm, ep)
+        kh, kw = wt.shape[1:3]
+        if then_norm:
+            self._colstats(y, _lib.conv2d_colstats_split(*geom, kh, kw, stride, pad, pad_hi), ep)
+        _lib.conv2d_nhwc(x.buf, wt, y.buf, *geom, kh, kw, stride, pad, epilogue=_lib.make_epilogue(bias=bias, **ep), pad_hi=pad_hi)
+        return y
+
+    def _conv_route(self, x, wt, stride, pad, pad_hi, normed, ep):
+        """_conv's geometry: the output tensor, (B, H, W, cin, cout), the route (None: the implicit GEMM); ``ep`` gets its row groups."""
         cout, kh, kw, cin = wt.shape
         assert cin == x.C, (cin, x.C)
         if normed:
             assert x.norm is not None, "normed=True on a tensor that is not a GroupNorm's (resampled) output"
-            gn, group_elems, gain, modulated = x.norm
-            normed = self.pairs_admissible(gn, group_elems, gain=gain, transform=True, modulated=modulated)
+            normed = self._pairs_ok(x.norm, transform=True)
         ph = pad if pad_hi is None else pad_hi
         OH = (x.H + pad + ph - kh) // stride + 1
         OW = (x.W + pad + ph - kw) // stride + 1
-        y = self._new(B, OH, OW, cout, x.buf)
-        if "rows_per_group" not in ep:
-            ep["rows_per_group"] = OH * OW
-        geom = (B, x.H, x.W, cin, cout)
+        ep.setdefault("rows_per_group", OH * OW)
+        geom = (x.buf.shape[0], x.H, x.W, cin, cout)
         route = None
         if (kh, kw, stride, pad, ph) == (3, 3, 1, 1, 1):
             route = conv3x3_route(*geom, normed, ep["rows_per_group"] == OH * OW)
-        pending = x.pending
-        if pending is not None and (route is None or route.name != "wino1d" or not pending.served(B, x.H, x.W, cout)):
-            # not the convolution _gn_act foresaw (a switch flipped in between): the pass after all, never a raw tensor into a kernel
-            x, pending = self._gn_act(pending.src, pending.gn, pending.act, pending.src2), None
-        if route is None:
-            if stats or fuse_gn is not None:
-                self._colstats(y, _lib.conv2d_colstats_split(*geom, kh, kw, stride, pad, pad_hi), ep)
-            _lib.conv2d_nhwc(x.buf, wt, y.buf, *geom, kh, kw, stride, pad, epilogue=_lib.make_epilogue(bias=bias, **ep), pad_hi=pad_hi)
-            return (y, False) if fuse_gn is not None else y
-        # the transformed filter bank is cached beside the panel; the entry keeps `wt` so that its id cannot be reused while it lives
+        return self._new(geom[0], OH, OW, cout, x.buf), geom, route
+
+    def _settle_pending(self, x, route, geom):
+        """``x`` as the convolution on ``route`` may read it: itself, or, where its norm is pending and this is not the convolution
+        _gn_act foresaw (a switch flipped in between), the pass after all -- never a raw tensor into a kernel that takes it for a normed one."""
+        p = x.pending
+        if p is None or p.applied_by(route, *geom[:3], geom[4]):
+            return x
+        return self._gn_act(p.src, p.gn, p.act, p.src2)
+
+    def _conv3x3(self, route, x, wt, bias, y, geom, then_norm, ep):
+        """_conv on one of CONV3X3_ROUTES: the filter bank, the epilogue with what rides beside it, one launch."""
         form = route.form(*geom)
+        # the transformed filter bank is cached beside the panel; the entry keeps `wt` so that its id cannot be reused while it lives
         bank = self._packed.setdefault(route.bank, {})
         key = (id(wt), *form.values()) if form else id(wt)
         if key not in bank:
-            bank[key] = (wt, getattr(_lib, route.pack)(wt, cin, cout, **form))
+            bank[key] = (wt, getattr(_lib, route.pack)(wt, *geom[3:], **form))
         # the fused tail takes bias and the per-image bias only: an activation or a scale in front of the norm stays two launches
-        if (fuse_gn is not None and pending is None and route.name == "wino1d" and _lib.conv2d_wino1d_gn_ok(*geom, fuse_gn[0].num_groups)
-                and not (set(ep) - {"rowbias", "ld_rowbias", "rows_per_group"})):
-            gn, act = fuse_gn
-            epilogue = _lib.with_groupnorm(_lib.make_epilogue(bias=bias, **ep), gn.num_groups, gn.weight.detach(), gn.bias.detach(), gn.eps, act)
-            getattr(_lib, route.launch)(x.buf, bank[key][1], y.buf, *geom, epilogue=epilogue, **form)
-            y.norm = (gn, (cout // gn.num_groups) * OH * OW, 1.0, False)     # what _gn_act sets: the consumer may run on fp16 pairs
-            return y, True
-        if stats or fuse_gn is not None:
+        fused = (isinstance(then_norm, tuple) and x.pending is None and route.name == "wino1d"
+                 and _lib.conv2d_wino1d_gn_ok(*geom, then_norm[0].num_groups) and not (set(ep) - {"rowbias", "ld_rowbias", "rows_per_group"}))
+        if then_norm and not fused:
             self._colstats(y, getattr(_lib, route.split)(*geom), ep)
         epilogue = _lib.make_epilogue(bias=bias, **ep)
-        if pending is not None:
-            two = pending.src2 is not None
-            epilogue = _lib.with_normload(epilogue, pending.coef, pending.act, pending.src2.buf if two else None, pending.src.C if two else None)
+        if fused:
+            gn, act = then_norm
+            epilogue = _lib.with_groupnorm(epilogue, gn.num_groups, gn.weight.detach(), gn.bias.detach(), gn.eps, act)
+            y.norm = NormedBy.of(gn, y.C, y.H * y.W)
+        elif x.pending is not None:
+            p = x.pending
+            epilogue = _lib.with_normload(epilogue, p.coef, p.act, *((None, None) if p.src2 is None else (p.src2.buf, p.src.C)))
         getattr(_lib, route.launch)(x.buf, bank[key][1], y.buf, *geom, epilogue=epilogue, **form)
-        return (y, False) if fuse_gn is not None else y
+        return y
 
     def _conv_gn_act(self, x, wt, bias, gn, act, mod=None, next_cout=None, **conv_args):
         """3x3 conv followed by GroupNorm ``gn`` (+ modulation ``mod``) + activation, the convolution's output read by nothing else
@@ -281,96 +314,62 @@ class NhwcExecutor(HipScoreModel):
         convolution with column sums and _gn_act, as two launches.  ``next_cout``: the norm's only reader is a 3x3 convolution to that many
         channels (_gn_act's ``conv_cout``: on 32-pixel rows that convolution's loader applies the norm)."""
         if mod is not None:
-            return self._gn_act(self._conv(x, wt, bias, stats=True, **conv_args), gn, act, mod=mod)
-        y, fused = self._conv(x, wt, bias, fuse_gn=(gn, act), **conv_args)
-        return y if fused else self._gn_act(y, gn, act, conv_cout=next_cout)
+            return self._gn_act(self._conv(x, wt, bias, then_norm=True, **conv_args), gn, act, mod=mod)
+        y = self._conv(x, wt, bias, then_norm=(gn, act), **conv_args)
+        return y if y.is_normed else self._gn_act(y, gn, act, conv_cout=next_cout)
 
-    def _pointwise(self, x, w, bias, stats=False, **ep):
-        """1x1 conv / NIN on NHWC = plain GEMM over [B*HW, Cin]; w is [Cout, Cin]."""
-        B = x.buf.shape[0]
-        cout, cin = w.shape
-        assert cin == x.C, (cin, x.C)
-        y = self._new(B, x.H, x.W, cout, x.buf)
-        if stats:
-            self._colstats(y, _lib.gemm_colstats_split(B * x.H * x.W, cout, cin, cin, w.stride(0), x.H * x.W), ep)
-        _lib.gemm(x.buf.view(-1, cin), w, out=y.buf.view(-1, cout), epilogue=_lib.make_epilogue(bias=bias, **ep))
-        return y
-
-    def _pointwise_pairs(self, pk, x, w, bias, act_scale, stats=False, **ep):
-        """_pointwise on fp16 pairs for an activation that is NOT a GroupNorm's output but whose scale is known: ``act_scale`` = device
+    def _pointwise(self, x, w, bias, stats=False, pairs=None, **ep):
+        """1x1 conv / NIN on NHWC = plain GEMM over [B*HW, Cin]; w is [Cout, Cin].  ``pairs=(pk, act_scale)``: on fp16 pairs where that
+        GEMM serves the shape, for an activation that is NOT a GroupNorm's output but whose scale is known: ``act_scale`` = device
         {s, 1 / s} (the attention output is a convex combination of the rows of v: never beyond v's range, so v's scale serves)."""
         B = x.buf.shape[0]
         cout, cin = w.shape
+        assert cin == x.C, (cin, x.C)
         M = B * x.H * x.W
-        if not _lib.gemm_pairs_ok(M, cout, cin):
-            return self._pointwise(x, w, bias, stats=stats, **ep)
+        on_pairs = pairs is not None and _lib.gemm_pairs_ok(M, cout, cin)
         y = self._new(B, x.H, x.W, cout, x.buf)
         if stats:
             self._colstats(y, _lib.gemm_colstats_split(M, cout, cin, cin, w.stride(0), x.H * x.W), ep)
-        _lib.gemm_pairs(x.buf.view(-1, cin), w, _lib._pairs_scale_of(pk, w), y.buf.view(-1, cout),
-                        epilogue=_lib.make_epilogue(bias=bias, **ep), act_scale=act_scale)
+        a, out = x.buf.view(-1, cin), y.buf.view(-1, cout)
+        if on_pairs:
+            _lib.gemm_pairs(a, w, _lib._pairs_scale_of(pairs[0], w), out, epilogue=_lib.make_epilogue(bias=bias, **ep), act_scale=pairs[1])
+        else:
+            _lib.gemm(a, w, out=out, epilogue=_lib.make_epilogue(bias=bias, **ep))
         return y
 
-    def _attention(self, pk, x, n, gn, wqk, bqk, wv, bv, wo, bo, cache, key, out_scale=1.0, heads=1):
-        """Self-attention over ``n`` = GroupNorm ``gn`` of ``x``: q|k projection (``wqk`` [2C, C], the two stacked), V^T,
+    def _attention(self, pk, x, n, wqk, bqk, wv, bv, wo, bo, cache, key, out_scale=1.0, heads=1):
+        """Self-attention over ``n`` = a GroupNorm of ``x``: q|k projection (``wqk`` [2C, C], the two stacked), V^T,
         softmax(q k^T / sqrt(D)) v per head, output projection, (+ x) * out_scale.  The V bias is added after P.V (the rows of P sum
         to one), so V^T is produced directly in the K-contiguous layout that product wants.  ``cache[key]``: the operands' power-of-two
-        scales, kept as long as the weights.  ``heads`` > 1: head h owns rows [h D, (h + 1) D) of each of q, k (the halves of ``wqk``)
-        and v, D = C / heads -- the callers permute their projection into that order at pack time (_attention_heads)."""
-        if heads != 1:
-            return self._attention_heads(pk, x, n, gn, wqk, bqk, wv, bv, wo, bo, cache, key, out_scale, heads)
+        scales, kept as long as the weights.  Head h owns rows [h D, (h + 1) D) of each of q, k (the halves of ``wqk``) and v,
+        D = C / heads -- the callers permute their projection into that order at pack time; the projections do not know the heads.
+        In between, ONE launch with the logits never written (csrc/attention.hip) where the norm is admitted to fp16 pairs and the
+        kernel serves the shape: ``attention256`` for one head, the streaming ``attention_heads`` for more.  Otherwise
+        the three-launch form once per head on column views of the same buffers."""
         B, HW, C = x.buf.shape[0], x.H * x.W, x.C
-        pairs = self.pairs_admissible(gn, n.norm[1], transform=False)
+        D = C // heads
+        gn = n.norm.gn
+        pairs = self._pairs_ok(n.norm, transform=False, gain=1.0, modulated=False)     # the projections read the norm's own output
         dev = x.buf.device
         qk = torch.empty(B * HW, 2 * C, device=dev, dtype=torch.float32)
         _lib.gemm_normed(pk, n.buf.view(-1, C), wqk, qk, epilogue=_lib.make_epilogue(bias=bqk), pairs=pairs)    # n: a GroupNorm's output
         # V^T[b] = Wv^T-panel [C, Cin] x n[b]^T -> [C, HW], K-contiguous for the P.V product (bias deferred)
         vt = torch.empty(B, C, HW, device=dev, dtype=torch.float32)
         _lib.gemm_weight_times_normed_t(pk, wv, n.buf, vt, B, HW, C, pairs=pairs)
-        mixed = torch.empty(B, HW, C, device=dev, dtype=torch.float32)
-        scale = float(C) ** (-0.5)                # BeatGANs: (q * s) . (k * s) with s = ch^-1/4  ==  q . k * ch^-1/2
-        if pairs and _lib.attention256_ok(B, HW, C):
-            # QK^T -> softmax -> PV in one launch, the logits never written (csrc/attention.hip); the operands' power-of-two scales from
-            # the projections' row norms (their input n has unit variance times gamma's scale)
+        mixed = _T(torch.empty(B, HW, C, device=dev, dtype=torch.float32), x.H, x.W, C)
+        scale = float(D) ** (-0.5)                # BeatGANs: (q * s) . (k * s) with s = D^-1/4 (BeatGANsblocks.py:482, :517)
+        if pairs and (_lib.attention256_ok(B, HW, C) if heads == 1 else _lib.attention_heads_ok(B, HW, heads, D)):
+            # the operands' power-of-two scales from the projections' row norms (their input n has unit variance times gamma's scale)
             if key not in cache:
                 gam = float(torch.sqrt((gn.weight.detach().double() ** 2).mean() + (gn.bias.detach().double() ** 2).mean()))
                 cache[key] = (_lib.pairs_scale_from_rows(wqk, bqk, gam), _lib.pairs_scale_from_rows(wv, bv, gam))
             s_qk, s_v = cache[key]
-            _lib.attention256(qk, vt, mixed, B, C, s_qk, s_v, scale, bias_v=bv)
-            return self._pointwise_pairs(pk, _T(mixed, x.H, x.W, C), wo, bo, s_v, residual=x.buf, out_scale=out_scale, stats=True)
-        logits = torch.empty(B, HW, HW, device=dev, dtype=torch.float32)
-        _lib.gemm(qk, qk[:, C:], out=logits, M=HW, N=HW, K=C, lda=2 * C, ldb=2 * C, ldc=HW, batch=B,
-                  stride_a=HW * 2 * C, stride_b=HW * 2 * C, stride_c=HW * HW)
-        _lib.softmax_rows(logits, logits, B * HW, HW, scale)
-        _lib.gemm(logits, vt, out=mixed, M=HW, N=C, K=HW, lda=HW, ldb=HW, ldc=C, batch=B,
-                  stride_a=HW * HW, stride_b=C * HW, stride_c=HW * C, epilogue=_lib.make_epilogue(bias=bv))
-        return self._pointwise(_T(mixed, x.H, x.W, C), wo, bo, residual=x.buf, out_scale=out_scale, stats=True)
-
-    def _attention_heads(self, pk, x, n, gn, wqk, bqk, wv, bv, wo, bo, cache, key, out_scale, heads):
-        """_attention with more than one head.  The projections and the output projection are the single-head block's (the heads are
-        column ranges of their outputs / input).  Where the streaming kernel serves the shape (csrc/attention.hip,
-        attention_heads_kernel: heads of 32 / 64 / 128 channels over a multiple of 64 tokens -- every class measured faster than the
-        per-head form, profiles/attention_heads_bench.txt) the heads run as ONE launch, the logits never written; otherwise (the
-        16-token middle block, other widths, norms not admitted to fp16 pairs, the safe rebuild under IDIFF_NO_PAIRS) as the
-        three-launch form once per head on column views of the same buffers."""
-        B, HW, C = x.buf.shape[0], x.H * x.W, x.C
-        D = C // heads
-        pairs = self.pairs_admissible(gn, n.norm[1], transform=False)
-        dev = x.buf.device
-        qk = torch.empty(B * HW, 2 * C, device=dev, dtype=torch.float32)
-        _lib.gemm_normed(pk, n.buf.view(-1, C), wqk, qk, epilogue=_lib.make_epilogue(bias=bqk), pairs=pairs)
-        vt = torch.empty(B, C, HW, device=dev, dtype=torch.float32)
-        _lib.gemm_weight_times_normed_t(pk, wv, n.buf, vt, B, HW, C, pairs=pairs)
-        mixed = torch.empty(B, HW, C, device=dev, dtype=torch.float32)
-        scale = float(D) ** (-0.5)                # (q * s) . (k * s) with s = D^-1/4 (BeatGANsblocks.py:482, :517)
-        if pairs and _lib.attention_heads_ok(B, HW, heads, D):
-            if key not in cache:
-                gam = float(torch.sqrt((gn.weight.detach().double() ** 2).mean() + (gn.bias.detach().double() ** 2).mean()))
-                cache[key] = (_lib.pairs_scale_from_rows(wqk, bqk, gam), _lib.pairs_scale_from_rows(wv, bv, gam))
-            s_qk, s_v = cache[key]
-            _lib.attention_heads(qk, vt, mixed, B, HW, heads, D, s_qk, s_v, scale, bias_v=bv)
-            return self._pointwise_pairs(pk, _T(mixed, x.H, x.W, C), wo, bo, s_v, residual=x.buf, out_scale=out_scale, stats=True)
-        if D % 4:
+            if heads == 1:
+                _lib.attention256(qk, vt, mixed.buf, B, C, s_qk, s_v, scale, bias_v=bv)
+            else:
+                _lib.attention_heads(qk, vt, mixed.buf, B, HW, heads, D, s_qk, s_v, scale, bias_v=bv)
+            return self._pointwise(mixed, wo, bo, pairs=(pk, s_v), residual=x.buf, out_scale=out_scale, stats=True)
+        if heads > 1 and D % 4:
             raise NotImplementedError(f"attention heads of {D} channels: the GEMM takes a head as a column view only where its width "
                                       "is a multiple of 4")
         logits = torch.empty(B, HW, HW, device=dev, dtype=torch.float32)
@@ -378,9 +377,9 @@ class NhwcExecutor(HipScoreModel):
             _lib.gemm(qk[:, h * D:], qk[:, C + h * D:], out=logits, M=HW, N=HW, K=D, lda=2 * C, ldb=2 * C, ldc=HW, batch=B,
                       stride_a=HW * 2 * C, stride_b=HW * 2 * C, stride_c=HW * HW)
             _lib.softmax_rows(logits, logits, B * HW, HW, scale)
-            _lib.gemm(logits, vt[:, h * D:(h + 1) * D], out=mixed[..., h * D:], M=HW, N=D, K=HW, lda=HW, ldb=HW, ldc=C, batch=B,
+            _lib.gemm(logits, vt[:, h * D:(h + 1) * D], out=mixed.buf[..., h * D:], M=HW, N=D, K=HW, lda=HW, ldb=HW, ldc=C, batch=B,
                       stride_a=HW * HW, stride_b=C * HW, stride_c=HW * C, epilogue=_lib.make_epilogue(bias=bv[h * D:(h + 1) * D]))
-        return self._pointwise(_T(mixed, x.H, x.W, C), wo, bo, residual=x.buf, out_scale=out_scale, stats=True)
+        return self._pointwise(mixed, wo, bo, residual=x.buf, out_scale=out_scale, stats=True)
 
     def _box(self, x, up):
         B = x.buf.shape[0]
