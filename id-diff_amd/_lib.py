@@ -155,6 +155,8 @@ _SIGNATURES = {
     "idiff_local_pca_ok": (c_i, [c_i, c_i, c_i, c_i]),
     "idiff_local_pca_chunk": (c_i, []),
     "idiff_local_pca_f64": (c_i, [c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
+    "idiff_simplex_skewness_ok": (c_i, [c_i, c_i, c_i, c_i]),
+    "idiff_simplex_skewness_f64": (c_i, [c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_i, c_p, c_p, c_p]),
     "idiff_empirical_score_ok": (c_i, [c_i64, c_i]),
     "idiff_empirical_score_f32": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i64, c_i, c_p]),
     "idiff_empirical_jacobian_ok": (c_i, [c_i64, c_i]),
@@ -1268,6 +1270,40 @@ def local_pca(X, centre, idx, n_vectors=0):
         raise RuntimeError(f"local_pca: {stalled} of {Q} queries reached the Jacobi sweep cap without converging, "
                            f"{outside} hold an index outside [0, {N}), {nonfinite} have a neighbourhood that is not finite (NaN or Inf in X)")
     return eig, basis
+
+
+# ------------------------------------------------------------------------------------------- simplex skewness
+def simplex_skewness(X, centre, idx, scales):
+    """Expected Simplex Skewness (d = 1) of every neighbourhood {centre[q]} + idx[q, :scales[s]] of X [N, D] (CUDA fp32,
+    contiguous; centre [Q] and idx [Q, k] int64 in ascending distance, 2 <= k <= 64; scales: 1 to 16 ints, strictly ascending,
+    2 <= scales[s] <= k): ess [Q, S, 3] fp64 = the weighted mean of |sin|, the weighted mean of |cos| and the weight sum over all
+    pairs of the rows centred on their mean (idiff_simplex_skewness_f64, one launch).  The kernel checks every index against
+    [0, N) before it reads a row.  One host sync: the per-query status, read back to raise ``RuntimeError`` naming how many
+    queries held an index out of range or met a NaN or Inf in their rows.  A scale whose rows are identical (status 4) does not
+    raise: its two means are NaN and its weight sum 0."""
+    _dev(X, "X"); _dev(centre, "centre", dtype=torch.int64); _dev(idx, "idx", dtype=torch.int64)
+    if X.ndim != 2 or centre.ndim != 1 or idx.ndim != 2 or idx.shape[0] != centre.shape[0]:
+        raise RuntimeError(f"simplex_skewness: X must be [N, D], centre [Q] and idx [Q, k], got {tuple(X.shape)}, "
+                           f"{tuple(centre.shape)} and {tuple(idx.shape)}")
+    (N, D), (Q, k) = X.shape, idx.shape
+    scales = [int(s) for s in scales]
+    S = len(scales)
+    host_scales = (c_i * max(S, 1))(*scales)
+    ess = torch.empty(Q, S, 3, dtype=torch.float64, device=X.device)
+    status = torch.empty(Q, dtype=torch.int32, device=X.device)
+    if Q == 0:                        # nothing to launch (and no pointers to pass); the sizes are still the library's to refuse
+        if not lib().idiff_simplex_skewness_ok(N, D, k, S):
+            raise RuntimeError(f"simplex_skewness: N = {N}, D = {D}, k = {k}, {S} scales not served (idiff_simplex_skewness_ok)")
+        return ess
+    _check(lib().idiff_simplex_skewness_f64(X.data_ptr(), N, D, centre.data_ptr(), idx.data_ptr(), Q, k,
+                                            ctypes.cast(host_scales, c_p), S, ess.data_ptr(), status.data_ptr(), _stream()),
+           "idiff_simplex_skewness_f64")
+    st = status.cpu()
+    outside, nonfinite = int((st == 2).sum()), int((st == 3).sum())
+    if outside or nonfinite:
+        raise RuntimeError(f"simplex_skewness: {outside} of {Q} queries hold an index outside [0, {N}), "
+                           f"{nonfinite} have a neighbourhood that is not finite (NaN or Inf in X)")
+    return ess
 
 
 # ------------------------------------------------------------------------------------------- geodesic distances (Isomap)

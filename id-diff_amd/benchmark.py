@@ -5,7 +5,8 @@ The reference fills a CSV (index ``method``: mle_5, mle_20, lpca, ppca; one colu
 (benchmark.py:57-68).  Here the estimators are module functions on the MI355X: the neighbour search of the ML
 estimators is one exact kNN (``_lib.knn``), the PCA estimators read the covariance eigenvalues of the fp64 spectrum
 kernels (``_lib.spectrum(X, return_eig=True)``); what remains is O(N k) or O(D^2) host arithmetic in fp64.
-An opt-in fifth kind of name, ``lpca_knn_<k>``, is the per-point form of lpca (``lpca.py``).
+An opt-in fifth kind of name, ``lpca_knn_<k>``, is the per-point form of lpca (``lpca.py``), and a sixth, ``ess_knn_<k>``, the
+per-point simplex skewness (``simplex.py``).
 """
 import math
 import os
@@ -177,6 +178,17 @@ def lpca_knn_k(name):
     return int(tail) if head == 'lpca_knn' and tail.isdigit() and tail.isascii() else None
 
 
+def ess_knn_k(name):
+    """k of an estimator name ``ess_knn_<k>`` (Expected Simplex Skewness over the k nearest neighbours of every point, the mean
+    over the points: ``simplex.local_dims``), or None for any other name.  Opt-in, exactly as ``lpca_knn_<k>`` is."""
+    head, _, tail = str(name).rpartition('_')
+    return int(tail) if head == 'ess_knn' and tail.isdigit() and tail.isascii() else None
+
+
+def _opt_in(name):
+    return lpca_knn_k(name) is not None or ess_knn_k(name) is not None
+
+
 # ------------------------------------------------------------------------------------------- the benchmark
 class Benchmark():
     """benchmark.py:21-91 of the reference: same constructor, CSV layout, skip-if-filled and error-tolerant loop."""
@@ -192,7 +204,7 @@ class Benchmark():
         if os.path.exists(self.file_name):
             exisiting_results = pd.read_csv(self.file_name, index_col='method')
             # opt-in rows a run before this one saved: update() fills only labels the frame has, and to_csv writes only the frame
-            self._add_rows(name for name in exisiting_results.index if lpca_knn_k(name) is not None)
+            self._add_rows(name for name in exisiting_results.index if _opt_in(name))
             self.results.update(exisiting_results)
 
     def _add_rows(self, names):
@@ -201,9 +213,9 @@ class Benchmark():
                 self.results.loc[name] = np.nan
 
     def _add_opt_in_rows(self):
-        """The rows of the ``lpca_knn_<k>`` names in ``self.estimators`` (appended after the constructor built the frame of the four
+        """The rows of the ``lpca_knn_<k>`` and ``ess_knn_<k>`` names in ``self.estimators`` (appended after the constructor built the frame of the four
         defaults), so that the filled-already tests below see them."""
-        self._add_rows(name for name in self.estimators if lpca_knn_k(name) is not None)
+        self._add_rows(name for name in self.estimators if _opt_in(name))
 
     def run(self):
         print('--------- STARTING BENCHMARK -----------')
@@ -224,8 +236,8 @@ class Benchmark():
             print(f'------ Benchmarking on dataset {dataset_name} completed --------')
 
     def evaluate_estimator(self, data, estimator_type, dataset_name):
-        knn_k = lpca_knn_k(estimator_type)
-        if knn_k is not None:
+        knn_k, ess_k = lpca_knn_k(estimator_type), ess_knn_k(estimator_type)
+        if knn_k is not None or ess_k is not None:
             self._add_rows([estimator_type])                    # an opt-in name: its row is not in the frame of the defaults
         if pd.isna(self.results[dataset_name].loc[estimator_type]):
             print(f'{estimator_type} on {dataset_name} START')
@@ -240,6 +252,9 @@ class Benchmark():
             elif knn_k is not None:
                 from . import lpca
                 estimated_dim = float(lpca.local_dims(data, knn_k).mean())
+            elif ess_k is not None:
+                from . import simplex
+                estimated_dim = float(simplex.local_dims(data, ess_k).mean())
             else:
                 raise ValueError(f"unknown estimator {estimator_type!r}")
             self.results.loc[estimator_type, dataset_name] = estimated_dim

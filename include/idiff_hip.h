@@ -727,6 +727,36 @@ int idiff_local_pca_chunk(void);
 int idiff_local_pca_f64(const float *X, int N, int D, const int64_t *centre, const int64_t *idx, int Q, int k, int n_vec,
                         double *eig, double *basis, int *status, void *stream);
 
+/* ------------------------------------------------------------------ simplex skewness: per-point ID across neighbourhood sizes */
+
+/* Expected Simplex Skewness with d = 1 (Johnsson, Soneson and Fontes 2015; the reference's R package has it as essLocalDimEst; no
+ * reference counterpart in code).  Query q has a centre row centre[q] and k neighbour rows idx[q, :] of X [N, D] fp32 (row-major,
+ * contiguous), the neighbours in ascending distance as idiff_knn_f32 writes them, so that the neighbourhood of size k' <= k is the
+ * centre and the first k' columns.  y_j = x_j - x_centre is formed in fp64 before any product and G = Y Y^T over the m = k + 1 rows
+ * on v_mfma_f64_16x16x4_f64, D streamed through LDS in chunks, exactly as idiff_local_pca_f64 does.  Then, for every scale
+ * k' = scales[s] with m' = k' + 1, on the leading m' x m' block of G: B = J G J, J = I - 1 1^T / m' (the Gram matrix of the rows
+ * centred on their own mean: B_ij = G_ij - (r_i + r_j) + g with the block's row means r and grand mean g summed in a fixed order), and
+ * over all pairs i < j < m'
+ *     ess[q, s, 0] = sum sqrt(max(0, B_ii B_jj - B_ij^2)) / W     the weighted mean of |sin| of the angle between two centred rows
+ *     ess[q, s, 1] = sum |B_ij| / W                               the weighted mean of |cos|
+ *     ess[q, s, 2] = W = sum sqrt(B_ii) sqrt(B_jj)                the weight sum
+ * One workgroup per query, one launch, no atomics, no host synchronisation, no allocation, no workspace; nothing [m, D] or [m, m]
+ * is written to HBM.  The bits of ess[q, s, :] depend on the query's first scales[s] + 1 rows alone: not on k, not on the other
+ * scales of the list, not on Q or on the other queries of the launch.
+ *
+ * scales: HOST array of S neighbourhood sizes, strictly ascending, 2 <= scales[s] <= k (read before the launch, not kept).
+ * ess [Q, S, 3] fp64.  status [Q] int32: 0 served; 2 an index of the query lies outside [0, N): THE KERNEL CHECKS every index before
+ * it reads a row of X, so the caller need not; the query's ess is NaN; 3 a value of the query's k + 1 rows is not finite (or |y_j|^2
+ * overflows): ess is NaN at every scale; 4 at least one scale has W = 0 exactly (its rows are identical): that scale's two means are
+ * NaN and its W is 0, the other scales are served.
+ *
+ * Needs 1 <= N, 1 <= D, 2 <= k <= 64, 1 <= S <= 16, 0 <= Q, the scales as above and non-null pointers (IDIFF_EINVAL otherwise,
+ * nothing launched; Q = 0 is a no-op).  idiff_simplex_skewness_ok (host only) = 1 where the sizes are served.  centre [Q] and
+ * idx [Q, k] are int64, as idiff_knn_f32 writes them. */
+int idiff_simplex_skewness_ok(int N, int D, int k, int S);
+int idiff_simplex_skewness_f64(const float *X, int N, int D, const int64_t *centre, const int64_t *idx, int Q, int k,
+                               const int *scales, int S, double *ess, int *status, void *stream);
+
 /* ------------------------------------------------------------------ score of the empirical distribution of a point cloud */
 
 /* The N points x_i of a cloud, each with weight 1 / N, convolved with N(0, sigma^2 I) -- exact for any finite data set, no training:
