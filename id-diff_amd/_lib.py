@@ -1061,7 +1061,7 @@ def sym_band(G, dense=True):
     band[j, k] = B[j + k, j], for timing."""
     _dev(G, "G", dtype=torch.float64)
     D = G.shape[0]
-    scratch = torch.zeros(lib().idiff_symtridiag_scratch_doubles(D), dtype=torch.float64, device=G.device)
+    scratch = torch.empty(lib().idiff_symtridiag_scratch_doubles(D), dtype=torch.float64, device=G.device)   # stage 1 writes the band AND its bulge room
     _check(lib().idiff_symband_f64(G.data_ptr(), D, scratch.data_ptr(), _stream()), "idiff_symband_f64")
     ld = lib().idiff_symband_ld()
     band = scratch[:D * ld].view(D, ld)                       # band[j, k] = B[j + k, j]

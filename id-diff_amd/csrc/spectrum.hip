@@ -469,6 +469,7 @@ __global__ void tridiag_tail_kernel(const double *__restrict__ A, int D, double 
     offd[D - 2] = A[(int64_t)(D - 2) * D + (D - 1)];
   }
   diag[D - 1] = A[(int64_t)(D - 1) * D + (D - 1)];
+  offd[D - 1] = 0.0;                                    // the entry nothing reads: written like every other path writes it
 }
 
 

@@ -14,6 +14,13 @@
  *     gives a thread-local message.
  *   - "Replaces" names the reference interface (file:line under GBATZOLIS/ID-diff)
  *     that the entry point stands in for.
+ *   - Buffers.  What a scratch buffer or workspace holds on entry is unspecified: every word a kernel reads from it has been
+ *     written by the same call (a kernel before it, or a memset on the stream).  Its size is exactly what the query beside the
+ *     entry point returns (idiff_*_scratch_doubles, idiff_*_workspace_bytes, or the count stated in the comment); nothing is
+ *     written beyond it.  What it holds on return is unspecified too, unless the comment says otherwise.  Every element of
+ *     every output is written on a return of 0, whatever the call computes for it (a refused query, a failed solve), unless
+ *     the comment names the elements that are not; an operand that is "only read" comes back bit for bit.
+ *     tests/test_hip_buffer_contract.py holds the fp64 / neighbour-search / graph launchers to this.
  */
 #ifndef IDIFF_HIP_H
 #define IDIFF_HIP_H
@@ -532,7 +539,8 @@ int idiff_symmetrize_upper_f64(double *G, int D, void *stream);
  * scratch: idiff_symtridiag_scratch_doubles(D) doubles (shared by the P matrices, which are processed in turn). */
 int64_t idiff_symtridiag_scratch_doubles(int D);
 /* stage 1 alone (D > 128): on return the first D * idiff_symband_ld() doubles of scratch hold the lower band,
- * band[j * ld + k] = B[j + k][j], k <= 32 (the rest of a column is bulge room, zero). */
+ * band[j * ld + k] = B[j + k][j], k <= 32 (the rest of a column is bulge room, zero: the kernel that extracts the band writes it,
+ * and the two zero columns behind the band, whatever the scratch held). */
 int idiff_symband_ld(void);
 int idiff_symband_f64(double *G, int D, double *scratch, void *stream);
 int idiff_symtridiag_f64(double *G, int P, int D, double *diag, double *offdiag, double *scratch, void *stream);
@@ -541,6 +549,9 @@ int idiff_symtridiag_f64(double *G, int P, int D, double *diag, double *offdiag,
  * ceil(D / 32) mutually waiting workgroups exceed HALF of what the device can hold resident -- asked of the
  * runtime per device -- or IDIFF_CHASE_WAVEFRONT is set), 3 one-stage sweep (IDIFF_TRIDIAG_ONESTAGE). */
 int idiff_symtridiag_plan(int D);
+/* diag, offdiag [P][D] -> eig [P][D] ascending.  offdiag[p][i] couples rows i and i + 1, so offdiag[p][D - 1] is the unused entry:
+ * idiff_symtridiag_f64 writes 0 there on every path, idiff_tridiag_eigvals_f64 never reads it (any value, a NaN too, changes nothing).
+ * A NaN or Inf in any entry that IS read turns the matrix's D eigenvalues into NaN. */
 int idiff_tridiag_eigvals_f64(const double *diag, const double *offdiag, int P, int D, double *eig, void *stream);
 
 /* The tangent side of the spectrum: T [D, k] row-major with orthonormal columns spanning the invariant subspace of the k SMALLEST
