@@ -55,6 +55,8 @@ _SIGNATURES = {
     "idiff_gemm_f32": (c_i, [c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_i, c_i, c_i, c_i,
                              ctypes.POINTER(Epilogue), c_p]),
     "idiff_gemm_2src_f32": (c_i, [c_p, c_p, c_i64, c_i, c_p, c_i64, c_p, c_i64, c_i, c_i, c_i, ctypes.POINTER(Epilogue), c_p]),
+    "idiff_gemm_2src_ld_f32": (c_i, [c_p, c_i64, c_p, c_i64, c_i, c_p, c_i64, c_p, c_i64, c_i, c_i, c_i, ctypes.POINTER(Epilogue), c_p]),
+    "idiff_gemm_2src_ld_ok": (c_i, [c_i, c_i]),
     "idiff_conv2d_nhwc_f32": (c_i, [c_p, c_p, c_p] + [c_i] * 10 + [ctypes.POINTER(Epilogue), c_p]),
     "idiff_gemm_route": (ctypes.c_char_p, [c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_i, c_i, c_i, c_i,
                                            ctypes.POINTER(Epilogue), c_i]),
@@ -76,6 +78,8 @@ _SIGNATURES = {
     "idiff_winograd43h_pack_f32": (c_i, [c_p, c_p, c_i, c_i, c_p]),
     "idiff_conv2d_winograd43h_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(Epilogue), c_p]),
     "idiff_conv2d_wino1d_ok": (c_i, [c_i] * 5),
+    "idiff_conv2d_wino1d_resup_ok": (c_i, [c_i] * 5),
+    "idiff_conv2d_wino1d_resup_f32": (c_i, [c_p, c_p, c_p] + [c_i] * 5 + [ctypes.POINTER(Epilogue), c_p, ctypes.POINTER(ctypes.c_float), c_p]),
     "idiff_conv2d_wino1d_colstats_split": (c_i, [c_i] * 5),
     "idiff_wino1d_weight_floats": (c_i64, [c_i, c_i]),
     "idiff_wino1d_pack_f32": (c_i, [c_p, c_p, c_i, c_i, c_p]),
@@ -350,6 +354,41 @@ def with_normload(ep, coef, act, x2=None, C1=None):
     return ep
 
 
+class ResidualUp2(NamedTuple):
+    """The upsampled-residual request of with_residual_up2."""
+    lo: torch.Tensor
+    taps: tuple
+
+
+def polyphase_up2(k, pad0, pad1):
+    """The 16 polyphase weights w[a][b][u][v] (flattened) of upfirdn2d(x, k, up=2, pad=(pad0, pad1)) with a 4 x 4 kernel ``k``: output pixel
+    (2 i + a, 2 j + b) = sum over u, v of x[i - 1 + a + u][j - 1 + b + v] * w[a][b][u][v], samples outside x counting as zero.  Pure host
+    arithmetic in fp64 on the kernel as given: zero insertion leaves every second sample, so of the four taps of the FLIPPED kernel along
+    an axis a phase meets two, t = a + 2 u, at input offset (a + t - pad0) / 2 = a + u - 1."""
+    k = [[float(v) for v in row] for row in (k.tolist() if hasattr(k, "tolist") else k)]
+    if len(k) != 4 or any(len(row) != 4 for row in k):
+        raise RuntimeError("polyphase_up2: a 4 x 4 kernel is expected")
+    if (pad0, pad1) != (2, 1):
+        raise RuntimeError(f"polyphase_up2: pads (2, 1) are expected (upsample_2d with a 4-tap kernel), got ({pad0}, {pad1})")
+    flipped = lambda t, s: k[3 - t][3 - s]
+    return tuple(flipped(a + 2 * u, b + 2 * v) for a in (0, 1) for b in (0, 1) for u in (0, 1) for v in (0, 1))
+
+
+def with_residual_up2(ep, lo, taps):
+    """Ask the convolution that consumes ``ep`` to add the residual ``lo`` [B, (H/2) * (W/2), Cout] (fp32, 16-byte aligned, pitch Cout)
+    upsampled x2 by the FIR whose 16 polyphase weights are ``taps`` (polyphase_up2), where a plain residual would be added: the
+    full-resolution residual is never written.  Rides beside the C struct as with_groupnorm's request does (``ep.residual_up2``);
+    conv2d_wino1d serves it through idiff_conv2d_wino1d_resup_f32 (ask conv2d_wino1d_resup_ok), every other wrapper refuses it."""
+    _dev(lo, "lo")
+    taps = tuple(float(t) for t in taps)
+    if len(taps) != 16:
+        raise RuntimeError(f"with_residual_up2: 16 polyphase weights are expected, got {len(taps)}")
+    if ep.residual:
+        raise RuntimeError("with_residual_up2: the epilogue already carries a residual")
+    ep.residual_up2 = ResidualUp2(lo, taps)
+    return ep
+
+
 def _ep_ref(epilogue, what):
     """The epilogue argument of a launch that has no fused GroupNorm: such a request is an error, never dropped."""
     if epilogue is None:
@@ -358,6 +397,8 @@ def _ep_ref(epilogue, what):
         raise RuntimeError(f"{what}: the epilogue asks for a GroupNorm in the loader (with_normload), which only conv2d_wino1d serves")
     if getattr(epilogue, "groupnorm", None) is not None:
         raise RuntimeError(f"{what}: the epilogue asks for a fused GroupNorm (with_groupnorm), which only conv2d_wino1d serves")
+    if getattr(epilogue, "residual_up2", None) is not None:
+        raise RuntimeError(f"{what}: the epilogue asks for an upsampled residual (with_residual_up2), which only conv2d_wino1d serves")
     return ctypes.byref(epilogue)
 
 
@@ -552,16 +593,23 @@ def gemm_weight_times_normed_t(cache, w, x, out, B, HW, C, pairs=True):
 
 
 def gemm_2src(a1, a2, bt, out, epilogue=None):
-    """out = epilogue([a1 | a2] @ bt.T) for two [M, K/2]-shaped sources of equal row pitch (concatenation never formed)."""
+    """out = epilogue([a1 | a2] @ bt.T) for two sources [M, K1] and [M, K2], each with its own row pitch (concatenation never
+    formed).  K1 % 32 == 0, K2 % 4 == 0."""
     _dev(a1, "a1"); _dev(a2, "a2"); _dev(bt, "bt"); _dev(out, "out")
     M, K1 = a1.shape
     K = K1 + a2.shape[1]
-    if a2.shape[0] != M or a1.stride(0) != a2.stride(0) or bt.shape[1] != K:
+    if a2.shape[0] != M or bt.shape[1] != K:
         raise RuntimeError(f"gemm_2src: shapes {tuple(a1.shape)} | {tuple(a2.shape)} x {tuple(bt.shape)}^T")
     ep = _ep_ref(epilogue, "gemm_2src")
-    _check(lib().idiff_gemm_2src_f32(a1.data_ptr(), a2.data_ptr(), a1.stride(0), K1, bt.data_ptr(), bt.stride(0), out.data_ptr(),
-                                     out.stride(0), M, bt.shape[0], K, ep, _stream()), "idiff_gemm_2src_f32")
+    _check(lib().idiff_gemm_2src_ld_f32(a1.data_ptr(), a1.stride(0), a2.data_ptr(), a2.stride(0), K1, bt.data_ptr(), bt.stride(0),
+                                        out.data_ptr(), out.stride(0), M, bt.shape[0], K, ep, _stream()), "idiff_gemm_2src_ld_f32")
     return out
+
+
+def gemm_2src_ld_ok(K1, K2):
+    """Whether the executor takes gemm_2src for sources of K1 and K2 columns with different row pitches (K1 % 32 == 0, K2 % 4 == 0);
+    no under IDIFF_NO_2SRC_PITCH and IDIFF_NO_PIPE.  Launches nothing."""
+    return bool(lib().idiff_gemm_2src_ld_ok(K1, K2))
 
 
 def conv2d_nhwc(x, wt, out, B, H, W, Cin, Cout, KH, KW, stride, pad, epilogue=None, pad_hi=None):
@@ -612,6 +660,17 @@ def _wino_conv(stem, packed_by, x, u, out, B, H, W, Cin, Cout, epilogue):
         raise RuntimeError(f"conv2d_{stem}: a filter bank of {u.numel()} floats ({want} expected): pack it with {packed_by}")
     gn = getattr(epilogue, "groupnorm", None)
     nl = getattr(epilogue, "normload", None)
+    ru = getattr(epilogue, "residual_up2", None)
+    if ru is not None and stem == "wino1d":
+        if gn is not None or nl is not None:
+            raise RuntimeError("conv2d_wino1d: the upsampled residual (with_residual_up2) cannot be combined with a fused GroupNorm "
+                               "(with_groupnorm) or one in the loader (with_normload)")
+        if ru.lo.numel() != B * (H // 2) * (W // 2) * Cout:
+            raise RuntimeError(f"conv2d_wino1d: a low-resolution residual of {ru.lo.numel()} floats for [B, (H/2)(W/2), Cout] = "
+                               f"[{B}, {(H // 2) * (W // 2)}, {Cout}]")
+        _check(lib().idiff_conv2d_wino1d_resup_f32(x.data_ptr(), u.data_ptr(), out.data_ptr(), B, H, W, Cin, Cout, ctypes.byref(epilogue),
+                                                   ru.lo.data_ptr(), (ctypes.c_float * 16)(*ru.taps), _stream()), "idiff_conv2d_wino1d_resup_f32")
+        return out
     if nl is not None and stem == "wino1d":
         if gn is not None:
             raise RuntimeError("conv2d_wino1d: a GroupNorm in the loader (with_normload) and one in the tail (with_groupnorm) in one launch")
@@ -697,6 +756,12 @@ def conv2d_wino1d_gn_ok(B, H, W, Cin, Cout, groups):
     """True when conv2d_wino1d also applies the GroupNorm (``groups`` groups) + activation behind it (with_groupnorm): maps of at most 256
     pixels in rows of at most 16, group widths that divide 64; off under IDIFF_NO_FUSED_GN and wherever conv2d_wino1d_ok is."""
     return bool(lib().idiff_conv2d_wino1d_gn_ok(B, H, W, Cin, Cout, groups))
+
+
+def conv2d_wino1d_resup_ok(B, H, W, Cin, Cout):
+    """True where conv2d_wino1d adds a residual given at half the resolution, upsampled x2 in its tail (with_residual_up2): rows of 8, 16 or
+    32 pixels, even H; off under IDIFF_NO_FUSED_RES_UP and wherever conv2d_wino1d_ok is."""
+    return bool(lib().idiff_conv2d_wino1d_resup_ok(B, H, W, Cin, Cout))
 
 
 def conv2d_wino1d_normload_ok(B, H, W, Cin, Cout):

@@ -49,9 +49,10 @@ struct IgemmParams {
   int has_ep;
   uint32_t a_bytes, b_bytes;  // extent of one batch slice of A / Bt for the buffer-addressed kernel
   int vec_ep;                 // epilogue operands allow 16-byte accesses (set by the launcher)
-  const float *A2;            // LINEAR, optional: columns K1.. of A live in a second matrix with the same row pitch
+  const float *A2;            // LINEAR, optional: columns K1.. of A live in a second matrix with its own row pitch lda2
   int K1;                     // (the concatenation [A | A2] is never materialised); 0 = single source
   uint32_t a2_bytes;
+  int64_t lda2;
   uint32_t c_bytes, res_bytes;  // extents of one batch slice of C and of the residual; buf_ep = they fit a buffer descriptor
   int buf_ep;
   const float *scale_a, *scale_b;   // fp16-pair form: device pointers to {s, 1 / s}, the power of two A / Bt is multiplied by before
@@ -389,10 +390,12 @@ igemm_pipe_kernel(const IgemmParams p) {
   const int row_base = tid >> 3;
 
   uint32_t a_base[A_PER_T], a_mask[A_PER_T];
+  uint32_t a2_base[A_PER_T];   // LINEAR: the same rows at the second source's pitch
 #pragma unroll
   for (int i = 0; i < A_PER_T; ++i) {
     const int m = m0 + row_base + i * ROW_STEP;
     const bool ok = m < p.M;
+    a2_base[i] = 0;
     if (CONV) {
       const int mm = ok ? m : 0;
       const int ox = mm % p.OW;
@@ -412,6 +415,7 @@ igemm_pipe_kernel(const IgemmParams p) {
       a_mask[i] = mask;
     } else {
       a_base[i] = (uint32_t)((int64_t)m * p.lda + kc) * 4u;
+      a2_base[i] = (uint32_t)((int64_t)m * p.lda2 + kc) * 4u;
       a_mask[i] = ok ? 1u : 0u;
     }
   }
@@ -460,13 +464,13 @@ igemm_pipe_kernel(const IgemmParams p) {
       if (++f_kx == p.KW) { f_kx = 0; ++f_ky; }
       if (f_tap == ntaps) { f_tap = 0; f_kx = 0; f_ky = 0; f_c0 += BK; }
     } else {
-      // wave-uniform choice of the source (columns K1.. live in the second matrix, same row offsets): a select of the
-      // descriptor, not a branch -- the k-tile body stays one basic block, which the interleaving below needs
+      // wave-uniform choice of the source (columns K1.. live in the second matrix, at its own row offsets): a select of the
+      // descriptor and of the row offsets, not a branch -- the k-tile body stays one basic block, which the interleaving below needs
       const bool second = p.K1 > 0 && f_kt * BK >= p.K1;
       const __amdgpu_buffer_rsrc_t rS = second ? rA2 : rA;
       const uint32_t koff = (uint32_t)(f_kt * BK - (second ? p.K1 : 0)) * 4u;
 #pragma unroll
-      for (int i = 0; i < A_PER_T; ++i) a_reg[i] = buf_load4(rS, (a_mask[i] && kok) ? a_base[i] + koff : OOB);
+      for (int i = 0; i < A_PER_T; ++i) a_reg[i] = buf_load4(rS, (a_mask[i] && kok) ? (second ? a2_base[i] : a_base[i]) + koff : OOB);
     }
 #pragma unroll
     for (int i = 0; i < B_PER_T; ++i) b_reg[i] = buf_load4(rB, (b_ok[i] && kok) ? b_base[i] + koffb : OOB);
@@ -1062,13 +1066,14 @@ int igemm_run(IgemmParams &p, int batch, int want, hipStream_t st, IgemmPlan *pr
 // the colstats queries at the end of the file, which decide whether the executor allocates column sums at all, ask nothing else.
 enum PipeServes { PIPE_NO, PIPE_YES, PIPE_A_BEYOND };   // the last: only A exceeds one buffer descriptor -- what the host cut is for
 bool pitches16(int K, int64_t lda, int64_t ldb) { return K % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0; }   // every row starts a 16-byte load
-// K1: the split column of two sources with one pitch, which extend as far as their K1 and K - K1 columns
-int pipe_fits_linear(int M, int N, int K, int64_t lda, int64_t ldb, int K1 = 0) {
-  if (!pitches16(K, lda, ldb) || extent_bytes(N, ldb, K) >= BUF_LIMIT) return PIPE_NO;
-  return extent_bytes(M, lda, K1 > K - K1 ? K1 : K - K1) < BUF_LIMIT ? PIPE_YES : PIPE_A_BEYOND;
+// K1: the split column of two sources, which extend as far as their K1 columns at pitch lda and their K - K1 columns at pitch lda2
+int pipe_fits_linear(int M, int N, int K, int64_t lda, int64_t ldb, int K1 = 0, int64_t lda2 = 0) {
+  if (K1 == 0) lda2 = lda;
+  if (!pitches16(K, lda, ldb) || lda2 % 4 || extent_bytes(N, ldb, K) >= BUF_LIMIT) return PIPE_NO;
+  return extent_bytes(M, lda, K1 ? K1 : K) < BUF_LIMIT && extent_bytes(M, lda2, K - K1) < BUF_LIMIT ? PIPE_YES : PIPE_A_BEYOND;
 }
-int pipe_serves_linear(int M, int N, int K, int64_t lda, int64_t ldb, int K1 = 0) {
-  return idiff::option(idiff::OPT_NO_PIPE) ? PIPE_NO : pipe_fits_linear(M, N, K, lda, ldb, K1);
+int pipe_serves_linear(int M, int N, int K, int64_t lda, int64_t ldb, int K1 = 0, int64_t lda2 = 0) {
+  return idiff::option(idiff::OPT_NO_PIPE) ? PIPE_NO : pipe_fits_linear(M, N, K, lda, ldb, K1, lda2);
 }
 int pipe_serves_conv(int B, int H, int W, int Cin, int Cout, int KH, int KW) {
   const int64_t K = (int64_t)KH * KW * Cin;
@@ -1181,7 +1186,7 @@ namespace {
 // point received it
 struct LinearCall {
   const char *name;                    // of the entry point, for its messages
-  const float *A, *A2;                 // two_src: columns K1.. of A are the columns of A2 (same row pitch)
+  const float *A, *A2;                 // two_src: columns K1.. of A are the columns of A2 (row pitch lda2)
   int K1;
   bool two_src;
   const float *Bt;
@@ -1192,6 +1197,7 @@ struct LinearCall {
   int want;                            // WANT_PIPE; WANT_PAIRS: w_scale (required) for the weight, act_scale for the other operand
   const float *w_scale, *act_scale;
   int weight_is_a;
+  int64_t lda2;                        // two_src: the row pitch of A2 (one source: lda)
 };
 
 // validate, cut on the host if A exceeds one buffer descriptor, fill the kernel arguments, run -- or, `probe`, report the plan of the
@@ -1205,21 +1211,21 @@ int linear_front(const LinearCall &c, hipStream_t st, IgemmPlan *probe) {
   if (c.M == 0 || c.N == 0 || c.batch == 0) { if (probe) probe->family = -1; return 0; }
   if (!c.A || (c.two_src && !c.A2) || !c.Bt || !c.C || (pairs && !c.w_scale)) return fail("%s: null pointer", c.name);
   if (c.K1 % BK) return fail("%s: the split column K1 = %d must be a multiple of %d", c.name, c.K1, BK);
-  if (c.lda < c.K1 || c.lda < c.K - c.K1 || c.ldb < c.K || c.ldc < c.N) return fail("%s: leading dimension smaller than the row length", c.name);
+  if (c.lda < c.K1 || c.lda2 < c.K - c.K1 || c.ldb < c.K || c.ldc < c.N) return fail("%s: leading dimension smaller than the row length", c.name);
   if (pairs && !pairs_geometry_ok(c.M, c.N, c.K, c.batch))
     return fail("%s: M=%d N=%d K=%d batch=%d not served (ask idiff_gemm_pairs_ok)", c.name, c.M, c.N, c.K, c.batch);
   if (c.batch > 65535) return fail("%s: batch %d exceeds grid.y", c.name, c.batch);
   // operands allow 16-byte loads; the pair form is asked for by name and does not read IDIFF_NO_PIPE (idiff_gemm_pairs_ok does)
-  const bool vec = pitches16(c.K, c.lda, c.ldb) && c.strideA % 4 == 0 && c.strideB % 4 == 0 && aligned16(c.A) &&
+  const bool vec = pitches16(c.K, c.lda, c.ldb) && c.lda2 % 4 == 0 && c.strideA % 4 == 0 && c.strideB % 4 == 0 && aligned16(c.A) &&
                    (!c.two_src || aligned16(c.A2)) && aligned16(c.Bt);
-  const int serves = !vec ? PIPE_NO : (pairs ? pipe_fits_linear : pipe_serves_linear)(c.M, c.N, c.K, c.lda, c.ldb, c.K1);
+  const int serves = !vec ? PIPE_NO : (pairs ? pipe_fits_linear : pipe_serves_linear)(c.M, c.N, c.K, c.lda, c.ldb, c.K1, c.lda2);
   if (serves == PIPE_A_BEYOND && c.batch == 1 && !pairs) {
     if (colstats) return fail("%s: colstats is not available for operands beyond 4 GiB", c.name);
     if (const int64_t cut = host_cut_row(c.M, 1, c.ep))
       return run_cut(c.M, cut, c.ep, probe != nullptr, [&](int64_t r0, int64_t r1, const idiff_epilogue *e) {
         LinearCall h = c;
         h.A += r0 * c.lda; h.C += r0 * c.ldc; h.M = (int)(r1 - r0); h.ep = e;
-        if (c.two_src) h.A2 += r0 * c.lda;
+        if (c.two_src) h.A2 += r0 * c.lda2;
         h.strideA = h.strideB = h.strideC = 0;
         return linear_front(h, st, probe);
       });
@@ -1238,19 +1244,19 @@ int linear_front(const LinearCall &c, hipStream_t st, IgemmPlan *probe) {
   }
   if (pairs && colstats && c.batch != 1) return fail("%s: colstats only for unbatched problems", c.name);
   p.a_bytes = (uint32_t)extent_bytes(c.M, c.lda, c.two_src ? c.K1 : c.K); p.b_bytes = (uint32_t)extent_bytes(c.N, c.ldb, c.K);
-  if (c.two_src) { p.A2 = c.A2; p.K1 = c.K1; p.a2_bytes = (uint32_t)extent_bytes(c.M, c.lda, c.K - c.K1); }
+  if (c.two_src) { p.A2 = c.A2; p.K1 = c.K1; p.lda2 = c.lda2; p.a2_bytes = (uint32_t)extent_bytes(c.M, c.lda2, c.K - c.K1); }
   if (pairs) { p.scale_a = c.weight_is_a ? c.w_scale : c.act_scale; p.scale_b = c.weight_is_a ? c.act_scale : c.w_scale; }
   return igemm_run<false>(p, c.batch, c.want, st, probe);
 }
 
 LinearCall linear_call(const char *name, const float *A, int64_t lda, int64_t strideA, const float *Bt, int64_t ldb, int64_t strideB, float *C,
                        int64_t ldc, int64_t strideC, int M, int N, int K, int batch, const idiff_epilogue *ep, int want) {
-  return LinearCall{name, A, nullptr, 0, false, Bt, C, lda, ldb, ldc, strideA, strideB, strideC, M, N, K, batch, ep, want, nullptr, nullptr, 0};
+  return LinearCall{name, A, nullptr, 0, false, Bt, C, lda, ldb, ldc, strideA, strideB, strideC, M, N, K, batch, ep, want, nullptr, nullptr, 0, lda};
 }
-LinearCall linear_call_2src(const char *name, const float *A1, const float *A2, int64_t lda, int K1, const float *Bt, int64_t ldb, float *C,
-                            int64_t ldc, int M, int N, int K, const idiff_epilogue *ep, int want) {
+LinearCall linear_call_2src(const char *name, const float *A1, int64_t lda, const float *A2, int64_t lda2, int K1, const float *Bt, int64_t ldb,
+                            float *C, int64_t ldc, int M, int N, int K, const idiff_epilogue *ep, int want) {
   LinearCall c = linear_call(name, A1, lda, 0, Bt, ldb, 0, C, ldc, 0, M, N, K, 1, ep, want);
-  c.A2 = A2; c.K1 = K1; c.two_src = true;
+  c.A2 = A2; c.lda2 = lda2; c.K1 = K1; c.two_src = true;
   return c;
 }
 }  // namespace
@@ -1272,13 +1278,23 @@ IDIFF_API int idiff_gemm_pairs_f32(const float *A, int64_t lda, int64_t strideA,
 
 IDIFF_API int idiff_gemm_2src_f32(const float *A1, const float *A2, int64_t lda, int K1, const float *Bt, int64_t ldb,
                                   float *C, int64_t ldc, int M, int N, int K, const idiff_epilogue *ep, void *stream) {
-  return linear_front(linear_call_2src("gemm_2src", A1, A2, lda, K1, Bt, ldb, C, ldc, M, N, K, ep, WANT_PIPE), (hipStream_t)stream, nullptr);
+  return linear_front(linear_call_2src("gemm_2src", A1, lda, A2, lda, K1, Bt, ldb, C, ldc, M, N, K, ep, WANT_PIPE), (hipStream_t)stream, nullptr);
+}
+
+IDIFF_API int idiff_gemm_2src_ld_ok(int K1, int K2) {
+  return K1 > 0 && K2 > 0 && K1 % BK == 0 && K2 % 4 == 0 && !idiff::option(idiff::OPT_NO_2SRC_PITCH) && !idiff::option(idiff::OPT_NO_PIPE);
+}
+
+IDIFF_API int idiff_gemm_2src_ld_f32(const float *A1, int64_t lda1, const float *A2, int64_t lda2, int K1, const float *Bt, int64_t ldb,
+                                     float *C, int64_t ldc, int M, int N, int K, const idiff_epilogue *ep, void *stream) {
+  return linear_front(linear_call_2src("gemm_2src_ld", A1, lda1, A2, lda2, K1, Bt, ldb, C, ldc, M, N, K, ep, WANT_PIPE), (hipStream_t)stream,
+                      nullptr);
 }
 
 IDIFF_API int idiff_gemm_pairs_2src_f32(const float *A1, const float *A2, int64_t lda, int K1, const float *act_scale, const float *Bt,
                                         int64_t ldb, const float *w_scale, float *C, int64_t ldc, int M, int N, int K,
                                         const idiff_epilogue *ep, void *stream) {
-  LinearCall c = linear_call_2src("gemm_pairs_2src", A1, A2, lda, K1, Bt, ldb, C, ldc, M, N, K, ep, WANT_PAIRS);
+  LinearCall c = linear_call_2src("gemm_pairs_2src", A1, lda, A2, lda, K1, Bt, ldb, C, ldc, M, N, K, ep, WANT_PAIRS);
   c.w_scale = w_scale; c.act_scale = act_scale;
   return linear_front(c, (hipStream_t)stream, nullptr);
 }

@@ -18,7 +18,7 @@ const char *const kOptionNames[OPT_COUNT] = {"IDIFF_NO_WINOGRAD", "IDIFF_NO_COLS
                                              "IDIFF_TRIDIAG_ONESTAGE", "IDIFF_UFD_ROWS", "IDIFF_CHASE_WAVEFRONT",
                                              "IDIFF_GRAM_SMALL_TILES", "IDIFF_CHASE_SPIN_LIMIT",
                                              "IDIFF_FAKE_CU_COUNT", "IDIFF_SBR_SYNC", "IDIFF_NO_SPLIT",
-                                             "IDIFF_NO_WINO43", "IDIFF_NO_WINO43H", "IDIFF_NO_PAIRS", "IDIFF_PAIRS_MIN_TILES", "IDIFF_NO_FUSED_ATTN", "IDIFF_NO_WINO1D", "IDIFF_NO_FUSED_GN", "IDIFF_NO_FUSED_GN_LOAD", "IDIFF_NO_FUSED_GN_LOAD_2SRC", "IDIFF_NO_FUSED_GN_FIR"};
+                                             "IDIFF_NO_WINO43", "IDIFF_NO_WINO43H", "IDIFF_NO_PAIRS", "IDIFF_PAIRS_MIN_TILES", "IDIFF_NO_FUSED_ATTN", "IDIFF_NO_WINO1D", "IDIFF_NO_FUSED_GN", "IDIFF_NO_FUSED_GN_LOAD", "IDIFF_NO_FUSED_GN_LOAD_2SRC", "IDIFF_NO_FUSED_GN_FIR", "IDIFF_NO_2SRC_PITCH", "IDIFF_NO_FUSED_RES_UP"};
 struct OptionTable {
   int v[OPT_COUNT];
   OptionTable() {

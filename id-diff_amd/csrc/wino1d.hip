@@ -119,6 +119,8 @@ struct Wino1dParams {
   const float *x2;                                 // wino1d_nl2_kernel: input channels [c1, Cin) come from x2 [B, H W, Cin - c1], [0, c1) from x [B, H W, c1]
   uint32_t x2_bytes;
   int c1;
+  int res_up2;                                     // wino1d_kernel<8|16|32>: ep.residual is the LOW-resolution residual [B, (H/2)(W/2), Cout] (pitch Cout,
+  float up_w[16];                                  // res_bytes its extent), upsampled x2 in the tail by the polyphase weights up_w[phase y][phase x][u][v]
 #ifdef IDIFF_W1D_STAMP
   uint64_t *stamps;                                // diagnostic build (scripts/wino1d_stamps.py): 8 ticks of 100 MHz per workgroup
 #endif
@@ -727,7 +729,17 @@ __device__ __forceinline__ void r1_body(const Wino1dParams &p) {
   } else {   // the plain kernel's tail, as it was (not indented: the lines are the ones wino1d_kernel always had)
   // the residual's 16 pixels of a round are requested one phase ahead (round 0: before the first park, round 1: behind round 0's outputs) and
   // arrive behind the parks and barriers
-  float4 res[16];
+  // The up2 state of the residual (p.res_up2, wino1d_kernel<8|16|32> alone): ep.residual is the residual at HALF the resolution and the thread
+  // forms its 16 pixels' values itself -- the FIR x2 of upfirdn2d_nhwc_up2_block, output (2 i + a, 2 j + b) = sum over u, v of
+  // lo[i - 1 + a + u][j - 1 + b + v] * up_w[a][b][u][v] in that kernel's tap order -- from the window its run of pixels needs: UR low-resolution
+  // rows x UC columns (one image row or half of one: 2 x 10; W = 8, two image rows: 3 x 6), requested where the plain state requests its 16
+  // pixels and held in the same registers.  A window entry outside the low-resolution image (row -1 or H/2, column -1 or W/2), or of a row
+  // beyond rows_total, is R1_INVALID: the descriptor's range check returns the zero the FIR's padding is, never a neighbouring row's or image's
+  // value.  Every offset is the range-checked VECTOR offset (the scalar one is not checked).
+  constexpr bool UP2 = NL == 0 && (W == 8 || W == 16 || W == 32);
+  constexpr int UR = W == 8 ? 3 : 2, UC = W == 8 ? 6 : 10;
+  const bool res_up2 = UP2 && p.res_up2 != 0;
+  float4 res[UP2 ? UR * UC : 16];
   auto request_res = [&](int rnd) __attribute__((always_inline)) {
     const uint32_t pxl = (uint32_t)(4 * (64 * rnd + 4 * tl));
     const bool ook = row0 + (int)(pxl / W) < p.rows_total;
@@ -735,13 +747,47 @@ __device__ __forceinline__ void r1_body(const Wino1dParams &p) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) res[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rR, (int)roff, i * ld_res * 4, 0));
   };
+  auto request_up2 = [&](int rnd) __attribute__((always_inline)) {
+    const int pxl = 4 * (64 * rnd + 4 * tl);
+    const int orow = row0 + pxl / W;                               // image * H + y; W = 8: y is even (the run is rows y and y + 1)
+    const bool ook = orow < p.rows_total;
+    const int img = orow / p.H, y = orow - img * p.H;
+    const int hl = p.H >> 1;
+    constexpr int WL = W / 2;
+    const int r0 = (y - 1) >> 1, c0 = ((pxl % W) >> 1) - 1;        // the window's first row and column: -1 at the image's top / left edge
+#pragma unroll
+    for (int k = 0; k < UC; ++k)                                   // column by column: the first pixels' entries arrive first
+#pragma unroll
+      for (int u = 0; u < UR; ++u) {
+        const int r = r0 + u, c = c0 + k;
+        const bool ok = ook && (unsigned)r < (unsigned)hl && (unsigned)c < (unsigned)WL;
+        const uint32_t off = ok ? ((uint32_t)((img * hl + r) * WL + c) * (uint32_t)p.Cout + (uint32_t)n) * 4u : R1_INVALID;
+        res[u * UC + k] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rR, (int)off, 0, 0));
+      }
+  };
+  // pixel i of the run from the window; uw[row of the run][b][u][v]: the phase a of the run's row(s) is chosen by finish
+  auto up2_res = [&](int i, const float (&uw)[2][8]) __attribute__((always_inline)) {
+    const int xr = W == 8 ? (i & 7) : i, rr = W == 8 ? (i >> 3) : 0;
+    const int b = xr & 1, k0 = (xr >> 1) + b;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int v = 0; v < 2; ++v) {
+        const float wt = uw[rr][(b * 2 + u) * 2 + v];
+        const float4 sv = res[(rr + u) * UC + k0 + v];
+        acc.x += sv.x * wt; acc.y += sv.y * wt; acc.z += sv.z * wt; acc.w += sv.w * wt;
+      }
+    return acc;
+  };
   double s1[2][4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}}, s2[2][4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
   // One round's 16 pixels with the epilogue's switches as COMPILE-TIME constants: tested at run time inside the loop every pixel became a chain
   // of scalar branches between its LDS reads and its store and nothing of one pixel overlapped the next -- 9.6 us per workgroup where the
   // constant form took 1.7 (profiles/r05_wino1d_stamps.txt).  ACT < 0: the activation by its run-time code.
   auto finish = [&](auto round_c, auto act_c, auto res_c, auto scaled_c, auto stats_c) __attribute__((always_inline)) {
     constexpr int RND = decltype(round_c)::value, ACT = decltype(act_c)::value;
-    constexpr bool RES = decltype(res_c)::value, SCALED = decltype(scaled_c)::value, STATS = decltype(stats_c)::value;
+    constexpr int RESK = decltype(res_c)::value;                               // the residual: 0 none, 1 plain, 2 up2
+    constexpr bool RES = RESK != 0, SCALED = decltype(scaled_c)::value, STATS = decltype(stats_c)::value;
     // row-tile m of the block is its pixels 4 m .. 4 m + 3 in row-major order
     const uint32_t pxl = (uint32_t)(4 * (64 * RND + 4 * tl));                  // my first pixel, counted from the block's first
     const int orow = row0 + (int)(pxl / W);
@@ -757,6 +803,11 @@ __device__ __forceinline__ void r1_body(const Wino1dParams &p) {
         badd.x += rb.x; badd.y += rb.y; badd.z += rb.z; badd.w += rb.w;
       }
       if (ep.rowscale) sc *= ep.rowscale[img];
+    }
+    float uw[2][8];                                    // up2: the weights of the run's row(s); H is even, so orow's parity is y's
+    if (RESK == 2) {
+#pragma unroll
+      for (int t = 0; t < 8; ++t) { uw[0][t] = (W != 8 && (orow & 1)) ? p.up_w[8 + t] : p.up_w[t]; uw[1][t] = p.up_w[8 + t]; }
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {                      // row-tile 4 tl + j of the round
@@ -783,7 +834,7 @@ __device__ __forceinline__ void r1_body(const Wino1dParams &p) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) y[a][e] = idiff::act_apply(y[a][e], ACT < 0 ? act : ACT);
         }
-        if (RES) { const float4 r = res[4 * j + a]; y[a][0] += r.x; y[a][1] += r.y; y[a][2] += r.z; y[a][3] += r.w; }
+        if (RES) { const float4 r = RESK == 2 ? up2_res(4 * j + a, uw) : res[4 * j + a]; y[a][0] += r.x; y[a][1] += r.y; y[a][2] += r.z; y[a][3] += r.w; }
         if (SCALED) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) y[a][e] *= sc;
@@ -805,15 +856,22 @@ __device__ __forceinline__ void r1_body(const Wino1dParams &p) {
     using ANone = std::integral_constant<int, (int)IDIFF_ACT_NONE>; using AAny = std::integral_constant<int, -1>;
     auto by_stats = [&](auto a, auto r, auto sc_) __attribute__((always_inline)) { if (want_stats) finish(round_c, a, r, sc_, T()); else finish(round_c, a, r, sc_, F()); };
     auto by_scale = [&](auto a, auto r) __attribute__((always_inline)) { if (scaled) by_stats(a, r, T()); else by_stats(a, r, F()); };
-    auto by_res = [&](auto a) __attribute__((always_inline)) { if (has_res) by_scale(a, T()); else by_scale(a, F()); };
+    auto by_res = [&](auto a) __attribute__((always_inline)) {
+      if constexpr (UP2) { if (res_up2) { by_scale(a, I2()); return; } }
+      if (has_res) by_scale(a, I1()); else by_scale(a, I0());
+    };
     if (act == (int)IDIFF_ACT_NONE) by_res(ANone()); else by_res(AAny());
   };
-  if (has_res) request_res(0);
+  auto request = [&](int rnd) __attribute__((always_inline)) {
+    if constexpr (UP2) { if (res_up2) { request_up2(rnd); return; } }
+    request_res(rnd);
+  };
+  if (has_res) request(0);
   park(I0()); park(I1());
   __syncthreads();
   IDIFF_W1D_T(4)
   finish_round(I0());
-  if (has_res) request_res(1);
+  if (has_res) request(1);
   __syncthreads();
   park(I2()); park(I3());
   __syncthreads();
@@ -943,12 +1001,25 @@ IDIFF_API int idiff_wino1d_pack_f32(const float *wt, float *u, int Cin, int Cout
 namespace {
 struct R1GroupNorm { int groups; const float *gamma, *beta; float eps; int act; };
 struct R1NormLoad { const float *coef; int act; const float *x2; int c1; };       // x2 != nullptr: two sources, x [.., c1] and x2 [.., Cin - c1]
+struct R1ResUp { const float *lo; const float *taps; };                            // the residual at half the resolution and its 16 polyphase weights (host)
+
+// the up2 residual's own conditions (the convolution's: r1_geometry_ok): the rows the tail's up2 state is built for, whole 2 x 2 blocks
+bool r1_resup_geometry_ok(int H, int W) { return (W == 8 || W == 16 || W == 32) && H % 2 == 0; }
 
 // the four entry points: gn == nullptr and nl == nullptr is idiff_conv2d_wino1d_f32
 int r1_run(const float *x, const float *u, float *out, int B, int H, int W, int Cin, int Cout, const idiff_epilogue *ep, const R1GroupNorm *gn,
-           const R1NormLoad *nl, void *stream) {
+           const R1NormLoad *nl, void *stream, const R1ResUp *ru = nullptr) {
   using namespace idiff;
   if (B == 0) return 0;
+  if (ru) {
+    // nothing is launched unless the plain tail of wino1d_kernel<8|16|32> finishes this call and the request is its only residual (the entry
+    // point has neither the fused GroupNorm's nor the loader norm's arguments: those combinations cannot be expressed)
+    if (option(OPT_NO_FUSED_RES_UP)) return fail("conv2d_wino1d_resup: switched off (IDIFF_NO_FUSED_RES_UP): ask idiff_conv2d_wino1d_resup_ok");
+    if (!r1_resup_geometry_ok(H, W))
+      return fail("conv2d_wino1d_resup: H=%d W=%d not served: W in {8, 16, 32}, H even (ask idiff_conv2d_wino1d_resup_ok)", H, W);
+    if (!ru->lo || ((uintptr_t)ru->lo & 15) || !ru->taps) return fail("conv2d_wino1d_resup: the low-resolution residual (16-byte aligned) and its 16 weights are required");
+    if (ep && ep->residual) return fail("conv2d_wino1d_resup: the epilogue already carries a residual");
+  }
   const bool two = nl && nl->x2;
   if (nl && (nl->x2 || nl->c1 != Cin)) {
     // two sources: whole K steps from each, each inside one buffer descriptor of its own
@@ -996,6 +1067,13 @@ int r1_run(const float *x, const float *u, float *out, int B, int H, int W, int 
   wino_fill(p, x, u, out, B, H, W, Cin, Cout, (int64_t)R1_NSLOT * Cin * Cout, res_bytes, ep, R1_COUT, false);
   p.rows_total = B * H;
   p.blocks_m = ceil_div(p.rows_total, R1_PIXELS / W);
+  if (ru) {
+    // the low-resolution residual in the residual's place: pitch Cout, a quarter of the output's extent (inside one descriptor with it)
+    p.has_ep = 1; p.ep.residual = ru->lo; p.ep.ld_residual = Cout;
+    p.res_bytes = (uint32_t)((int64_t)B * (H / 2) * (W / 2) * Cout * 4);
+    p.res_up2 = 1;
+    for (int t = 0; t < 16; ++t) p.up_w[t] = ru->taps[t];
+  }
 #ifdef IDIFF_W1D_STAMP
   { const char *e = getenv("IDIFF_W1D_STAMP_PTR"); p.stamps = e ? reinterpret_cast<uint64_t *>(strtoull(e, nullptr, 0)) : nullptr; }
 #endif
@@ -1032,6 +1110,19 @@ int r1_run(const float *x, const float *u, float *out, int B, int H, int W, int 
 IDIFF_API int idiff_conv2d_wino1d_f32(const float *x, const float *u, float *out, int B, int H, int W, int Cin, int Cout,
                                       const idiff_epilogue *ep, void *stream) {
   return r1_run(x, u, out, B, H, W, Cin, Cout, ep, nullptr, nullptr, stream);
+}
+
+// The x2 FIR of an up block's shortcut inside Conv_1's tail (scripts/shortcut_shape_ab.py, profiles/shortcut_shape_ab.txt).
+// IDIFF_NO_FUSED_RES_UP answers no.
+IDIFF_API int idiff_conv2d_wino1d_resup_ok(int B, int H, int W, int Cin, int Cout) {
+  if (!idiff_conv2d_wino1d_ok(B, H, W, Cin, Cout) || idiff::option(idiff::OPT_NO_FUSED_RES_UP)) return 0;
+  return r1_resup_geometry_ok(H, W) ? 1 : 0;
+}
+
+IDIFF_API int idiff_conv2d_wino1d_resup_f32(const float *x, const float *u, float *out, int B, int H, int W, int Cin, int Cout,
+                                            const idiff_epilogue *ep, const float *lo, const float *taps, void *stream) {
+  const R1ResUp ru = {lo, taps};
+  return r1_run(x, u, out, B, H, W, Cin, Cout, ep, nullptr, nullptr, stream, &ru);
 }
 
 IDIFF_API int idiff_conv2d_wino1d_gn_ok(int B, int H, int W, int Cin, int Cout, int groups) {

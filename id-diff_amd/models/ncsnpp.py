@@ -12,7 +12,8 @@ libidiff_hip.so.  What differs from the reference's eager PyTorch graph, by desi
 * the Dense_0 projections of ALL residual blocks are one GEMM (their weights are stacked at load time);
 * ``torch.cat([h, hs.pop()], dim=1)`` (ncsnpp.py:324) is never materialised on its own: GroupNorm reads the
   two sources and writes the concatenated normalised tensor the next conv consumes, and the 1x1 shortcut
-  conv is split into two K-slices accumulated through the residual epilogue;
+  conv is one contraction over its two sources, each at its own row pitch (two K-slices accumulated through the
+  residual epilogue where that form does not serve the widths);
 * FIR resampling calls the same ``upfirdn2d`` kernel as ``op.upfirdn2d`` with minor = C;
 * the V bias of attention is added after P.V (softmax rows sum to one), so V^T can be produced directly
   in the K-contiguous layout the P.V product wants.
@@ -284,6 +285,10 @@ class NCSNpp(NhwcExecutor):
         pk["fir_down"] = torch.tensor(k, device=dev)
         pk["fir_up"] = torch.tensor(k * 4.0, device=dev)
         pk["fir_len"] = int(k.shape[0])
+        # the x2 resampler as four 2 x 2 sub-kernels, for the convolution tail that upsamples its residual itself (_resblock): the kernel
+        # and pads _fir(..., "up") hands to upfirdn2d; a 4-tap kernel only
+        n = pk["fir_len"]
+        pk["fir_up_taps"] = _lib.polyphase_up2(k * 4.0, (n - 2 + 1) // 2 + 1, (n - 2) // 2) if n == 4 else None
         # absolute gain of the resamplers (bound of |output| / max|input|): the whole tap sum without zero insertion, the largest
         # polyphase tap sum with it
         pk["fir_gain"] = {"down": float(np.abs(k).sum()), "pre_conv": float(np.abs(k).sum()),
@@ -375,16 +380,23 @@ class NCSNpp(NhwcExecutor):
                               next_cout=mod.out_ch)
         # shortcut
         if hasattr(mod, "Conv_2") or hasattr(mod, "NIN_0"):
-            # cat[x, x2] with equal row pitch: one two-source contraction; otherwise two K-slices through the residual epilogue
-            fused = x2 is not None and x.C == x2.C and x.C % 32 == 0
+            # cat[x, x2]: one two-source contraction, each source at its own row pitch; otherwise two K-slices through the residual
+            # epilogue (the partial product written and read back).  The pack is kept per form: a switch may change between forwards.
+            fused = x2 is not None and x.C % 32 == 0 and x2.C % 4 == 0 and (x.C == x2.C or _lib.gemm_2src_ld_ok(x.C, x2.C))
             split = x.C if (x2 is not None and not fused) else None
+            form = () if split is None else ("split",)
             if hasattr(mod, "Conv_2"):
-                ws, bs = self._conv_w(pk, (idx, 2), mod.Conv_2, split)
+                ws, bs = self._conv_w(pk, (idx, 2) + form, mod.Conv_2, split)
                 ws = [w.view(w.shape[0], -1) for w in ws] if split is not None else ws.view(ws.shape[0], -1)
             else:
-                ws, bs = self._nin_w(pk, (idx, "nin"), mod.NIN_0, split)
+                ws, bs = self._nin_w(pk, (idx, "nin") + form, mod.NIN_0, split)
             if early_shortcut:
-                sc = resample(self._pointwise(x, ws, None))
+                # where Conv_1's tail upsamples its residual itself, the shortcut stays at the low resolution: no FIR pass, no
+                # full-resolution shortcut written and read back
+                sc = self._pointwise(x, ws, None)
+                up2_taps = self._up2_residual_taps(h, mod.out_ch, pk["fir_up_taps"] if self.fir else None)
+                if up2_taps is None:
+                    sc = resample(sc)
             elif x2 is None:
                 sc = self._pointwise(x, ws, bs)
             elif fused:
@@ -402,6 +414,8 @@ class NCSNpp(NhwcExecutor):
             if (idx, "1+shortcut") not in pk["conv"]:
                 pk["conv"][(idx, "1+shortcut")] = (w1, (b1 + bs).contiguous())
             b1 = pk["conv"][(idx, "1+shortcut")][1]
+            if up2_taps is not None:
+                return self._conv(h, w1, b1, residual_up2=(sc.buf, up2_taps), out_scale=rs, then_norm=True, normed=True)
         return self._conv(h, w1, b1, residual=sc.buf, out_scale=rs, then_norm=True, normed=True)   # next: a GroupNorm_0 / skip
 
     def _attn(self, idx, x, pk):

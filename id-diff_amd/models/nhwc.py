@@ -87,6 +87,11 @@ WINO43_PAIRS_MIN_WORKGROUPS = 256
 # launches of fewer workgroups than this, and maps narrower than this, stay on the 2-D pair kernel
 WINO1D_MIN_WORKGROUPS = 256
 WINO1D_MIN_WIDTH = 4
+# The x2 FIR of an up block's shortcut in Conv_1's tail (NhwcExecutor._up2_residual_taps) is routed where it was measured faster than the
+# resampler's pass beyond the repetitions' spread (scripts/shortcut_shape_ab.py, profiles/shortcut_shape_ab.txt, B = 2240, 256 -> 256, us):
+# 8 -> 16: 210 + 1090 against 1084 (-216, spread 30); 16 -> 32: 782 + 4404 against 4422 (-765, spread 64); 4 -> 8: 44 + 327 against 316
+# (-55, spread 58: inside it, not routed although the kernel serves rows of 8 pixels).
+RESUP_MIN_WIDTH = 16
 
 
 def _wino43_workgroups(B, H, W, cout):
@@ -239,8 +244,10 @@ class NhwcExecutor(HipScoreModel):
         _lib.groupnorm_coef(*x.stats, x.C, *s2.stats, s2.C, B, x.H * x.W, gn.num_groups, gn.eps, gn.weight.detach(), gn.bias.detach(), coef)
         return _T(x.buf, x.H, x.W, C, norm=norm, pending=pending._replace(coef=coef))
 
-    def _conv(self, x, wt, bias, stride=1, pad=1, pad_hi=None, normed=False, then_norm=None, **ep):
+    def _conv(self, x, wt, bias, stride=1, pad=1, pad_hi=None, normed=False, then_norm=None, residual_up2=None, **ep):
         """``then_norm``: what reads the output.  True: a GroupNorm -> ask the epilogue for the per-tile column sums (``stats``).
+        ``residual_up2 = (lo, taps)``: the residual at half the resolution, upsampled x2 by the FIR of the polyphase weights ``taps`` in the
+        convolution's tail (_lib.with_residual_up2); only the ``wino1d`` route serves it and the caller has asked (_up2_residual_taps).
         ``(gn, act)`` (_conv_gn_act's argument): that GroupNorm, unmodulated, and nothing else -> where the row-wise kernel applies it in
         its own tail the result is the GroupNorm's output (``is_normed``, no ``stats``), otherwise the convolution's with its column sums.
         ``normed=True``: the input is the output of a GroupNorm (+ activation, + FIR resampling), i.e. bounded by
@@ -250,7 +257,9 @@ class NhwcExecutor(HipScoreModel):
         y, geom, route = self._conv_route(x, wt, stride, pad, pad_hi, normed, ep)
         x = self._settle_pending(x, route, geom)
         if route is not None:
-            return self._conv3x3(route, x, wt, bias, y, geom, then_norm, ep)
+            return self._conv3x3(route, x, wt, bias, y, geom, then_norm, ep, residual_up2)
+        if residual_up2 is not None:
+            raise RuntimeError("_conv: an upsampled residual for a convolution off the 3x3 routes")
         kh, kw = wt.shape[1:3]
         if then_norm:
             self._colstats(y, _lib.conv2d_colstats_split(*geom, kh, kw, stride, pad, pad_hi), ep)
@@ -282,7 +291,19 @@ class NhwcExecutor(HipScoreModel):
             return x
         return self._gn_act(p.src, p.gn, p.act, p.src2)
 
-    def _conv3x3(self, route, x, wt, bias, y, geom, then_norm, ep):
+    def _up2_residual_taps(self, x, cout, taps):
+        """``taps`` where the 3x3 convolution of ``x`` (a GroupNorm's output) to ``cout`` channels adds a residual given at half the
+        resolution in its own tail: the ``wino1d`` route, no norm pending for its loader, the kernel's query (rows of 8 / 16 / 32 pixels;
+        IDIFF_NO_FUSED_RES_UP answers no).  Otherwise None: the caller upsamples the residual itself."""
+        if taps is None or x.pending is not None or x.norm is None or x.W < RESUP_MIN_WIDTH:
+            return None
+        geom = (x.buf.shape[0], x.H, x.W, x.C, cout)
+        route = conv3x3_route(*geom, self._pairs_ok(x.norm, transform=True), True)
+        if route is None or route.name != "wino1d" or not _lib.conv2d_wino1d_resup_ok(*geom):
+            return None
+        return taps
+
+    def _conv3x3(self, route, x, wt, bias, y, geom, then_norm, ep, residual_up2=None):
         """_conv on one of CONV3X3_ROUTES: the filter bank, the epilogue with what rides beside it, one launch."""
         form = route.form(*geom)
         # the transformed filter bank is cached beside the panel; the entry keeps `wt` so that its id cannot be reused while it lives
@@ -303,6 +324,8 @@ class NhwcExecutor(HipScoreModel):
         elif x.pending is not None:
             p = x.pending
             epilogue = _lib.with_normload(epilogue, p.coef, p.act, *((None, None) if p.src2 is None else (p.src2.buf, p.src.C)))
+        if residual_up2 is not None:        # (every launcher but conv2d_wino1d's plain form refuses the request: never dropped)
+            epilogue = _lib.with_residual_up2(epilogue, *residual_up2)
         getattr(_lib, route.launch)(x.buf, bank[key][1], y.buf, *geom, epilogue=epilogue, **form)
         return y
 

@@ -60,7 +60,9 @@ const char *idiff_variant_flags(void);
  * IDIFF_NO_FUSED_GN_LOAD_2SRC (idiff_conv2d_wino1d_normload_2src_ok answers 0: the GroupNorm of cat[x1, x2] in front of a row-wise
  * convolution stays a pass of its own), IDIFF_NO_FUSED_GN_FIR (idiff_upfirdn2d_gn_ok answers 0: the GroupNorm in front of the FIR
  * resampling of an up / down block stays a pass of its own), IDIFF_NO_PAIRS (idiff_gemm_pairs_ok answers 0: the 1x1
- * projections behind a GroupNorm stay on idiff_gemm_f32's six-product form), IDIFF_PAIRS_MIN_TILES (tests: the number of 128 x 128
+ * projections behind a GroupNorm stay on idiff_gemm_f32's six-product form), IDIFF_NO_2SRC_PITCH (idiff_gemm_2src_ld_ok answers 0: the
+ * shortcut of cat[h, skip] with sources of different widths stays two contractions), IDIFF_NO_FUSED_RES_UP (idiff_conv2d_wino1d_resup_ok
+ * answers 0: the shortcut of an up block is upsampled by a pass of its own), IDIFF_PAIRS_MIN_TILES (tests: the number of 128 x 128
  * tiles from which idiff_gemm_pairs_ok answers 1; default 256).
  * Returns the previous value, -1 for an unknown name.  No reference counterpart. */
 int idiff_set_option(const char *name, int value);
@@ -222,6 +224,15 @@ int idiff_gemm_pairs_2src_f32(const float *A1, const float *A2, int64_t lda, int
  * layerspp.py:271-274) without materialising the concatenation or an intermediate partial product.  K1 % 32 == 0. */
 int idiff_gemm_2src_f32(const float *A1, const float *A2, int64_t lda, int K1, const float *Bt, int64_t ldb, float *C,
                         int64_t ldc, int M, int N, int K, const idiff_epilogue *ep, void *stream);
+/* The same with a row pitch per source, A1 (M x K1) at lda1 and A2 (M x (K - K1)) at lda2: cat[h, skip] of two tensors of different
+ * channel counts (256 + 128 in the up path of the flagship network), which otherwise takes two contractions and a partial product
+ * written and read back through the residual term.  K1 % 32 == 0, (K - K1) % 4 == 0; each source inside one buffer descriptor, or the
+ * rows are cut in two on the host (both sources shifted).  idiff_gemm_2src_f32 is this call with lda2 = lda1.
+ *   idiff_gemm_2src_ld_ok   1 where the executor should take this form for sources of K1 and K2 columns; 0 under IDIFF_NO_2SRC_PITCH
+ *                           (A/B runs: the two-contraction path returns) and IDIFF_NO_PIPE.  Launches nothing. */
+int idiff_gemm_2src_ld_ok(int K1, int K2);
+int idiff_gemm_2src_ld_f32(const float *A1, int64_t lda1, const float *A2, int64_t lda2, int K1, const float *Bt, int64_t ldb, float *C,
+                           int64_t ldc, int M, int N, int K, const idiff_epilogue *ep, void *stream);
 
 /* 2-D convolution, NHWC activations: x [B, H, W, Cin] (Cin % 4 == 0), weights packed as
  * wt [Cout, KH, KW, Cin] (= the reference's [Cout, Cin, KH, KW] nn.Conv2d weight permuted once at load),
@@ -379,6 +390,18 @@ int idiff_conv2d_wino1d_normload_f32(const float *x, const float *u, float *out,
 int idiff_conv2d_wino1d_normload_2src_ok(int B, int H, int W, int C1, int C2, int Cout);
 int idiff_conv2d_wino1d_normload_2src_f32(const float *x1, int C1, const float *x2, int C2, const float *u, float *out, int B, int H, int W,
                                           int Cout, const idiff_epilogue *ep, const float *coef, int act, void *stream);
+
+/* The plain form with its residual given at HALF the resolution: lo [B, (H/2) * (W/2), Cout] (pitch Cout, 16-byte aligned) is upsampled x2 in
+ * the tail by the FIR whose 16 polyphase weights are taps[a][b][u][v] (host memory; passed on as kernel arguments): output pixel
+ * (2 i + a, 2 j + b) receives sum over u, v of lo[i - 1 + a + u][j - 1 + b + v] * taps[a][b][u][v], samples outside lo counting as zero --
+ * upfirdn2d with up = 2, a 4 x 4 kernel and pads (2, 1), i.e. the shortcut of an up block (W_s . x before the upsampling) without the
+ * resampler's pass and without the full-resolution shortcut.  ep->residual must be NULL; everything else of the epilogue as in the plain form.
+ *   idiff_conv2d_wino1d_resup_ok   1 where this form is served: idiff_conv2d_wino1d_ok, W in {8, 16, 32}, H even; 0 under
+ *                                  IDIFF_NO_FUSED_RES_UP.
+ *   idiff_conv2d_wino1d_resup_f32  anything else is refused (IDIFF_EINVAL, nothing launched). */
+int idiff_conv2d_wino1d_resup_ok(int B, int H, int W, int Cin, int Cout);
+int idiff_conv2d_wino1d_resup_f32(const float *x, const float *u, float *out, int B, int H, int W, int Cin, int Cout, const idiff_epilogue *ep,
+                                  const float *lo, const float *taps, void *stream);
 
 /* ------------------------------------------------------------------ normalisation / pointwise (HBM-bound) */
 
